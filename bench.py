@@ -7,6 +7,14 @@ compute mode, synthetic data; one "step" = one train_iter_func-equivalent evalua
 cost + full gradient + alpha + Li back on the host.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4|C5|H] [--dtype f32|f64] [--rows N]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` = K / wall time of the K steps, `ms_per_step`
+= its inverse in ms; `stages_ms`, `roofline` and `secondary.featuremap/gram/xtz` come from the hipEvents of those same steps.
+--dump-outputs DIR writes what the last timed step returned (cost, grad, alpha, Li) as DIR/<name>.npy in float64; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  --full adds everything
+that takes runs of its own, described below (box probe, host-array leg, fp64 / plain fp32 / f16x3 legs with their parity
+blocks, the function triple and the on-device loop, CPU baselines).
 
 --gpus N > 1 without a torchrun environment: this process (which touches no GPU) starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD, relays rank 0's JSON line
@@ -14,12 +22,12 @@ and exits with the child's code.  Under torchrun (the driver's launch) every ran
 one rank per GPU over RCCL, the N rows sharded over the ranks (strong scaling -- total work fixed, as
 the metric is quoted at fixed N), three all-reduces per evaluation.  Rank 0 prints ONE JSON line.
 
-Before the timed loop a ~100 ms BOX PROBE (scfgp_box_probe: register-only fp32 MFMA loop, sustained clock, streaming copy)
+With --full, before the timed loop a ~100 ms BOX PROBE (scfgp_box_probe: register-only fp32 MFMA loop, sustained clock, streaming copy)
 is printed as `secondary.box`, so lines from different leases of the pool can be normalised.  With more than one rank the
 three sums over ranks are bracketed by events on the stream they run on: `stages_ms.exchange1..3`, `comm_share`, and
 `stages_ms_max_over_ranks` (one small all-reduce after the loop).
 
-In the default single-GPU run at config H the same process then also runs the fp64 engine (the
+With --full, in a single-GPU run at config H the same process then also runs the fp64 engine (the
 reference's arithmetic, SCFGP/SCFGP.py:95-96,138) on the same rows: `secondary.f64` and the
 fp32-vs-fp64 `parity_at_size` block, and times the CPU restatements on a bounded sample (`cpu_baseline`).
 """
@@ -71,6 +79,12 @@ def parse_args(argv=None):
                     help='the three sums by the library itself (scfgp_comm_init: ncclAllReduce on its own stream) instead of torch.distributed')
     ap.add_argument('--opt', action='append', default=[], metavar='NAME=VALUE',
                     help='scfgp_set_option on the benchmarked engine (tuning runs only; the bench line records it)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MiB in all)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the measurements that take runs of their own: box probe, host-array leg, fp64 / plain fp32 / f16x3 '
+                         'legs and parity, function triple and on-device loop, CPU baselines (--no-secondary / --no-cpu / --triple '
+                         'select among them)')
     a = ap.parse_args(argv)
     N, D, S, M, dt, label = CONFIGS[a.config]
     a.custom = any(v is not None for v in (a.rows, a.D, a.S, a.M))
@@ -213,6 +227,30 @@ def box_probe(device):
 
 def rel(a, b):
     return float(np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300))
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """[(name, array)] -> d/<name>.npy in float64.  When the whole set would pass DUMP_LIMIT bytes, the largest arrays are
+    replaced, largest first, by a fixed sample of their entries (seeded, flat indices in ascending order) in d/<name>.npy and
+    those flat indices in d/<name>_index.npy (float64: exact below 2**53), so that the same arguments give the same files."""
+    os.makedirs(d, exist_ok=True)
+    arrays = [(n, np.ascontiguousarray(np.asarray(v, dtype=np.float64))) for n, v in arrays]
+    over = sum(v.nbytes for _, v in arrays) + (1 << 20) - DUMP_LIMIT          # 1 MiB kept for the .npy headers
+    files = {}
+    for name, v in sorted(arrays, key=lambda nv: -nv[1].nbytes):
+        if over > 0 and v.size > 1:
+            keep = int(max(min(v.size - 1, (v.nbytes - over) // 16), 1))      # a kept entry costs its value and its index
+            idx = np.sort(np.random.default_rng(SEED).choice(v.size, keep, replace=False))
+            over -= v.nbytes - 16 * keep
+            files[name + '_index'] = idx.astype(np.float64)
+            v = v.ravel()[idx]
+        files[name] = v
+    for name, v in files.items():
+        np.save(os.path.join(d, name + '.npy'), v)
+    return sorted(files)
 
 
 def _timed_leg(eng, steps, warmup):
@@ -388,7 +426,7 @@ def main(a):
     lo, hi = shard_rows(N, rank, world)
     # the probe runs before the engine exists (its own stream, its 2 GiB freed again); building the problem below takes seconds
     # of host work, so the chip's clock and thermal state have settled again when the warm-up starts
-    box = box_probe(local) if rank == 0 else None
+    box = box_probe(local) if rank == 0 and a.full else None
     eng = HipEngine(D, S, M, dtype=a.dtype, device=local, stream=torch.cuda.current_stream().cuda_stream)
     for kv in a.opt:
         eng.set_option(kv.split('=')[0], int(kv.split('=')[1]))
@@ -434,6 +472,9 @@ def main(a):
         dist.all_reduce(smax, op=dist.ReduceOp.MAX)
         stage_max = dict(zip(stage_names, [float(v) for v in smax.tolist()]))
     cond = eng.condition()
+
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, [('cost', cost), ('grad', grad), ('alpha', alpha), ('Li', Li)])
 
     if rank == 0:
         ms_step = dt / a.steps * 1e3
@@ -507,8 +548,9 @@ def main(a):
         }
         for v in out["secondary"].values():
             v["frac"] = v["achieved"] / v["peak"]
-        out["secondary"]["box"] = box
-        if world == 1 and not a.no_secondary:
+        if a.full:
+            out["secondary"]["box"] = box
+        if a.full and world == 1 and not a.no_secondary:
             # the same evaluation when the caller hands over HOST arrays every call (what the reference's Theano functions
             # receive, SCFGP/SCFGP.py:237): upload of X, y over PCIe from pageable memory + packing + evaluation.  Never `value`.
             ts = []
@@ -521,15 +563,15 @@ def main(a):
                                                   "note": "scfgp_eval with host X, y on every call (median of 3); resident-data rate is `value`"}
         # the fp64 leg and the fp32-vs-fp64 parity block: at the headline shape and at the two other 1e6-row fp32 configs (C3's
         # D = 8 makes A ill-conditioned: that is where fp32 products cost the most accuracy, and the line says so)
-        if world == 1 and a.config in ('H', 'C3', 'C5') and a.dtype == 'f32' and not a.custom and not a.no_secondary:
+        if a.full and world == 1 and a.config in ('H', 'C3', 'C5') and a.dtype == 'f32' and not a.custom and not a.no_secondary:
             out["secondary"]["f64"], out["parity_at_size"], plain, f16 = f64_leg_and_parity(
                 X, y, params, D, S, M, local, (cost, grad, alpha, Li), eng)
             out["secondary"]["f16x3"] = f16
             if plain is not None:
                 out["secondary"]["plain_fp32"] = plain
-        if world == 1 and not a.no_secondary and a.dtype == 'f32' and (not a.custom or a.triple):
+        if a.full and world == 1 and not a.no_secondary and a.dtype == 'f32' and (not a.custom or a.triple):
             out["secondary"]["through_triple"] = through_triple(X, y, params, D, S, M, local)
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(X, y, params, S, M, N, a.cpu_rows)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

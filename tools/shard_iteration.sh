@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-shard_iter}
 mkdir -p $O
 for rows in 1000000 125000; do
-  timeout -k 10 600 python3 bench.py --rows $rows --steps 10 --warmup 3 --no-cpu --triple > $O/rows_$rows.json 2> $O/rows_$rows.err || { tail $O/rows_$rows.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --rows $rows --steps 10 --warmup 3 --no-cpu --triple > $O/rows_$rows.json 2> $O/rows_$rows.err || { tail $O/rows_$rows.err; exit 1; }
 done
 python3 - <<PY
 import json
