@@ -130,6 +130,17 @@ int scfgp_predict_raw(scfgp_ctx* ctx, const double* Xs_raw, int64_t T, const dou
 int scfgp_set_y_scaler(scfgp_ctx* ctx, int mode, double min, double max, double boxcox, double mu, double std);
 int scfgp_predict_y(scfgp_ctx* ctx, const double* Xs_raw, int64_t T, const double* alpha, const double* Li,
                     const double* ys, double* mu_y, double* std_y, double* metrics);
+/* Gradients of the predictive mean and std in the inputs.  mu, std (T doubles each) as the predict call of `mode` returns them, bit
+ * for bit; dmu, dstd (T x D row-major) their derivatives in the inputs that call takes:
+ *   mode 0  scaled Xs, as scfgp_predict: d mu / d x, d std / d x
+ *   mode 1  column-selected raw Xs through the registered X scaler, as scfgp_predict_raw: the same chained through the derivative of
+ *           the scaler's forward transform, column by column
+ *   mode 2  mode 1 and the y scaler, as scfgp_predict_y: mu, std are mu_y, std_y; dmu = bw'(mu) d mu,
+ *           dstd = (bw'(mu + std) (d mu + d std) - bw'(mu - std) (d mu - d std)) / 2 (bw = the y scaler's backward transform)
+ * dstd may be NULL: then only the mean gradient is formed (no V* = Phi* B product).  SCFGP_EARG for bad arguments, a missing scaler
+ * (modes 1, 2) or parameters not set. */
+int scfgp_predict_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int mode,
+                       double* mu, double* std, double* dmu, double* dstd);
 
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded

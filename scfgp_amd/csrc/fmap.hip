@@ -271,6 +271,31 @@ __device__ __forceinline__ double scale_x(double x, int mode, const double* __re
     const double z = (bc - mu) / sd;
     return mode == 4 ? z : 0.5 * erfc(-z * 0.70710678118654752440);
 }
+// d scale_x / dx (scfgp_predict_grad in raw inputs): 1 / (max - min), 1 / std, the normal pdf, and through the Box-Cox map
+// d sign(t)|t|^lm / dt / lm = |t|^(lm - 1)
+__device__ __forceinline__ double scale_x_deriv(double x, int mode, const double* __restrict__ sp, int D, int d) {
+    if (mode == 0) return 1.0;
+    const double mn = sp[d], mx = sp[D + d], lm = sp[2 * D + d], mu = sp[3 * D + d], sd = sp[4 * D + d];
+    const double inv_sqrt_2pi = 0.39894228040143267794;
+    if (mode == 1) return 1.0 / (mx - mn);
+    if (mode == 2) return 1.0 / sd;
+    if (mode == 3) { const double z = (x - mu) / sd; return inv_sqrt_2pi * exp(-0.5 * z * z) / sd; }
+    const double t = (x - mn) / (mx - mn);
+    const double bc = ((t < 0 ? -1.0 : (t > 0 ? 1.0 : 0.0)) * pow(fabs(t), lm) - 1.0) / lm;
+    const double z = (bc - mu) / sd, dz = pow(fabs(t), lm - 1.0) / ((mx - mn) * sd);
+    return mode == 4 ? dz : inv_sqrt_2pi * exp(-0.5 * z * z) * dz;
+}
+__global__ void xgrad_kernel(const double* __restrict__ Xraw, int64_t total, int D, int mode, const double* __restrict__ sp,
+                             double* __restrict__ dmu, double* __restrict__ dstd) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const double f = scale_x_deriv(Xraw[e], mode, sp, D, (int)(e % D));
+        dmu[e] *= f;
+        if (dstd) dstd[e] *= f;
+    }
+}
+void xgrad_chunk(const double* Xraw, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st) {
+    hipLaunchKernelGGL(xgrad_kernel, dim3(2048), dim3(256), 0, st, Xraw, n * D, D, mode, sp, dmu, dstd);
+}
 __global__ void pack_data_kernel(const double* __restrict__ Xraw, const double* __restrict__ yraw, const int64_t* __restrict__ idx,
                                  double* __restrict__ Xt, double* __restrict__ y, int D, int Dp, int64_t N, int64_t Np,
                                  int mode, const double* __restrict__ sp) {

@@ -219,6 +219,22 @@ void ypost_chunk(double* mu, double* sd, const double* ys, int64_t n, int mode, 
 // out[6] = MAE, NMAE, MSE, NMSE, MNLP, SCORE from nparts x 4 partial sums over n targets
 void ypost_metrics(const double* part, int nparts, int64_t n, double* out, hipStream_t st);
 
+// ---- predgrad.hip, gradients of predict in its inputs (scfgp_predict_grad) ---------------------------------------------
+// columns of the typed operand FT = Fall^T (rows d >= D zero): a multiple of 16 that the launches' column tiles cover
+int predgrad_ft_cols(int D);
+// FT (round_up(J,16) x predgrad_ft_cols(D), type T) from Fall; rows j >= J and columns d >= D zero
+template <typename T> void predgrad_operand(const Geom& g, const double* Fall, T* FT, hipStream_t st);
+// dmu[n][d] = sum_j Fall[d][j] (phi_c alpha_s - phi_s alpha_c)_nj and, dstd != NULL, dstd[n][d] = kappa / sd_n sum_j Fall[d][j]
+// (phi_c V_s - phi_s V_c)_nj, V = Phi B; n < N, d < D (ld D)
+template <typename T>
+void predgrad(const Geom& g, const T* Phi, const T* V, const double* alpha, const T* FT, const double* sd, const Scal* sc, double* dmu,
+              double* dstd, hipStream_t st);
+// chain rules of the scalers, in place on n x D gradients (dstd may be NULL): xgrad_chunk multiplies column d by the derivative of
+// the packing transform at the raw input Xraw[n][d] (modes of pack_data); ygrad_chunk turns d mu, d std into those of mu_y = bw(mu) and
+// std_y = (bw(mu + std) - bw(mu - std)) / 2 (mu, sd: the scaled predictions of the same rows, before ypost_chunk)
+void xgrad_chunk(const double* Xraw, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st);
+void ygrad_chunk(const double* mu, const double* sd, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st);
+
 // ---- on-device update rules (SCFGP/Optimizer.py) --------------------------------------------
 struct OptHyper { double lr, b1, b2, eps, momentum; };   // b1 doubles as rho for rmsprop/adadelta; momentum < 0: no Nesterov
 // theta <- rule(theta, grad); st = [s1 | s2 | velocity]; tctr[0] = step counter, tctr[1] = index into hist

@@ -343,6 +343,35 @@ __device__ __forceinline__ double y_backward(double x, int mode, const double* _
     const double ib = (u < 0 ? -1.0 : (u > 0 ? 1.0 : 0.0)) * pow(fabs(u), 1.0 / lm);
     return ib * (mx - mn) + mn;
 }
+// d y_backward / dx (scfgp_predict_grad mode 2); ppf' = 1 / pdf(ppf), d sign(u)|u|^(1/lm) / dt = |u|^(1/lm - 1) for u = t lm + 1
+__device__ __forceinline__ double y_backward_deriv(double x, int mode, const double* __restrict__ sp) {
+    const double mn = sp[0], mx = sp[1], lm = sp[2], mu = sp[3], sd = sp[4];
+    const double inv_sqrt_2pi = 0.39894228040143267794;
+    if (mode == 0) return 1.0;
+    if (mode == 1) return mx - mn;
+    if (mode == 2) return sd;
+    if (mode == 3) { const double z = norm_ppf(x); return 1.0 / (inv_sqrt_2pi * exp(-0.5 * z * z) * sd); }
+    double t, dt;
+    if (mode == 4) { t = x * sd + mu; dt = sd; }
+    else { const double z = norm_ppf(x); t = z * sd + mu; dt = sd / (inv_sqrt_2pi * exp(-0.5 * z * z)); }
+    return (mx - mn) * pow(fabs(t * lm + 1.0), 1.0 / lm - 1.0) * dt;
+}
+__global__ __launch_bounds__(256) void ygrad_kernel(const double* __restrict__ mu, const double* __restrict__ sd, int64_t total, int D,
+                                                    int mode, const double* __restrict__ sp, double* __restrict__ dmu,
+                                                    double* __restrict__ dstd) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t n = e / D;
+        const double m = mu[n], gm = dmu[e];
+        if (dstd) {
+            const double s = sd[n], gs = dstd[e];
+            dstd[e] = 0.5 * (y_backward_deriv(m + s, mode, sp) * (gm + gs) - y_backward_deriv(m - s, mode, sp) * (gm - gs));
+        }
+        dmu[e] = y_backward_deriv(m, mode, sp) * gm;
+    }
+}
+void ygrad_chunk(const double* mu, const double* sd, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st) {
+    hipLaunchKernelGGL(ygrad_kernel, dim3(2048), dim3(256), 0, st, mu, sd, n * D, D, mode, sp, dmu, dstd);
+}
 __global__ __launch_bounds__(1024) void ymean_kernel(const double* __restrict__ ys, int64_t n, double* __restrict__ out) {
     __shared__ double red[1024];
     double s = 0;

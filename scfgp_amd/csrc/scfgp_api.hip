@@ -180,6 +180,9 @@ struct scfgp_ctx {
     int ys_mode = 0; double* d_yscale = nullptr;                 // y scaler for scfgp_predict_y (5 doubles)
     // predict chunk buffers
     double *p_Xt = nullptr, *p_vpart = nullptr, *p_mupart = nullptr; void *p_Phi = nullptr;
+    // ... and those of scfgp_predict_grad, allocated by its first call: FT = Fall^T typed; with the std gradient C = Phi* Li^T, V = C Li
+    // (PRED_ROWS x Kp each, typed) and the typed Li
+    void *p_FT = nullptr, *p_C = nullptr, *p_V = nullptr, *p_Li = nullptr;
     // on-device optimiser + captured training iteration
     int opt_algo = -1; OptHyper opt_h{}; double *d_opt = nullptr, *d_tctr = nullptr, *d_hist = nullptr; int hist_cap = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; int64_t graph_N = -1; bool in_train = false, warm = false;
@@ -450,6 +453,7 @@ extern "C" void scfgp_destroy(scfgp_ctx* c) {
     dfree(c->d_Abar); dfree(c->d_BT); dfree(c->d_AbarT); dfree(c->d_B16); dfree(c->d_f16scale); dfree(c->d_f16tmp); dfree(c->d_vecs); dfree(c->d_scalars); dfree(c->d_yy);
     dfree(c->d_flag); dfree(c->d_partial); dfree(c->d_work); dfree(c->d_grad);
     dfree(c->p_Xt); dfree(c->p_vpart); dfree(c->p_mupart); dfree(c->p_Phi);
+    dfree(c->p_FT); dfree(c->p_C); dfree(c->p_V); dfree(c->p_Li);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->graph) hipGraphDestroy(c->graph);
     dfree(c->d_opt); dfree(c->d_tctr); dfree(c->d_hist);
@@ -685,6 +689,20 @@ template <typename T> struct Impl {
         SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
         SK::apply_predict(g, (const T*)c->p_Phi, Bt, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);           // Bt = Li^T
         SK::rowpredict(g, c->p_mupart, c->p_vpart, c->d_sc, mu, sd, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // after predict_chunk: d mu / d x~ and (dstd != NULL) d sigma / d x~ of the chunk's rows (predgrad.hip).  V* = Phi* B in the factor
+    // form C = Phi* Li^T, V = C Li (pass 2's level-2 products, loader-staged tiles): its rounding errors grow with sqrt(cond(A)) where
+    // those of V = Phi* B formed directly grow with cond(A).  The by-products vpart / mupart of apply_c land in the chunk's partials,
+    // which rowpredict has consumed.
+    static int predict_grad_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, const double* sd, double* dmu, double* dstd) {
+        if (dstd) {
+            SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart,
+                        c->st, 0);
+            SK::apply_vc(g, (const T*)c->p_C, (const T*)c->p_Li, LiT, (T*)c->p_V, c->st, 0);
+        }
+        predgrad<T>(g, (const T*)c->p_Phi, (const T*)c->p_V, c->alpha_pred(), (const T*)c->p_FT, sd, c->d_sc, dmu, dstd, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
@@ -1031,11 +1049,29 @@ extern "C" int scfgp_eval_rows(scfgp_ctx* c, const int64_t* idx, int64_t n, int 
     return run_eval(c, want_grad, cost, grad, alpha, Li, true);
 }
 
+// buffers of scfgp_predict_grad beside predict's own (first call only; the std gradient's on its first call)
+static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
+    const Geom& g = c->g;
+    const int64_t Kp = g.Kp;
+    const size_t ts = c->tsize();
+    int rc;
+    if (!c->p_FT && (rc = dmalloc(c, &c->p_FT, ts * round_up(g.J, 16) * predgrad_ft_cols(g.D)))) return rc;
+    if (want_std && !c->p_V) {
+        if ((rc = dmalloc(c, &c->p_Li, ts * Kp * Kp))) return rc;
+        if ((rc = dmalloc(c, &c->p_C, ts * PRED_ROWS * Kp))) return rc;
+        if ((rc = dmalloc(c, &c->p_V, ts * PRED_ROWS * Kp))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->p_C, 0, ts * PRED_ROWS * Kp, c->st));
+        HIPCHK(c, hipMemsetAsync(c->p_V, 0, ts * PRED_ROWS * Kp, c->st));
+    }
+    return SCFGP_OK;
+}
+
 // raw_mode: apply the registered X scaler while packing; post: y-scaler backward transform of the outputs on
-// the device and, with targets ys, the six validation metrics
+// the device and, with targets ys, the six validation metrics; dmu != NULL: also the gradients of mu (and, dstd != NULL, of std) in
+// the inputs, T x D each (scfgp_predict_grad)
 static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
                         double* mu, double* sd, int raw_mode, int post = 0, const double* ys = nullptr,
-                        double* metrics = nullptr) {
+                        double* metrics = nullptr, double* dmu = nullptr, double* dstd = nullptr) {
     if (!c || !Xs || !alpha || !Li || !mu || !sd || T < 1) { if (c) c->err = "predict: bad arguments"; return SCFGP_EARG; }
     if (!c->have_params) { c->err = "predict: parameters not set"; return SCFGP_EARG; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1051,6 +1087,8 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
         if ((rc = dmalloc(c, &c->p_Phi, ts * PRED_ROWS * Kp))) return rc;
         HIPCHK(c, hipMemsetAsync(c->p_Phi, 0, ts * PRED_ROWS * Kp, c->st));
     }
+    const bool grad = dmu != nullptr;
+    if (grad && (rc = ensure_pred_grad(c, dstd != nullptr))) return rc;
     // Li (K x K host) -> T1 (Kp x Kp, identity padding); typed transposed copy -> AbarT scratch
     DevTmp raw, d_out, d_ys, d_part;                              // Li / two chunks of Xs | mu, sd of all T rows | targets, mean, metrics | chunk partials
     const int64_t rawstride = PRED_ROWS * g0.D;
@@ -1065,6 +1103,18 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     const void* Bt = c->d_AbarT;                                  // AbarT is scratch outside adjoint..pass3
     if (c->dtype == SCFGP_F32) SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
     else SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
+    DevTmp d_grad;                                                // dmu | dstd of all T rows (T x D each)
+    if (grad) {
+        if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D * (dstd ? 2 : 1)))) return rc;
+        if (c->dtype == SCFGP_F32) {
+            predgrad_operand(g0, c->d_Fall, (float*)c->p_FT, c->st);
+            if (dstd) SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
+        } else {
+            predgrad_operand(g0, c->d_Fall, (double*)c->p_FT, c->st);
+            if (dstd) SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
+        }
+    }
+    double* d_dmu = d_grad; double* d_dsd = grad && dstd ? d_grad + T * g0.D : nullptr;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     const int nchunks = (int)((T + PRED_ROWS - 1) / PRED_ROWS);
     if (post && ys) {
@@ -1099,10 +1149,21 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
         g.N = std::min<int64_t>(PRED_ROWS, T - t0); g.Np = round_up(g.N, 256);
         HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
         pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, raw_mode ? c->xs_mode : 0, c->d_xscale);
-        HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
+        if (!grad) HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
         rc = c->dtype == SCFGP_F32 ? Impl<float>::predict_chunk(c, g, (const float*)Bt, d_mu + t0, d_sd + t0)
                                    : Impl<double>::predict_chunk(c, g, (const double*)Bt, d_mu + t0, d_sd + t0);
         if (rc) return rc;
+        if (grad) {
+            // the gradients in x~, then the scalers' chain rules: the X scaler's at the raw inputs (still in raw's half h: its
+            // release is recorded after them), the y scaler's at the scaled mu, sigma (before ypost_chunk transforms them in place)
+            double* gm = d_dmu + t0 * g0.D; double* gs = d_dsd ? d_dsd + t0 * g0.D : nullptr;
+            rc = c->dtype == SCFGP_F32 ? Impl<float>::predict_grad_chunk(c, g, (const float*)Bt, d_sd + t0, gm, gs)
+                                       : Impl<double>::predict_grad_chunk(c, g, (const double*)Bt, d_sd + t0, gm, gs);
+            if (rc) return rc;
+            if (raw_mode && c->xs_mode) xgrad_chunk(raw + h * rawstride, g.N, g0.D, c->xs_mode, c->d_xscale, gm, gs, c->st);
+            if (post) ygrad_chunk(d_mu + t0, d_sd + t0, g.N, g0.D, c->ys_mode, c->d_yscale, gm, gs, c->st);
+            HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
+        }
         if (post)
             ypost_chunk(d_mu + t0, d_sd + t0, d_ys.p ? d_ys + t0 : nullptr, g.N, c->ys_mode, c->d_yscale, d_ys.p ? d_ys + T : nullptr,
                         d_part.p ? d_part + 4 * YPOST_BLOCKS * i : nullptr, c->st);
@@ -1110,6 +1171,8 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     }
     HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (grad) HIPCHK(c, hipMemcpyAsync(dmu, d_dmu, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
+    if (grad && dstd) HIPCHK(c, hipMemcpyAsync(dstd, d_dsd, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (post && ys) {
         ypost_metrics(d_part, YPOST_BLOCKS * nchunks, T, d_ys + T + 1, c->st);
@@ -1163,6 +1226,17 @@ extern "C" int scfgp_predict_y(scfgp_ctx* c, const double* Xs, int64_t T, const 
     if (c && ((c->xs_mode && !c->d_xscale) || !c->d_yscale)) { c->err = "predict_y: scalers not set"; return SCFGP_EARG; }
     if (c && ys && !metrics) { c->err = "predict_y: targets given without a metrics buffer"; return SCFGP_EARG; }
     return predict_impl(c, Xs, T, alpha, Li, mu_y, std_y, 1, 1, ys, metrics);
+}
+
+// Gradients of the predictive mean and std in the inputs (predgrad.hip).  mu, std are those of scfgp_predict (mode 0),
+// scfgp_predict_raw (1) or scfgp_predict_y (2), bit for bit: the same chunks, kernels and order.
+extern "C" int scfgp_predict_grad(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li, int mode,
+                                  double* mu, double* sd, double* dmu, double* dstd) {
+    if (!c) return SCFGP_EARG;
+    if (!Xs || !alpha || !Li || !mu || !sd || !dmu || T < 1 || mode < 0 || mode > 2) { c->err = "predict_grad: bad arguments"; return SCFGP_EARG; }
+    if (mode >= 1 && !c->d_xscale) { c->err = "predict_grad: no X scaler set"; return SCFGP_EARG; }
+    if (mode == 2 && !c->d_yscale) { c->err = "predict_grad: no y scaler set"; return SCFGP_EARG; }
+    return predict_impl(c, Xs, T, alpha, Li, mu, sd, mode >= 1 ? 1 : 0, mode == 2 ? 1 : 0, nullptr, nullptr, dmu, dstd);
 }
 
 // ----------------------------------------------------------------------------------------------

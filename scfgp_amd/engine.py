@@ -25,6 +25,13 @@ def num_params(D, S, M):
     return 3 + D * S + M * S + S + M
 
 
+def _scatter(g, cols, width):
+    """(T, len(cols)) gradients -> (T, width), zero in the columns not listed"""
+    out = np.zeros((g.shape[0], width))
+    out[:, cols] = g
+    return out
+
+
 class PeerFailed(RuntimeError):
     """Row shards: another rank failed in this evaluation (SCFGP_EPEER); no rank's results are valid."""
 
@@ -232,6 +239,41 @@ class HipEngine(object):
         self._check(self.lib.scfgp_predict_y(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), dptr(ys), dptr(mu), dptr(sd),
                                              dptr(met) if ys is not None else None), 'predict_y')
         return mu, sd, (dict(zip(self.METRICS, met.tolist())) if ys is not None else None)
+
+    PREDICT_GRAD_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
+
+    def predict_grad(self, Xs, alpha, Li, mode='scaled', want_std=True):
+        """Gradients of pred_func's outputs in its inputs (include/scfgp_hip.h: scfgp_predict_grad).  mode 'scaled': Xs as predict
+        takes it; 'raw': unscaled Xs through the registered X scaler, as predict_raw; 'y': that and the y scaler, as predict_y.
+        Returns mu (T,1), std (T,), dmu (T,D), dstd (T,D) (None without want_std); mu and std are those of the matching predict call, bit
+        for bit.  In the 'raw' / 'y' modes dmu, dstd are (T, D_raw): the constant columns the X scaler dropped get zero gradients."""
+        if mode not in self.PREDICT_GRAD_MODES:
+            raise ValueError('predict_grad: mode must be one of %s' % sorted(self.PREDICT_GRAD_MODES))
+        m = self.PREDICT_GRAD_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('predict_grad: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        D_in = Xs.shape[1]
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if alpha.size != self.K or Li.shape != (self.K, self.K):
+            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
+        T = Xs.shape[0]
+        mu = np.empty((T, 1)); sd = np.empty(T)
+        dmu = np.empty((T, self.D)); dsd = np.empty((T, self.D)) if want_std else None
+        self._check(self.lib.scfgp_predict_grad(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), m, dptr(mu), dptr(sd), dptr(dmu), dptr(dsd)),
+                    'predict_grad')
+        if cols is not None:
+            dmu, dsd = _scatter(dmu, cols, D_in), (None if dsd is None else _scatter(dsd, cols, D_in))
+        return mu, sd, dmu, dsd
 
     # -- staged evaluation (row-sharded data parallelism) --------------------------------------
     def pass1(self):

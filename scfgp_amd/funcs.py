@@ -272,6 +272,17 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return self.engine.predict_y(Xs_raw, alpha, Li, ys)
 
+    def pred_grad_func(self, Xs, alpha, Li):
+        """pred_func and its input gradients: [mu (T,1), std (T,), dmu (T,D), dstd (T,D)] for scaled Xs."""
+        self._sync_params()
+        return list(self.engine.predict_grad(Xs, alpha, Li))
+
+    def pred_grad_y(self, Xs_raw, x_scaler, y_scaler, alpha, Li):
+        """pred_y's mu_y, std_y and their gradients in the raw inputs: [mu_y (T,1), std_y (T,), dmu_y (T,D_raw), dstd_y (T,D_raw)]."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, y_scaler)
+        return list(self.engine.predict_grad(Xs_raw, alpha, Li, mode='y'))
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

@@ -257,6 +257,16 @@ class SCFGP(object):
                 self.evals[k][1].append(v)
         return mu_y, std_y
 
+    def predict_grad(self, Xs):
+        """Predictions and their gradients in the inputs, in raw X and raw y units: mu_y (T,1), std_y (T,1), dmu_y (T,D), dstd_y (T,D)
+        with D the raw column count (zero columns where the X scaler dropped a constant column).  mu_y, std_y are those of
+        predict(Xs) with device_scaler=True, bit for bit."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('predict_grad needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        mu_y, std_y, dmu_y, dstd_y = owner.pred_grad_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li)
+        return mu_y, std_y[:, None], dmu_y, dstd_y
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
