@@ -264,7 +264,12 @@ int scfgp_set_profiling(scfgp_ctx* ctx, int enable);
 int scfgp_get_timings(scfgp_ctx* ctx, double* ms, const char** names, int n);
 /* copy an internal device buffer to the host for tests ("Phi","V","G","W","XZ","Li","B","Abar",
  * "p","q","vecs","Fall","Xt","scalars"); returns the number of bytes copied or <0.  "G" is exchange buffer 1 unpacked
- * (the summed Gram, Phi^T y, y^T y and the status word) at any stage; "W" is exchange buffer 2 as the adjoint stage left it */
+ * (the summed Gram, Phi^T y, y^T y and the status word) at any stage; "W" is exchange buffer 2 as the adjoint stage left it.
+ * Compute mode SCFGP_F16X3 only (elsewhere an error with a message): "Phi16", "V16g", "qV16g" the Np x Kp plane-form arrays of
+ * Phi, V and diag(q) V (4 bytes per element, per 16 columns 16 fp16 h's then 16 l's; without the padding behind them); "B16"
+ * the K x K operand of the apply products in plane form (Kp x Kp x 4 bytes, row j = column j); "f16scale" its 4 floats
+ * (scale[0] = 2^-(e_Phi + e_operand), scale[1] = 2^e_operand); "f16tmp" the 8 floats of bounds and scales (0: bound of |Phi|,
+ * 2..4: 2^-e, 2^-e_w and the Gram scale of the last split pass, 5: bound of |V|, 6: max |q| (1 + 1e-6)) */
 int64_t scfgp_debug_read(scfgp_ctx* ctx, const char* name, void* host, int64_t max_bytes);
 /* options (name, value):
  *   "gram_nsplit"  row-split units of the Gram products (0 = default)

@@ -363,6 +363,7 @@ template <typename T> struct ApplyPlan {
         total = jt;
     }
 };
+bool F16x3Kernels::apply_runs(const Geom& g) { return ApplyPlan<float>(g.K).count[0] > 0; }
 template <class Cfg, int EPI, typename T>
 static int apply_launch_cfg(const Geom& g, int njt, int col0, int jt0, const T* Phi, const T* Bm, T* V, double* vpart,
                             const double* p, const double* q, const double* y, const double* alpha, const double* ut,

@@ -218,9 +218,17 @@ __global__ __launch_bounds__(1024) void split_rows_kernel(const float* __restric
                     put(reinterpret_cast<char*>(out_pl + n * Kp) + poff, h, l);
                 }
                 if (rw) {
+                    // x f is rounded to fp32 once and split from there (the empty asm keeps it so).  Left to itself the compiler
+                    // folded the product into the split's v_fma_mix*_f16: l = fp16(x f - h') against h' = fp16(x f) rounded once from
+                    // the exact product, not against the h = fp16(fp32(x f)) it stores -- h + l was a step of h off wherever the two
+                    // roundings differ, and the weighted Gram 300x fp32 mode's error (tests/test_gpu_f16x3_stages.py)
                     const float f = (float)(rw[n] * up1);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) split2(x[k] * f, h[k], l[k]);
+                    for (int k = 0; k < 4; ++k) {
+                        float xf = x[k] * f;
+                        asm("" : "+v"(xf));
+                        split2(xf, h[k], l[k]);
+                    }
                     put(reinterpret_cast<char*>(out_w + n * Kp) + poff, h, l);
                 }
             }

@@ -147,6 +147,9 @@ struct F16x3Kernels {
     static int apply(const Geom& g, int njt, int col0, int slot0, const float* Phi, const F16Operands& f, float* V,
                      double* vpart, const double* p, const double* q, const double* y, const double* alpha, const double* ut, double* mu,
                      hipStream_t st, int64_t rb0, int64_t nrb);
+    // apply.hip: whether the apply products run these tiles at all -- the launch plan has full 128-column blocks (K > 256); below
+    // that fp32 mode's register tiles do, and V = Phi B's epilogue writes no planes
+    static bool apply_runs(const Geom& g);
     // gram_f16.hip.  The Np x Kp plane-form arrays are allocated with F16_PAD bytes behind them (the Gram's last 256-column block may
     // stick out of Kp).  tmp: 8 floats on the device; after a split pass tmp + 4 is the scale of the Gram product that follows.
     // sidepart: side_blocks(g) x Kp doubles, the block partials of M^T w (reduce_side sums them).

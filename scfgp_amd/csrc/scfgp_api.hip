@@ -538,8 +538,9 @@ template <typename T> struct Impl {
                 // whose row chunks are the "splits" of the shared reduction
                 const int nch = F16x3Kernels::gram_chunks(g, c->f16_chunk());
                 { ProfScope ps(c, w ? "split_v" : "split_phi");
-                  // V's own planes were written by the epilogue of V = Phi B (pass2)
-                  if (w) F16x3Kernels::split_v(g, (const float*)Mx, w, side, nullptr, c->d_qV16g, c->d_f16side, c->d_f16tmp, c->st);
+                  // V's own planes were written by the epilogue of V = Phi B (pass2) -- unless fp32 mode's register tiles formed V (K <= 256)
+                  if (w) F16x3Kernels::split_v(g, (const float*)Mx, w, side, F16x3Kernels::apply_runs(g) ? nullptr : c->d_V16g, c->d_qV16g,
+                                               c->d_f16side, c->d_f16tmp, c->st);
                   else F16x3Kernels::split_phi(g, (const float*)Mx, side, c->d_sc, c->d_Phi16, c->d_f16side, c->d_f16tmp, c->st); }
                 { ProfScope ps(c, name);
                   F16x3Kernels::gram(g, w ? c->d_V16g : c->d_Phi16, w ? c->d_qV16g : c->d_Phi16, c->d_f16tmp + 4, c->f16_chunk(), c->d_slabs, c->st); }
@@ -1598,6 +1599,16 @@ extern "C" int64_t scfgp_debug_read(scfgp_ctx* c, const char* name, void* host, 
     else if (s == "Fall") { src = c->d_Fall; bytes = 8 * (int64_t)g.Dp * g.Jp; }
     else if (s == "Xt") { src = c->d_Xt; bytes = 8 * g.Np * g.Dp; }
     else if (s == "scalars") { src = c->d_scalars; bytes = 8 * 32; }
+    else if (s == "Phi16" || s == "V16g" || s == "qV16g" || s == "B16" || s == "f16scale" || s == "f16tmp") {
+        if (!c->split16) { c->err = "debug_read: " + s + " exists in compute mode SCFGP_F16X3 only"; return SCFGP_EARG; }
+        const int64_t plane = 4 * g.Np * g.Kp;                  // the F16_PAD bytes behind the Np x Kp arrays are left out
+        if (s == "Phi16") { src = c->d_Phi16; bytes = plane; }
+        else if (s == "V16g") { src = c->d_V16g; bytes = plane; }
+        else if (s == "qV16g") { src = c->d_qV16g; bytes = plane; }
+        else if (s == "B16") { src = c->d_B16; bytes = 4 * K2; }
+        else if (s == "f16scale") { src = c->d_f16scale; bytes = sizeof(float) * 4; }
+        else { src = c->d_f16tmp; bytes = sizeof(float) * 8; }
+    }
     else { c->err = "debug_read: unknown buffer " + s; return SCFGP_EARG; }
     if (!src) return SCFGP_EARG;
     if (bytes > max_bytes) bytes = max_bytes;
