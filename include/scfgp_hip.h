@@ -141,6 +141,28 @@ int scfgp_predict_y(scfgp_ctx* ctx, const double* Xs_raw, int64_t T, const doubl
  * (modes 1, 2) or parameters not set. */
 int scfgp_predict_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int mode,
                        double* mu, double* std, double* dmu, double* dstd);
+/* ---- posterior sample functions (no reference counterpart: the reference reports the marginals only) ---------------------------
+ * With A = Phi^T Phi + (sigma_n^2 + eps) I = L L^T, Li = L^-1, alpha = Li^T Li Phi^T y and kappa = softplus(c) (SCFGP/SCFGP.py:103-110),
+ * pred_func's marginals are mu*(x) = phi(x)^T alpha and sigma*(x)^2 = kappa (1 + ||Li phi(x)||^2).  Since A^-1 = Li^T Li, the weights
+ *     w_s = alpha + sqrt(kappa) Li^T z_s,   z_s ~ N(0, I_K),   i.e. w ~ N(alpha, kappa A^-1),
+ * give sample functions f_s(x) = phi(x)^T w_s with mean mu*, variance sigma*^2 - kappa and covariance kappa phi(x)^T A^-1 phi(x');
+ * y_s(x) = f_s(x) + sqrt(kappa) eps_s(x) has pred_func's marginal N(mu*, sigma*^2).  Index k of w runs over alpha's layout (the J cosine
+ * features, then the J sine features).
+ * Random numbers (part of the contract: a sample function is a function -- the same seed gives the same S functions in any call, on any
+ * rows, in any chunking, and sample s does not depend on nsamp or T): Philox4x64-10 (Random123), counter (c0, c1, 0, 0), key (seed, stream);
+ * U(u) = ((u >> 11) + 0.5) 2^-53; with the four words w of a block and p = (s & 3) >> 1, r = sqrt(-2 ln U(w[2p])), the normal is
+ * r cos(2 pi U(w[2p+1])) for even s, r sin(2 pi U(w[2p+1])) for odd s (fp64).
+ *     z[k][s]    block (k, s >> 2), stream 0            eps[t][s]  block (t, s >> 2), stream 1   (t: the row's index in the call's Xs)
+ * 1 <= nsamp <= 1024; alpha, Li as scfgp_eval returns them (Li lower triangular: entries above the diagonal are not read).
+ * scfgp_sample_weights: W (K x nsamp, row-major, fp64) = alpha 1^T + sqrt(kappa) Li^T Z, computed in fp64 in every compute mode.
+ * scfgp_sample: out (T x nsamp, row-major) = f_s(x_t), plus sqrt(kappa) eps[t][s] if `noise`; mode 0 scaled Xs (as scfgp_predict),
+ *   1 column-selected raw Xs through the registered X scaler (as scfgp_predict_raw), 2 mode 1 and then the y scaler's backward transform
+ *   of every element (as scfgp_predict_y: samples in raw y units).  Phi* W runs in the context's precision (fp64 MFMA; exact fp32 MFMA
+ *   with fp64 partial sums in SCFGP_F32 and SCFGP_F16X3, which agree bit for bit); device memory does not grow with T.
+ * SCFGP_EARG for bad arguments, a missing scaler (modes 1, 2) or parameters not set. */
+int scfgp_sample_weights(scfgp_ctx* ctx, const double* alpha, const double* Li, int nsamp, uint64_t seed, double* W);
+int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp,
+                 uint64_t seed, int mode, int noise, double* out);
 
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded

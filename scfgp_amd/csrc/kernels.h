@@ -238,6 +238,21 @@ void predgrad(const Geom& g, const T* Phi, const T* V, const double* alpha, cons
 void xgrad_chunk(const double* Xraw, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st);
 void ygrad_chunk(const double* mu, const double* sd, int64_t n, int D, int mode, const double* sp, double* dmu, double* dstd, hipStream_t st);
 
+// ---- sample.hip, posterior sample functions (scfgp_sample, scfgp_sample_weights) -----------------------------------------------------
+// the weight arrays are sample_w_rows(K) x sample_w_cols(nsamp), zero outside K x nsamp
+inline int64_t sample_w_rows(int K) { return round_up(K, 64); }
+inline int sample_w_cols(int nsamp) { return (int)round_up(nsamp, 64); }
+// Z (scratch) <- the normals of `seed`; W (fp64) and Wt (type T) <- alpha 1^T + sqrt(kappa) Li^T Z (Li: K x K device copy of the host
+// matrix, lower triangular; alpha: K)
+template <typename T>
+void sample_weights(const Geom& g, const double* Li, const double* alpha, const Scal* sc, int nsamp, uint64_t seed, double* Z, double* W,
+                    T* Wt, hipStream_t st);
+// out (N x nsamp, row-major) = Phi Wt over the K features of the chunk's rows; noise: + sqrt(kappa) eps of rows t0 + n; ymode >= 0: then
+// the y scaler's backward transform of that mode (sp: its 5 parameters)
+template <typename T>
+void sample_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode, const double* ysp,
+                    const Scal* sc, double* out, hipStream_t st);
+
 // ---- on-device update rules (SCFGP/Optimizer.py) --------------------------------------------
 struct OptHyper { double lr, b1, b2, eps, momentum; };   // b1 doubles as rho for rmsprop/adadelta; momentum < 0: no Nesterov
 // theta <- rule(theta, grad); st = [s1 | s2 | velocity]; tctr[0] = step counter, tctr[1] = index into hist

@@ -707,6 +707,14 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_sample: the chunk's Phi* as predict_chunk forms it, then out (N x nsamp) = Phi* W and the epilogue (sample.hip)
+    static int sample_chunk(scfgp_ctx* c, const Geom& g, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode,
+                            double* out) {
+        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
+        sample_product<T>(g, (const T*)c->p_Phi, Wt, nsamp, t0, seed, noise, ymode, c->d_yscale, c->d_sc, out, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
 };
 
 #define DISPATCH(c, fn, ...) ((c)->dtype == SCFGP_F32 ? Impl<float>::fn(__VA_ARGS__) : Impl<double>::fn(__VA_ARGS__))
@@ -1050,6 +1058,23 @@ extern "C" int scfgp_eval_rows(scfgp_ctx* c, const int64_t* idx, int64_t n, int 
     return run_eval(c, want_grad, cost, grad, alpha, Li, true);
 }
 
+// the chunk buffers of the predict family and of scfgp_sample (first call only); the padding columns of Phi* stay zero
+static int ensure_pred_chunk(scfgp_ctx* c) {
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp;
+    const size_t ts = c->tsize();
+    int rc;
+    if (!c->p_Xt) {
+        if ((rc = dmalloc(c, &c->p_Xt, sizeof(double) * PRED_ROWS * g0.Dp))) return rc;
+        if (g0.lowrank && (rc = dmalloc(c, &c->p_Tt, sizeof(double) * PRED_ROWS * g0.Sp))) return rc;
+        if ((rc = dmalloc(c, &c->p_vpart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
+        if ((rc = dmalloc(c, &c->p_mupart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
+        if ((rc = dmalloc(c, &c->p_Phi, ts * PRED_ROWS * Kp))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->p_Phi, 0, ts * PRED_ROWS * Kp, c->st));
+    }
+    return SCFGP_OK;
+}
+
 // buffers of scfgp_predict_grad beside predict's own (first call only; the std gradient's on its first call)
 static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
     const Geom& g = c->g;
@@ -1078,16 +1103,8 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp;
-    const size_t ts = c->tsize();
     int rc;
-    if (!c->p_Xt) {
-        if ((rc = dmalloc(c, &c->p_Xt, sizeof(double) * PRED_ROWS * g0.Dp))) return rc;
-        if (g0.lowrank && (rc = dmalloc(c, &c->p_Tt, sizeof(double) * PRED_ROWS * g0.Sp))) return rc;
-        if ((rc = dmalloc(c, &c->p_vpart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
-        if ((rc = dmalloc(c, &c->p_mupart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
-        if ((rc = dmalloc(c, &c->p_Phi, ts * PRED_ROWS * Kp))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->p_Phi, 0, ts * PRED_ROWS * Kp, c->st));
-    }
+    if ((rc = ensure_pred_chunk(c))) return rc;
     const bool grad = dmu != nullptr;
     if (grad && (rc = ensure_pred_grad(c, dstd != nullptr))) return rc;
     // Li (K x K host) -> T1 (Kp x Kp, identity padding); typed transposed copy -> AbarT scratch
@@ -1238,6 +1255,121 @@ extern "C" int scfgp_predict_grad(scfgp_ctx* c, const double* Xs, int64_t T, con
     if (mode >= 1 && !c->d_xscale) { c->err = "predict_grad: no X scaler set"; return SCFGP_EARG; }
     if (mode == 2 && !c->d_yscale) { c->err = "predict_grad: no y scaler set"; return SCFGP_EARG; }
     return predict_impl(c, Xs, T, alpha, Li, mu, sd, mode >= 1 ? 1 : 0, mode == 2 ? 1 : 0, nullptr, nullptr, dmu, dstd);
+}
+
+// ----------------------------------------------------------------------------------------------
+// posterior sample functions (sample.hip; derivation and random-number contract in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int SAMPLE_MAX = 1024;
+// the weights of nsamp sample functions on the device: W (fp64) and Wt (the context's type), sample_w_rows(K) x sample_w_cols(nsamp)
+struct SampleW { DevTmp z, w, wt; };
+static int sample_weights_dev(scfgp_ctx* c, const double* alpha, const double* Li, int nsamp, uint64_t seed, SampleW& sw) {
+    const Geom& g = c->g;
+    const int64_t n = sample_w_rows(g.K) * sample_w_cols(nsamp);
+    DevTmp dli, dal;
+    int rc;
+    if ((rc = dmalloc(c, &dli.p, sizeof(double) * g.K * g.K))) return rc;
+    if ((rc = dmalloc(c, &dal.p, sizeof(double) * g.K))) return rc;
+    if ((rc = dmalloc(c, &sw.z.p, sizeof(double) * n))) return rc;
+    if ((rc = dmalloc(c, &sw.w.p, sizeof(double) * n))) return rc;
+    if ((rc = dmalloc(c, &sw.wt.p, c->tsize() * n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(dli, Li, sizeof(double) * g.K * g.K, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(dal, alpha, sizeof(double) * g.K, hipMemcpyHostToDevice, c->st));
+    if (c->dtype == SCFGP_F32) sample_weights<float>(g, dli, dal, c->d_sc, nsamp, seed, sw.z, sw.w, (float*)sw.wt.p, c->st);
+    else sample_weights<double>(g, dli, dal, c->d_sc, nsamp, seed, sw.z, sw.w, sw.wt, c->st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // dli, dal are released on return
+    return SCFGP_OK;
+}
+static int sample_check(scfgp_ctx* c, bool ptrs_ok, int nsamp, const char* who) {
+    if (!ptrs_ok) { c->err = std::string(who) + ": bad arguments"; return SCFGP_EARG; }
+    if (nsamp < 1 || nsamp > SAMPLE_MAX) { c->err = std::string(who) + ": nsamp must lie in 1..1024"; return SCFGP_EARG; }
+    return SCFGP_OK;
+}
+
+extern "C" int scfgp_sample_weights(scfgp_ctx* c, const double* alpha, const double* Li, int nsamp, uint64_t seed, double* W) {
+    if (!c) return SCFGP_EARG;
+    if (int rc = sample_check(c, alpha && Li && W, nsamp, "sample_weights")) return rc;
+    if (!c->have_params) { c->err = "sample_weights: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    SampleW sw;
+    if (int rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw)) return rc;
+    HIPCHK(c, hipMemcpy2DAsync(W, sizeof(double) * nsamp, sw.w, sizeof(double) * sample_w_cols(nsamp), sizeof(double) * nsamp, c->g.K,
+                               hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SCFGP_OK;
+}
+
+// A sibling of predict_impl: the same double-buffered upload of Xs on the copy stream, pack_data (with the X scaler in modes 1, 2) and
+// feature map per chunk of PRED_ROWS rows, then Phi* W.  The samples of a chunk land in one of two staging buffers and go to their
+// place in `out` on the copy stream while the next chunk computes: device memory is two chunks of samples whatever T is.
+extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp, uint64_t seed,
+                            int mode, int noise, double* out) {
+    if (!c) return SCFGP_EARG;
+    int rc;
+    if ((rc = sample_check(c, Xs && alpha && Li && out && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample"))) return rc;
+    if (mode >= 1 && !c->d_xscale) { c->err = "sample: no X scaler set"; return SCFGP_EARG; }
+    if (mode == 2 && !c->d_yscale) { c->err = "sample: no y scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "sample: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    SampleW sw;
+    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
+    const int64_t rawstride = PRED_ROWS * g0.D, rows = std::min<int64_t>(T, PRED_ROWS);
+    DevTmp raw, stage;                                            // two chunks of Xs | two chunks of samples
+    if ((rc = dmalloc(c, &raw.p, sizeof(double) * 2 * rawstride))) return rc;
+    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * nsamp))) return rc;
+    struct Events {
+        // up / fre: the two halves of raw (uploaded / free again); done / out: the two staging buffers (computed / copied out)
+        hipEvent_t e[4][2] = {};
+        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
+    for (auto& p : ev.e)
+        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    auto upload = [&](int64_t i) -> int {
+        const int64_t t0 = i * PRED_ROWS, n = std::min<int64_t>(PRED_ROWS, T - t0);
+        const int h = (int)(i & 1);
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xs + t0 * g0.D, sizeof(double) * n * g0.D, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    // chunk i's samples to the host (pageable: the host waits in this call while chunk i + 1 computes)
+    auto download = [&](int64_t i) -> int {
+        const int64_t t0 = i * PRED_ROWS, n = std::min<int64_t>(PRED_ROWS, T - t0);
+        const int h = (int)(i & 1);
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
+        HIPCHK(c, hipMemcpyAsync(out + t0 * nsamp, stage + h * rows * nsamp, sizeof(double) * n * nsamp, hipMemcpyDeviceToHost, c->copy_st));
+        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    const int ymode = mode == 2 ? c->ys_mode : -1;
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const int64_t t0 = i * PRED_ROWS;
+        const int h = (int)(i & 1);
+        Geom g = g0;
+        g.N = std::min<int64_t>(PRED_ROWS, T - t0); g.Np = round_up(g.N, 256);
+        HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
+        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
+        HIPCHK(c, hipEventRecord(fre[h], c->st));
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[h], 0));
+        double* o = stage + h * rows * nsamp;
+        rc = c->dtype == SCFGP_F32 ? Impl<float>::sample_chunk(c, g, (const float*)sw.wt.p, nsamp, t0, seed, noise, ymode, o)
+                                   : Impl<double>::sample_chunk(c, g, (const double*)sw.wt.p, nsamp, t0, seed, noise, ymode, o);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(done[h], c->st));
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i >= 1 && (rc = download(i - 1))) return rc;
+    }
+    if ((rc = download(nchunks - 1))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return SCFGP_OK;
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -275,6 +275,49 @@ class HipEngine(object):
             dmu, dsd = _scatter(dmu, cols, D_in), (None if dsd is None else _scatter(dsd, cols, D_in))
         return mu, sd, dmu, dsd
 
+    SAMPLE_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
+
+    def _factors(self, alpha, Li):
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if alpha.size != self.K or Li.shape != (self.K, self.K):
+            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
+        return alpha, Li
+
+    def sample_weights(self, alpha, Li, nsamp, seed=0):
+        """Weights of nsamp posterior sample functions (include/scfgp_hip.h: scfgp_sample_weights): W (K, nsamp) = alpha 1^T +
+        sqrt(kappa) Li^T Z with Z drawn from `seed` by the library's counter-based generator; column s is the same for any nsamp."""
+        alpha, Li = self._factors(alpha, Li)
+        W = np.empty((self.K, int(nsamp)))
+        self._check(self.lib.scfgp_sample_weights(self.ctx, dptr(alpha), dptr(Li), int(nsamp), int(seed) & (2 ** 64 - 1), dptr(W)),
+                    'sample_weights')
+        return W
+
+    def sample(self, Xs, alpha, Li, nsamp, seed=0, mode='scaled', noise=False):
+        """nsamp posterior sample functions evaluated at the rows of Xs (include/scfgp_hip.h: scfgp_sample): (T, nsamp), column s =
+        phi(x)^T w_s (+ sqrt(kappa) eps with noise).  mode 'scaled': Xs as predict takes it; 'raw': unscaled Xs through the registered
+        X scaler, as predict_raw; 'y': that and the y scaler's backward transform of every sample, as predict_y."""
+        if mode not in self.SAMPLE_MODES:
+            raise ValueError('sample: mode must be one of %s' % sorted(self.SAMPLE_MODES))
+        m = self.SAMPLE_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('sample: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        alpha, Li = self._factors(alpha, Li)
+        T = Xs.shape[0]
+        out = np.empty((T, max(int(nsamp), 0)))
+        self._check(self.lib.scfgp_sample(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), int(nsamp), int(seed) & (2 ** 64 - 1), m,
+                                          int(bool(noise)), dptr(out)), 'sample')
+        return out
+
     # -- staged evaluation (row-sharded data parallelism) --------------------------------------
     def pass1(self):
         self._check(self.lib.scfgp_pass1(self.ctx), 'pass1')

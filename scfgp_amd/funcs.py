@@ -283,6 +283,12 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return list(self.engine.predict_grad(Xs_raw, alpha, Li, mode='y'))
 
+    def sample_y(self, Xs_raw, x_scaler, y_scaler, alpha, Li, nsamp, seed=0, noise=False):
+        """nsamp posterior sample functions at the raw rows Xs_raw, in raw y units (T, nsamp)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, y_scaler)
+        return self.engine.sample(Xs_raw, alpha, Li, nsamp, seed=seed, mode='y', noise=noise)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

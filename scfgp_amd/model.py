@@ -267,6 +267,15 @@ class SCFGP(object):
         mu_y, std_y, dmu_y, dstd_y = owner.pred_grad_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li)
         return mu_y, std_y[:, None], dmu_y, dstd_y
 
+    def sample(self, Xs, nsamples, seed=0, noise=False):
+        """nsamples posterior sample functions of the fitted model at the raw rows Xs, in raw y units: (T, nsamples).  Column s is
+        phi(x)^T w_s with w_s ~ N(alpha, kappa A^-1) (plus observation noise with noise=True), mapped through the y scaler's backward
+        transform; the same seed gives the same functions on any rows (include/scfgp_hip.h: scfgp_sample)."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('sample needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        return owner.sample_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, noise=noise)
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
