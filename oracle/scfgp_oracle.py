@@ -128,13 +128,18 @@ def predict(Xs, alpha, Li, params, S, M):
 # --------------------------------------------------------------------------
 # value + gradient: the 3-sweep algorithm (replaces TT.grad, SCFGP.py:129)
 # --------------------------------------------------------------------------
-def value_and_grad(X, y, params, S, M, chunk=8192, n_global=None):
+def value_and_grad(X, y, params, S, M, chunk=8192, n_global=None, with_scale=False, rows3=None, zbar_hook=None):
     """Hand-derived exact gradient of `forward(...)[0]` w.r.t. the flat vector.
 
     Three row sweeps (chunked so N x K temporaries stay small), each ending in a
     reduction that is additive over rows -- the same structure the HIP path uses
     and the reason the data-parallel version needs three all-reduces.
-    Returns (cost, grad (P,), alpha (K,1), Li (K,K)).
+    Returns (cost, grad (P,), alpha (K,1), Li (K,K)); with with_scale=True also
+    `scale` (P-3,): grad[3:]'s abs-sum scale, sweep 3 and the epilogue with every
+    signed sum replaced by its sum of absolute values (tests/parity.py).
+    rows3 = (lo, hi) and zbar_hook(Zc, Zs, lo, hi) -> (Zc, Zs) let tests mutate sweep 3
+    (rows left out of its sums; a damaged half of Zbar = Zc - Zs, Zc = Phi_cos o Phibar_sin,
+    Zs = Phi_sin o Phibar_cos); both default to the exact sweep.
     """
     X = np.asarray(X, np.float64); y = np.asarray(y, np.float64).reshape(-1)
     N, D = X.shape
@@ -157,10 +162,10 @@ def value_and_grad(X, y, params, S, M, chunk=8192, n_global=None):
         hi = min(N, lo + chunk); Ph = phi_rows(lo, hi)
         G += Ph.T @ Ph; g += Ph.T @ y[lo:hi]; yy += (y[lo:hi] ** 2).sum()
     st1 = dict(G=G, g=g, yy=yy)
-    return _finish_from_sweep1(X, y, params, S, M, st1, chunk, Ng, phi_rows)
+    return _finish_from_sweep1(X, y, params, S, M, st1, chunk, Ng, phi_rows, with_scale, rows3, zbar_hook)
 
 
-def _finish_from_sweep1(X, y, params, S, M, st1, chunk, Ng, phi_rows):
+def _finish_from_sweep1(X, y, params, S, M, st1, chunk, Ng, phi_rows, with_scale=False, rows3=None, zbar_hook=None):
     N, D = X.shape
     a, b, c, l_F, r_F, F, l_FC, FC = unpack_params(params, D, S, M)
     J = S + M; K = 2 * J
@@ -204,19 +209,34 @@ def _finish_from_sweep1(X, y, params, S, M, st1, chunk, Ng, phi_rows):
     # ---- sweep 3
     bbar = 0.0
     XZ = np.zeros((D, J)); colsum = np.zeros(J)
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk); Ph = phi_rows(lo, hi)
+    XZa = np.zeros((D, J)); colsa = np.zeros(J)
+    r0, r1 = (0, N) if rows3 is None else rows3
+    for lo in range(r0, r1, chunk):
+        hi = min(r1, lo + chunk); Ph = phi_rows(lo, hi)
         p = p_all[lo:hi]; q = q_all[lo:hi]
         Pb = (np.outer(p, alpha) + np.outer(y[lo:hi], ut)
               + 2 * q[:, None] * (Ph @ B) + 2 * (Ph @ Abar))
         bbar += (Pb * Ph).sum()
-        Zb = Ph[:, :J] * Pb[:, J:] - Ph[:, J:] * Pb[:, :J]
+        Zc = Ph[:, :J] * Pb[:, J:]; Zs = Ph[:, J:] * Pb[:, :J]
+        if with_scale:
+            Za = np.abs(Zc) + np.abs(Zs)
+            XZa += np.abs(X[lo:hi]).T @ Za; colsa += Za.sum(0)
+        if zbar_hook is not None:
+            Zc, Zs = zbar_hook(Zc, Zs, lo, hi)
+        Zb = Zc - Zs
         XZ += X[lo:hi].T @ Zb; colsum += Zb.sum(0)
     st3 = dict(XZ=XZ, colsum=colsum, bbar=bbar)
     pen = _penalty(l_F, F, S, M)
     cost = (T1 + T2 + T3 + T4 + pen) / Ng
     grad = _epilogue(params, D, S, M, st3, abar, cbar, Ng)
-    return float(cost), grad, alpha.reshape(-1, 1), Li
+    if not with_scale:
+        return float(cost), grad, alpha.reshape(-1, 1), Li
+    # the epilogue's chain rule in absolute values: F_bar = XZ_F - colsum_F / D, lF_bar = XZ_l - colsum_l / D + F_bar r_F,
+    # rF_bar = F_bar^T l_F, the phase entries the column sums themselves (the penalty's closed form is left out)
+    aF = XZa[:, S:] + colsa[None, S:] / D
+    alF = XZa[:, :S] + colsa[None, :S] / D
+    scale = np.concatenate(((alF + aF @ np.abs(r_F)).ravel(), (aF.T @ np.abs(l_F)).ravel(), colsa[:S], colsa[S:])) / Ng
+    return float(cost), grad, alpha.reshape(-1, 1), Li, scale
 
 
 def _epilogue(params, D, S, M, st3, abar, cbar, Ng):

@@ -1731,6 +1731,18 @@ extern "C" int64_t scfgp_debug_read(scfgp_ctx* c, const char* name, void* host, 
     else if (s == "Fall") { src = c->d_Fall; bytes = 8 * (int64_t)g.Dp * g.Jp; }
     else if (s == "Xt") { src = c->d_Xt; bytes = 8 * g.Np * g.Dp; }
     else if (s == "scalars") { src = c->d_scalars; bytes = 8 * 32; }
+    else if (s == "C") {                                         // factor form: C = Phi Li^T of the last pass 2 at level 2
+        if (!c->d_C || c->c_cap < g.Np || !c->last_cform) { c->err = "debug_read: C exists only after a pass 2 in the factor form (level 2)"; return SCFGP_EARG; }
+        src = c->d_C; bytes = ts * g.Np * g.Kp;
+    }
+    else if (s == "Phi64") {                                     // the fp64 features of an escalated pass 1 (levels 1 and 2)
+        if (!c->d_Phi64 || c->phi64_cap < g.Np) { c->err = "debug_read: Phi64 exists only in fp32 mode at a raised level"; return SCFGP_EARG; }
+        src = c->d_Phi64; bytes = 8 * g.Np * g.Kp;
+    }
+    else if (s == "Tt") {                                        // T~ = [X l_F | 1] of the rank-S projection, Np x Sp
+        if (!c->d_Tt) { c->err = "debug_read: Tt exists only where the projection goes through the S columns"; return SCFGP_EARG; }
+        src = c->d_Tt; bytes = 8 * g.Np * g.Sp;
+    }
     else if (s == "Phi16" || s == "V16g" || s == "qV16g" || s == "B16" || s == "f16scale" || s == "f16tmp") {
         if (!c->split16) { c->err = "debug_read: " + s + " exists in compute mode SCFGP_F16X3 only"; return SCFGP_EARG; }
         const int64_t plane = 4 * g.Np * g.Kp;                  // the F16_PAD bytes behind the Np x Kp arrays are left out

@@ -16,6 +16,7 @@ import pytest
 
 from oracle import scfgp_oracle as O
 from scfgp_amd import synth
+from tests import parity as PB
 from tests.golden.make_oracle_kats import CASES, case_inputs
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +69,10 @@ def test_oracle_kats_fp64(name):
     mu, sd = pred_func(Xs, alpha, Li)
     assert mu.shape == (T, 1) and sd.shape == (T,)
     assert rel(mu, z[name + '/mu']) < 1e-8 and rel(sd, z[name + '/std']) < 1e-9
+    ref = PB.oracle_all(X, y, params, S, M, Xs)
+    r = PB.check_all((cost, grad, alpha, Li), ref, D, S, M, 'f64')
+    r['predict'] = PB.check_predict(mu, sd, ref['mu'], ref['std'], 'f64')
+    print('\n%s f64 blocks: %s' % (name, PB.fmt(r)))
     # train_iter_func: outputs at the PRE-update parameters, then the vector moves
     c2, a2, L2 = train_iter_func(X, y)
     assert float(c2) == float(cost) and np.array_equal(a2, alpha)
@@ -92,6 +97,10 @@ def test_oracle_kats_fp32_mode(name, mode):
     assert rel(alpha, z[name + '/alpha']) < 1e-3
     mu, sd = eng.predict(Xs, z[name + '/alpha'], Li)
     assert rel(mu, z[name + '/mu']) < 1e-4 and rel(sd, z[name + '/std']) < 1e-4
+    r = PB.check_all((cost, grad, alpha, Li), PB.oracle_all(X, y, params, S, M), D, S, M, mode)
+    mu0, sd0 = O.predict(Xs, z[name + '/alpha'], Li, params, S, M)
+    r['predict'] = PB.check_predict(mu, sd, mu0, sd0, mode)
+    print('\n%s %s blocks: %s' % (name, mode, PB.fmt(r)))
     eng.close()
 
 
@@ -142,6 +151,7 @@ def test_minibatches_of_different_sizes():
         c, g, a, L = cf.value_and_grad(Xb, yb)
         c0, g0, a0, L0 = O.value_and_grad(Xb, yb, params, S, M)
         assert abs(float(c) - c0) < 1e-10 * abs(c0) and rel(g, g0) < 1e-7 and rel(a, a0) < 1e-7
+        PB.oracle_check((c, g, a, L), Xb, yb, params, S, M, 'f64', label='minibatch')
 
 
 @pytest.mark.parametrize('N,D,S,M', [(1, 1, 2, 2), (3, 2, 2, 3), (255, 3, 2, 5), (513, 70, 5, 60),
@@ -163,9 +173,11 @@ def test_ragged_and_degenerate_shapes(N, D, S, M, dtype):
     ftol = tol if dtype == 'f64' else 2e-2      # alpha, Li carry cond(A) times the fp32 Gram error
     assert abs(float(cost) - c0) < (1e-10 if dtype == 'f64' else 2e-5) * max(1.0, abs(c0))
     assert rel(grad, g0) < tol and rel(alpha, a0) < ftol and rel(Li, L0) < ftol
+    PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, alpha_li=dtype == 'f64', label='ragged')
     mu, sd = eng.predict(Xs, a0, L0)
     mu0, sd0 = O.predict(Xs, a0, L0, params, S, M)
     assert rel(mu, mu0) < tol and rel(sd, sd0) < tol
+    PB.check_predict(mu, sd, mu0, sd0, dtype)
     # a second, smaller data set through the same context (capacity is kept, padding rewritten)
     n2 = max(1, N // 3)
     c2, g2, _, _ = eng.eval(np.ascontiguousarray(X[:n2]), np.ascontiguousarray(y[:n2]), want_grad=True)
@@ -488,6 +500,7 @@ def test_index_list_minibatches_on_resident_rows():
         c, g, a, L = eng.eval_rows(idx, True)
         c0, g0, a0, L0 = O.value_and_grad(X[idx], y[idx], params, S, M)
         assert abs(float(c) - c0) < 1e-10 * abs(c0) and rel(g, g0) < 1e-7 and rel(a, a0) < 1e-7
+        PB.oracle_check((c, g, a, L), X[idx], y[idx], params, S, M, 'f64', label='index list')
     c2, g2, _, _ = eng.eval(want_grad=True)                 # all rows again
     assert float(c2) == float(c_full) and np.array_equal(g2, g_full)
     with pytest.raises(ValueError):
@@ -522,6 +535,7 @@ def test_baseline_config_shapes_against_oracle(N, D, S, M, dtype):
         for u, v in zip(grad_blocks(grad, D, S, M), grad_blocks(g0, D, S, M)):
             assert rel(u, v) < 1e-3
         assert rel(Li, L0) < 1e-3
+    PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, label='baseline shape')
     eng.close()
 
 

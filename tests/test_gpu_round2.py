@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import scfgp_oracle as O
+from tests import parity as PB
 from tests.golden.make_oracle_kats import CASES, case_inputs
 
 pytestmark = pytest.mark.gpu
@@ -273,6 +274,7 @@ def test_predict_triangular_product_against_the_oracle(D, S, M, T, dtype, tol):
     mu0, sd0 = O.predict(Xs[sel], alpha, Li, params, S, M)
     assert mu.shape == (T, 1) and sd.shape == (T,)
     assert rel(mu[sel], mu0) < tol and rel(sd[sel], sd0) < tol, (rel(mu[sel], mu0), rel(sd[sel], sd0))
+    PB.check_predict(mu[sel], sd[sel], mu0, sd0, dtype)
     eng.close()
 
 
@@ -296,6 +298,7 @@ def test_apply_tiles_fed_by_lds_dma_match(N, D, S, M, dtype, ptol, ctol, gtol):
         eng = HipEngine(D, S, M, dtype=dtype); eng.set_params(params); eng.set_option('apply_dma', dma); eng.set_data(X, y)
         cost, grad, alpha, Li = eng.eval(want_grad=True)
         out[dma] = (float(cost), grad.copy(), alpha.copy(), eng.debug_read('p', (N,)).copy(), eng.debug_read('q', (N,)).copy())
+        PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, label='apply_dma %d' % dma)
         eng.close()
     for dma in (1, 2):
         assert abs(out[dma][0] - out[0][0]) < ptol * 1e-2 * abs(out[0][0])
@@ -329,4 +332,5 @@ def test_random_shapes_against_oracle(dtype, ctol, gtol):
         assert abs(float(cost) - c0) < ctol * max(1.0, abs(c0)), (N, D, S, M, float(cost), c0)
         assert rel(grad, g0) < gtol, (N, D, S, M, rel(grad, g0))
         assert np.all(np.triu(Li, 1) == 0)
+        PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, alpha_li=dtype == 'f64', label='random shape')
         eng.close()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import scfgp_oracle as O
+from tests import parity as PB
 from scfgp_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -249,6 +250,7 @@ def test_factor_form_of_pass2_matches_oracle(dtype, dma, ctol, gtol):
             assert abs(float(c) - c0) < ctol * max(1.0, abs(c0)), (ff, float(c), c0)
             for u, v in zip(grad_blocks(g, D, S, M), grad_blocks(g0, D, S, M)):
                 assert rel(u, v) < gtol, (N, ff, rel(u, v))
+            PB.oracle_check((c, g, a, L), X, y, params, S, M, dtype, label='factor_form %d' % ff)
             p = eng.debug_read('p', (N,)); V = eng.debug_read('V', (eng.dims()['Np'], eng.dims()['Kp']),
                                                                np.float64 if dtype == 'f64' else np.float32)
             if ref is None:
@@ -322,6 +324,7 @@ def test_rank_s_backward_projection_matches_the_dense_one(dtype, gtol):
             assert abs(float(c) - c0) < (1e-10 if dtype == 'f64' else 2e-5) * max(1.0, abs(c0))
             for u, v in zip(grad_blocks(g, D, S, M), grad_blocks(g0, D, S, M)):
                 assert rel(u, v) < gtol, (lrb, D, rel(u, v))
+            PB.oracle_check((c, g, a, L), X, y, params, S, M, dtype, label='lowrank_bwd %d' % lrb)
             J = S + M
             assert np.abs(g[-J:]).max() < (1e-9 if dtype == 'f64' else 1e-3) * np.abs(g).max()      # phases: zero gradient
             eng.close()
@@ -437,6 +440,7 @@ def test_random_shapes_with_the_optional_paths_forced(dtype, opts, ctol, gtol):
         assert abs(float(cost) - c0) < ctol * max(1.0, abs(c0)), (N, D, S, M, float(cost), c0)
         assert rel(grad, g0) < gtol, (N, D, S, M, rel(grad, g0))
         eng.close()
+        PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, alpha_li=dtype == 'f64', label='random shape')
 
 
 def test_non_finite_cost_comes_back_as_a_value_through_the_triple():
@@ -510,6 +514,7 @@ def test_one_context_through_a_random_sequence_of_calls(D, S, M, dtype, ctol, gt
             assert rel(alpha, a0) < max(ptol, 0 if dtype == 'f64' else 1e-3), (step, log)
             if wg:
                 assert rel(g, g0) < gtol, (step, log, rel(g, g0))
+                PB.oracle_check((c, g, alpha, Li), X, y, params, S, M, dtype, alpha_li=dtype == 'f64', label='sequence')
         elif op == 'rows':
             n = int(rng.choice([1, 10, max(1, X.shape[0] // 2), X.shape[0]]))
             idx = rng.integers(0, X.shape[0], n)
@@ -526,6 +531,7 @@ def test_one_context_through_a_random_sequence_of_calls(D, S, M, dtype, ctol, gt
             mu0, sd0 = O.predict(Xs, alpha, Li, params, S, M)
             assert mu.shape == (T, 1) and sd.shape == (T,)
             assert rel(mu, mu0) < ptol and rel(sd, sd0) < ptol, (step, log, rel(mu, mu0), rel(sd, sd0))
+            PB.check_predict(mu, sd, mu0, sd0, dtype)
         elif op == 'train':
             eng.opt_init('adam', learning_rate=1e-3)
             hist, alpha, Li = eng.train(2)
@@ -559,3 +565,4 @@ def test_lds_dma_apply_tiles_on_random_widths(dtype, dma, ctol, gtol):
         assert abs(float(cost) - c0) < ctol * max(1.0, abs(c0)), (N, D, S, M, float(cost), c0)
         assert rel(grad, g0) < gtol, (N, D, S, M, rel(grad, g0))
         eng.close()
+        PB.oracle_check((cost, grad, alpha, Li), X, y, params, S, M, dtype, alpha_li=dtype == 'f64', label='random shape')

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from tests import artifact_predict as AP
+from tests import parity as P
 
 pytestmark = pytest.mark.gpu
 
@@ -261,8 +262,9 @@ def test_training_with_the_sums_inside_the_library_equals_the_plain_loop(dtype):
 # max(1, |cost|), per-block gradient norms <= 1e-3, alpha / Li / mu* / sigma* as fp32 mode) against fp64 mode = the reference's arithmetic.
 # ---------------------------------------------------------------------------------------------------------------------------
 def _blocks(g, D, S, M):
-    o = 3 + D * S
-    return g[:3], g[3:o], g[o:o + M * S]
+    """(a, b, c), l_F, r_F of the flat vector, in tests/parity.py's layout"""
+    L = P.layout(D, S, M)
+    return g[[L['a'], L['b'], L['c']]], g[L['l_F']], g[L['r_F'].ravel()]
 
 
 @pytest.mark.parametrize('f16_gram', [1, 0])
@@ -309,11 +311,47 @@ def test_f16x3_mode_passes_fp32_modes_parity_tier(N, D, S, M, abc, f16_gram):
     print('f16x3', {k: '%.1e' % v for k, v in err['f16x3'].items()})
     e16, e32 = err['f16x3'], err['f32']
     assert e16['cost'] < 1e-5 and e16['g0'] < 1e-3 and e16['g1'] < 1e-3 and e16['g2'] < 1e-3
+    g, L = outs['f16x3'][1], P.layout(D, S, M)
+    for k, rho in zip(('a', 'b', 'c'), P.TOL['f16x3']['rho']):       # each scalar on its own: g0 is a norm over the three
+        assert abs(g[L[k]] - g64[L[k]]) <= rho * abs(g64[L[k]]), (k, g[L[k]], g64[L[k]])
     if not f16_gram:       # alpha and Li come from pass 1 (the fp32 Gram, untouched then): identical to fp32 mode's
         assert np.array_equal(outs['f16x3'][2], outs['f32'][2]) and np.array_equal(outs['f16x3'][3], outs['f32'][3])
     for k in ('cost', 'g0', 'g1', 'g2', 'alpha', 'Li', 'mu', 'sd'):
         assert e16[k] <= 4 * e32[k] + 2e-9, (k, e16[k], e32[k])
     assert e16['alpha'] < 1e-3 and e16['Li'] < 1e-3 and e16['mu'] < 1e-3 and e16['sd'] < 1e-3
+
+
+_ORACLE = {}
+
+
+@pytest.mark.parametrize('f16_gram', [1, 0])
+@pytest.mark.parametrize('N,D,S,M,abc', [(20000, 16, 16, 256, (-1.0, 0.0, -1.0)), (33000, 8, 32, 256, (-1.0, 0.0, -1.0)),
+                                          (40000, 32, 16, 496, (-2.0, 0.5, -1.0)), (30000, 24, 20, 300, (-0.5, -0.5, -2.0)),
+                                          (3000, 8, 4, 60, (-1.0, 0.0, -1.0)), (5000, 13, 8, 120, (-1.0, 0.0, -1.0))])
+def test_f16x3_mode_against_the_oracle(N, D, S, M, abc, f16_gram):
+    """f16x3 straight against the CPU oracle through tests/parity.py's block checks at fp32's row: the four shapes of
+    test_f16x3_mode_passes_fp32_modes_parity_tier (apply_dma = 2) and two with K <= 256 (fp32 register tiles for the apply)."""
+    from scfgp_amd import synth
+    from scfgp_amd.engine import HipEngine
+    from oracle import scfgp_oracle as O
+    seed = 0x5CF60A00 + M
+    X = synth.make_X(seed, N, D); y = synth.normal(seed + 1, 0, N).reshape(-1, 1)
+    params = synth.make_params(seed + 2, D, S, M, abc=abc)
+    Xs = synth.make_X(seed + 3, 3000, D)
+    if (N, M) not in _ORACLE:
+        _ORACLE[(N, M)] = P.oracle_all(X, y, params, S, M)
+    ref = _ORACLE[(N, M)]
+    e = HipEngine(D, S, M, 'f16x3')
+    e.set_option('gram64', 0); e.set_option('apply_dma', 2); e.set_option('f16_gram', f16_gram)
+    e.set_params(params); e.set_data(X, y)
+    res = e.eval()
+    mu, sd = e.predict(Xs, res[2], res[3])
+    e.close()
+    mu0, sd0 = O.predict(Xs, res[2], res[3], params, S, M)
+    r = P.check_all(res, ref, D, S, M, 'f16x3')
+    r['predict'] = P.check_predict(mu, sd, mu0, sd0, 'f16x3')
+    print('\nf16x3 vs oracle K %d f16_gram %d: %s' % (2 * (S + M), f16_gram, P.fmt(r)))
+    assert abs(float(res[0]) - ref['cost']) < 1e-5 * max(1.0, abs(ref['cost']))
 
 
 def test_f16x3_mode_at_the_headline_shape():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import scfgp_oracle as O
+from tests import parity as PB
 from tests.golden.make_oracle_kats import CASES, case_inputs
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +89,10 @@ def test_stages_match_oracle(name, dtype, tol):
     # 2 tr(Abar G) + ut^T Phi^T y + 2 sum q v + sum p mu needs neither matrix and appears in d_scalars after finish
     bbar_o = ora.x3[D * J + J]
     assert np.all(XZ[Dp:] == 0) and np.all(XZ[:, J:] == 0)
+    ref = PB.oracle_all(X, y, params, S, M)
+    colsa = ref['scale'][-J:] * N                                      # sum over rows of |Zbar| per column
+    t = PB.TOL[dtype]
+    assert np.all(np.abs(XZ[D, :J] - ora.x3[D * J:D * J + J]) <= t['beta'] * np.abs(ora.x3[D * J:D * J + J]) + t['tau'] * colsa)   # ones row
 
     cost, grad, alpha, Li_h = eng.finish(True)
     c_o, g_o, al_o, Li_o = ora.finish(True)
@@ -95,6 +100,7 @@ def test_stages_match_oracle(name, dtype, tol):
         name, dtype, abs(cost - c_o) / abs(c_o), rel(grad, g_o), rel(alpha, al_o), rel(Li_h, Li_o)))
     assert abs(cost - c_o) < (1e-10 if dtype == 'f64' else 1e-5) * max(1.0, abs(c_o))
     assert rel(grad, g_o) < ctol
+    print('%s %s blocks: %s' % (name, dtype, PB.fmt(PB.check_grad(grad, g_o, ref['scale'], D, S, M, dtype))))
     assert rel(alpha, al_o) < ctol and rel(Li_h, Li_o) < ctol
     sc = eng.debug_read('scalars', (32,))
     assert abs(sc[4] - bbar_o) < (1e-10 if dtype == 'f64' else ctol) * max(1.0, abs(bbar_o)), (sc[4], bbar_o)     # R_BBAR
