@@ -164,6 +164,26 @@ int scfgp_sample_weights(scfgp_ctx* ctx, const double* alpha, const double* Li, 
 int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp,
                  uint64_t seed, int mode, int noise, double* out);
 
+/* ---- joint posterior covariance between test points (no reference counterpart: the reference reports the marginals only) -------
+ * Under the weight posterior w ~ N(alpha, kappa A^-1) above, two function values have covariance kappa phi(x)^T A^-1 phi(x'); with
+ * A^-1 = Li^T Li that is
+ *     cov[i][j] = Cov[f(a_i), f(b_j)] = kappa <Li phi(a_i), Li phi(b_j)>        (Ta x Tb, row-major, fp64)
+ * the exact matrix of which the sample covariance of scfgp_sample's draws is an estimate.  Its diagonal is sigma*^2 - kappa.
+ * Xb == NULL is the symmetric form: Tb is ignored, the result is Ta x Ta, symmetric bit for bit and equal bit for bit to the cross form
+ * with Xb = Xa; noise != 0 adds kappa to its diagonal (the covariance of the noisy observations that scfgp_sample(..., noise = 1) draws).
+ * With Xb given, noise != 0 is SCFGP_EARG: row i of Xa and row j of Xb are different observations even if the numbers agree.
+ * mode 0: scaled inputs (as scfgp_predict); 1: column-selected raw inputs through the registered X scaler (as scfgp_predict_raw).  There
+ * is no raw-y mode: the y scaler's backward transform is not affine (Box-Cox, normal CDF), so the model defines no covariance in raw y
+ * units; scfgp_sample mode 2 is the route to joint statistics of raw y.
+ * Li as scfgp_eval returns it (entries above the diagonal are not read); alpha is not needed.  1 <= Tb <= 32768 (in the symmetric form,
+ * Ta); Ta >= 1 otherwise without limit: the rows of Xa go through in chunks and the result leaves through two staging panels, so device
+ * memory does not grow with Ta x Tb.  The products run in the context's precision (fp64 MFMA; exact fp32 MFMA with fp64 partial sums
+ * in SCFGP_F32 and SCFGP_F16X3, which agree bit for bit); an element's value depends on its two rows only, not on Ta, Tb or its place
+ * in the call.  The training state of the context survives.  SCFGP_EARG (with a scfgp_last_error text, before any device work) for bad
+ * arguments, a missing X scaler in mode 1 or parameters not set. */
+int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double* Xb, int64_t Tb, const double* Li, int mode, int noise,
+                      double* cov);
+
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded
  * over ranks each sweep ends in one sum over ranks.  The host framework (torch.distributed

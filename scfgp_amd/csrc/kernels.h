@@ -253,6 +253,14 @@ template <typename T>
 void sample_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode, const double* ysp,
                     const Scal* sc, double* out, hipStream_t st);
 
+// ---- predcov.hip, joint posterior covariance between test points (scfgp_predict_cov) ---------------------------------------------------
+// out[n][j] (n < nrows, j < Tb; row-major, leading dimension Tb, fp64) = kappa sum_k Ca[n][k] Cb[j][k] over the K features, + kappa
+// where row_base + n == j with `noise`.  Ca, Cb: C = Phi Li^T as apply_c leaves it (leading dimension Kp, columns K.. zero), with
+// round_up(nrows, 128) and round_up(Tb, 128) readable rows.
+template <typename T>
+void predcov(const Geom& g, const T* Ca, const T* Cb, int64_t nrows, int64_t Tb, int64_t row_base, int noise, const Scal* sc, double* out,
+             hipStream_t st);
+
 // ---- on-device update rules (SCFGP/Optimizer.py) --------------------------------------------
 struct OptHyper { double lr, b1, b2, eps, momentum; };   // b1 doubles as rho for rmsprop/adadelta; momentum < 0: no Nesterov
 // theta <- rule(theta, grad); st = [s1 | s2 | velocity]; tctr[0] = step counter, tctr[1] = index into hist

@@ -707,6 +707,14 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_predict_cov: the chunk's Phi* as predict_chunk forms it, then C = Phi* Li^T as predict_grad_chunk does (vpart / mupart land
+    // in the chunk's partials and are ignored)
+    static int cov_factor_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, T* C) {
+        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
+        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart, c->st, 0);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
     // scfgp_sample: the chunk's Phi* as predict_chunk forms it, then out (N x nsamp) = Phi* W and the epilogue (sample.hip)
     static int sample_chunk(scfgp_ctx* c, const Geom& g, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode,
                             double* out) {
@@ -1075,20 +1083,28 @@ static int ensure_pred_chunk(scfgp_ctx* c) {
     return SCFGP_OK;
 }
 
+// the factor-form buffers that the std gradient of scfgp_predict_grad and scfgp_predict_cov share (first call of either only): the
+// typed Li and two PRED_ROWS x Kp typed arrays (C = Phi* Li^T and V = C Li there; Ca and Cb here), padding columns zero
+static int ensure_pred_factor(scfgp_ctx* c) {
+    if (c->p_V) return SCFGP_OK;
+    const int64_t Kp = c->g.Kp;
+    const size_t ts = c->tsize();
+    int rc;
+    if ((rc = dmalloc(c, &c->p_Li, ts * Kp * Kp))) return rc;
+    if ((rc = dmalloc(c, &c->p_C, ts * PRED_ROWS * Kp))) return rc;
+    if ((rc = dmalloc(c, &c->p_V, ts * PRED_ROWS * Kp))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->p_C, 0, ts * PRED_ROWS * Kp, c->st));
+    HIPCHK(c, hipMemsetAsync(c->p_V, 0, ts * PRED_ROWS * Kp, c->st));
+    return SCFGP_OK;
+}
+
 // buffers of scfgp_predict_grad beside predict's own (first call only; the std gradient's on its first call)
 static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
     const Geom& g = c->g;
-    const int64_t Kp = g.Kp;
     const size_t ts = c->tsize();
     int rc;
     if (!c->p_FT && (rc = dmalloc(c, &c->p_FT, ts * round_up(g.J, 16) * predgrad_ft_cols(g.D)))) return rc;
-    if (want_std && !c->p_V) {
-        if ((rc = dmalloc(c, &c->p_Li, ts * Kp * Kp))) return rc;
-        if ((rc = dmalloc(c, &c->p_C, ts * PRED_ROWS * Kp))) return rc;
-        if ((rc = dmalloc(c, &c->p_V, ts * PRED_ROWS * Kp))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->p_C, 0, ts * PRED_ROWS * Kp, c->st));
-        HIPCHK(c, hipMemsetAsync(c->p_V, 0, ts * PRED_ROWS * Kp, c->st));
-    }
+    if (want_std && (rc = ensure_pred_factor(c))) return rc;
     return SCFGP_OK;
 }
 
@@ -1366,6 +1382,123 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(nchunks - 1))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// joint posterior covariance between test points (predcov.hip; contract in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+// A sibling of predict_impl and scfgp_sample: the same double-buffered upload, pack_data (X scaler in mode 1) and feature map per
+// chunk of PRED_ROWS rows, then C = Phi* Li^T by apply_c.  Cb (the rows of Xb) is formed once, into p_V; each chunk of Xa gives Ca
+// in p_C; in the symmetric case (Ta <= PRED_ROWS) Ca is both operands.  A chunk's rows of the result are computed in panels of R
+// rows x Tb, full rows in the symmetric case too (its symmetry comes from the commutativity of the products, predcov.hip), into one
+// of two staging panels that the copy stream drains into `cov` while the next panel computes: device memory does not grow with
+// Ta x Tb.
+static constexpr int64_t COV_PANEL_BYTES = (int64_t)128 << 20;   // per staging panel: the size scfgp_sample stages per chunk at 512 samples
+extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, const double* Xb, int64_t Tb, const double* Li, int mode,
+                                 int noise, double* cov) {
+    if (!c) return SCFGP_EARG;
+    if (!Xa || !Li || !cov || mode < 0 || mode > 1) { c->err = "predict_cov: bad arguments"; return SCFGP_EARG; }
+    const bool sym = Xb == nullptr;
+    if (sym) Tb = Ta;
+    if (Ta < 1) { c->err = "predict_cov: Ta must be at least 1"; return SCFGP_EARG; }
+    if (Tb < 1 || Tb > PRED_ROWS) {
+        c->err = sym ? "predict_cov: the symmetric form takes 1..32768 rows" : "predict_cov: Tb must lie in 1..32768";
+        return SCFGP_EARG;
+    }
+    if (!sym && noise) { c->err = "predict_cov: noise is defined for the symmetric form (Xb == NULL) only"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "predict_cov: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "predict_cov: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp;
+    const size_t ts = c->tsize();
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    // panel height: whole 128-row tiles within COV_PANEL_BYTES, no more than a chunk holds
+    const int64_t R = std::min<int64_t>(round_up(std::min<int64_t>(Ta, PRED_ROWS), 128),
+                                        std::max<int64_t>(128, COV_PANEL_BYTES / ((int64_t)sizeof(double) * Tb) / 128 * 128));
+    DevTmp raw, stage;                                            // Li / two chunks of X | two panels of the result
+    const int64_t rawstride = PRED_ROWS * g0.D;
+    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * R * Tb))) return rc;
+    // Li -> T1 (identity padding) -> the typed Li^T (AbarT: scratch outside adjoint..pass3) and Li, as predict_impl prepares them
+    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
+    pad_square(raw, g0.K, g0.Kp, c->d_T1, c->st);
+    if (c->dtype == SCFGP_F32) {
+        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
+    } else {
+        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    struct Events {
+        // up / fre: the two halves of raw (uploaded / free again); done / out: the two staging panels (computed / copied out)
+        hipEvent_t e[4][2] = {};
+        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
+    for (auto& p : ev.e)
+        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    // uploads: job 0 is Xb in the cross form, the chunks of Xa follow
+    const int64_t nchunks = (Ta + PRED_ROWS - 1) / PRED_ROWS, first = sym ? 0 : 1, njobs = nchunks + first;
+    auto job_rows = [&](int64_t job) { return job < first ? Tb : std::min<int64_t>(PRED_ROWS, Ta - (job - first) * PRED_ROWS); };
+    auto upload = [&](int64_t job) -> int {
+        const double* src = job < first ? Xb : Xa + (job - first) * PRED_ROWS * g0.D;
+        const int h = (int)(job & 1);
+        if (job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, src, sizeof(double) * job_rows(job) * g0.D, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    // panel p (rows [row0, row0 + n) of the result) to the host (pageable: the host waits in this call while the next panel computes)
+    struct Panel { int64_t row0, n; };
+    auto download = [&](int64_t p, Panel pn) -> int {
+        const int h = (int)(p & 1);
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
+        HIPCHK(c, hipMemcpyAsync(cov + pn.row0 * Tb, stage + h * R * Tb, sizeof(double) * pn.n * Tb, hipMemcpyDeviceToHost, c->copy_st));
+        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    const void* Bt = c->d_AbarT;
+    int64_t npanel = 0;
+    Panel prev = {0, 0};
+    if ((rc = upload(0))) return rc;
+    for (int64_t job = 0; job < njobs; ++job) {
+        const int h = (int)(job & 1);
+        Geom g = g0;
+        g.N = job_rows(job); g.Np = round_up(g.N, 256);
+        HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
+        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        HIPCHK(c, hipEventRecord(fre[h], c->st));
+        void* C = job < first ? c->p_V : c->p_C;
+        rc = c->dtype == SCFGP_F32 ? Impl<float>::cov_factor_chunk(c, g, (const float*)Bt, (float*)C)
+                                   : Impl<double>::cov_factor_chunk(c, g, (const double*)Bt, (double*)C);
+        if (rc) return rc;
+        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
+        if (job < first) continue;
+        const int64_t t0 = (job - first) * PRED_ROWS;
+        const char* Cb = (const char*)(sym ? c->p_C : c->p_V);
+        for (int64_t r0 = 0; r0 < g.N; r0 += R, ++npanel) {
+            const Panel pn = {t0 + r0, std::min<int64_t>(R, g.N - r0)};
+            const int ph = (int)(npanel & 1);
+            if (npanel >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[ph], 0));
+            const char* Ca = (const char*)c->p_C + ts * r0 * Kp;
+            double* o = stage + ph * R * Tb;
+            if (c->dtype == SCFGP_F32) predcov<float>(g0, (const float*)Ca, (const float*)Cb, pn.n, Tb, pn.row0, noise, c->d_sc, o, c->st);
+            else predcov<double>(g0, (const double*)Ca, (const double*)Cb, pn.n, Tb, pn.row0, noise, c->d_sc, o, c->st);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(done[ph], c->st));
+            if (npanel >= 1 && (rc = download(npanel - 1, prev))) return rc;
+            prev = pn;
+        }
+    }
+    if ((rc = download(npanel - 1, prev))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());

@@ -318,6 +318,43 @@ class HipEngine(object):
                                           int(bool(noise)), dptr(out)), 'sample')
         return out
 
+    PREDICT_COV_MODES = {'scaled': 0, 'raw': 1}
+
+    def predict_cov(self, Xa, Li, Xb=None, mode='scaled', noise=False):
+        """Joint posterior covariance of the function values at the rows of Xa and Xb (include/scfgp_hip.h: scfgp_predict_cov):
+        (Ta, Tb) float64, cov[i][j] = kappa <Li phi(a_i), Li phi(b_j)>, in the units of the scaled target.  Xb=None is the symmetric
+        form (Ta, Ta), symmetric bit for bit; noise=True (symmetric form only) adds kappa to its diagonal.  mode 'scaled': inputs as
+        predict takes them; 'raw': unscaled inputs through the registered X scaler, as predict_raw."""
+        if mode not in self.PREDICT_COV_MODES:
+            raise ValueError('predict_cov: mode must be one of %s' % sorted(self.PREDICT_COV_MODES))
+        m = self.PREDICT_COV_MODES[mode]
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('predict_cov: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+
+        def rows(X, name):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim != 2:
+                raise TypeError('%s must be a 2-d float64 array' % name)
+            if cols is not None:
+                X = X[:, cols]
+            X = np.ascontiguousarray(X)
+            if X.shape[1] != self.D:
+                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
+            return X
+        Xa = rows(Xa, 'Xa')
+        Xb = None if Xb is None else rows(Xb, 'Xb')
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if Li.shape != (self.K, self.K):
+            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        Ta, Tb = Xa.shape[0], (Xa.shape[0] if Xb is None else Xb.shape[0])
+        if Xb is not None and Tb == 0:
+            raise ValueError('predict_cov: Xb has no rows')           # an empty array has no pointer to tell it from Xb=None
+        cov = np.empty((Ta, Tb) if 0 < Tb <= 32768 else (0, 0))       # out of range: the library refuses before it writes
+        self._check(self.lib.scfgp_predict_cov(self.ctx, dptr(Xa), Ta, dptr(Xb), Tb, dptr(Li), m, int(bool(noise)), dptr(cov)),
+                    'predict_cov')
+        return cov
+
     # -- staged evaluation (row-sharded data parallelism) --------------------------------------
     def pass1(self):
         self._check(self.lib.scfgp_pass1(self.ctx), 'pass1')

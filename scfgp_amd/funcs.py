@@ -289,6 +289,12 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return self.engine.sample(Xs_raw, alpha, Li, nsamp, seed=seed, mode='y', noise=noise)
 
+    def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
+        """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.predict_cov(Xa_raw, Li, Xb=Xb_raw, mode='raw', noise=noise)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

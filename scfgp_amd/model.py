@@ -276,6 +276,18 @@ class SCFGP(object):
             raise TypeError('sample needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
         return owner.sample_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, noise=noise)
 
+    def predict_cov(self, Xs, Xs2=None, noise=False):
+        """Joint posterior covariance of the fitted model's function values between the raw rows Xs and Xs2 (None: among the rows of
+        Xs, a bit-for-bit symmetric matrix): (T, T2) = kappa phi(x)^T A^-1 phi(x').  Inputs are in raw X units; the covariance is that
+        of the SCALED target, the space the model is Gaussian in: the y scaler's backward transform is not affine (Box-Cox, normal
+        CDF), so no covariance in raw y units follows from the model.  For joint statistics of raw y draw functions with `sample`.
+        noise=True (Xs2=None only) adds the observation noise kappa to the diagonal; the diagonal then equals the squared scaled
+        std that pred_func reports (include/scfgp_hip.h: scfgp_predict_cov)."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('predict_cov needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        return owner.pred_cov_raw(Xs, self.X_scaler, self.Li, Xb_raw=Xs2, noise=noise)
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled

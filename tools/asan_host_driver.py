@@ -15,8 +15,20 @@ for (D, S, M) in [(13, 8, 64), (64, 32, 1024), (512, 64, 2048), (3, 2, 3), (8, 2
                 for tp in (0, 1):
                     assert lib.scfgp_selftest_row_splits(D, S, M, N, dt, ns, tp) == 0
                     n += 1
+# argument errors of scfgp_predict_cov that need no device: the null context, and (where a context exists) every check that precedes
+# the first device call
+x = (C.c_double * 4)(0.0, 0.0, 0.0, 0.0)
+xp = C.cast(x, C.POINTER(C.c_double))
+assert lib.scfgp_predict_cov(None, xp, 1, None, 0, xp, 0, 0, xp) == -1
+n += 1
 # a context on a GPU-less box: create fails cleanly inside hipSetDevice / hipMalloc, the error text is readable, destroy is safe
 rc = lib.scfgp_create(C.byref(ctx), 4, 2, 3, 0, 0, None)
 print('create on a GPU-less box ->', rc, lib.scfgp_last_error(ctx) if ctx else None)
+if ctx:
+    for args in [(None, 1, None, 0, xp, 0, 0, xp), (xp, 0, None, 0, xp, 0, 0, xp), (xp, 1, xp, 0, xp, 0, 0, xp),
+                 (xp, 1, xp, 32769, xp, 0, 0, xp), (xp, 1, xp, 1, xp, 0, 1, xp), (xp, 1, None, 0, xp, 1, 0, xp),
+                 (xp, 1, None, 0, xp, 2, 0, xp), (xp, 1, None, 0, xp, 0, 0, xp)]:     # the last: parameters not set
+        assert lib.scfgp_predict_cov(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'predict_cov')
+        n += 1
 if ctx: lib.scfgp_destroy(ctx)
 print('host-side calls under ASan/UBSan:', n + 4, 'ok')
