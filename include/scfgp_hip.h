@@ -184,6 +184,31 @@ int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alph
 int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double* Xb, int64_t Tb, const double* Li, int mode, int noise,
                       double* cov);
 
+/* ---- absorbing new observations into a fitted posterior (no reference counterpart: the reference refits on all rows) --------------
+ * The posterior of a Fourier-feature model is a Bayesian linear model in K weights, so n new rows enter it through a K x K update that
+ * never looks at the old rows.  With A = Phi^T Phi + lam I = L L^T, Li = L^-1, alpha = A^-1 Phi^T y a fit and (Xn, yn) new rows with
+ * features Phi_n at the SAME hyper-parameters:
+ *     C = Phi_n Li^T (n x K)         r = yn - Phi_n alpha              S = I + C^T C = M M^T  (M lower; eigenvalues >= 1)
+ *     Li' = M^-1 Li                  gamma = S^-1 C^T r                alpha' = alpha + Li^T gamma
+ * A' = A + Phi_n^T Phi_n = L S L^T = (L M)(L M)^T and L M is lower triangular with a positive diagonal, so Li' is THE inverse Cholesky
+ * factor of the fit on all rows and (alpha', Li') are what scfgp_eval returns on the concatenated data: everything that takes
+ * (alpha, Li) keeps working.  Nothing but alpha, Li and the parameters is needed (a model restored from a checkpoint has no rows).
+ * mode 0: scaled rows (as scfgp_predict); 1: column-selected raw Xn through the registered X scaler (as scfgp_predict_raw).  yn is always
+ * the SCALED target: the device has only the y scaler's backward transform.  alpha (K) and Li (K x K, entries above the diagonal are not
+ * read) as scfgp_eval returns them; alpha_out (K) and Li_out (K x K, lower triangular, zeros above the diagonal) may alias the inputs and
+ * are written only on success.  n >= 1 without limit: the rows go through in chunks whose C^T C and C^T r are summed in fp64, so device
+ * memory does not grow with n.  The feature map uses the context's CURRENT parameters; that they are the ones Li was computed with is the
+ * caller's contract (the library cannot check it).  The products run in the context's precision (fp64 MFMA; exact fp32 MFMA with fp64
+ * sums across 4096-row blocks in SCFGP_F32 and SCFGP_F16X3, which agree bit for bit); the K x K stage is fp64: Cholesky of S, and
+ * Li' = M^-1 Li as a lower-triangular x lower-triangular product that skips the zero blocks of both operands (K^3 / 3 flops).  The training
+ * state of the context survives (resident rows, exchange buffers, Li / B of the last evaluation, optimiser state, precision level).
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL pointers, n < 1, a bad mode, a missing X scaler in mode 1 or
+ * parameters not set; SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if the Cholesky of S fails: the outputs are
+ * untouched in all three cases.  Out of scope: a communicator / row-sharded form (the update is replicated work on n rows: every rank
+ * calls it with the same rows), removing observations, and keeping the factors resident on the device between calls. */
+int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
+                    double* alpha_out, double* Li_out);
+
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded
  * over ranks each sweep ends in one sum over ranks.  The host framework (torch.distributed

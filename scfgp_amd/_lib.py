@@ -43,6 +43,7 @@ SIGNATURES = {
     'scfgp_sample': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
+    'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_pass1': (C.c_int, [C.c_void_p]),
     'scfgp_factor': (C.c_int, [C.c_void_p]),
     'scfgp_pass2': (C.c_int, [C.c_void_p, C.c_int]),

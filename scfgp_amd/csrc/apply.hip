@@ -553,6 +553,20 @@ void ApplyKernels<T>::rowpredict(const Geom& g, const double* mupart, const doub
     hipLaunchKernelGGL((rowstats_kernel<1>), dim3(nblocks), dim3(256), 0, st, mupart, vpart, apply_njt<T>(g),
                        (const double*)nullptr, sc, mu, sd, (double*)nullptr, g.N, g.Np);
 }
+// r = y - mu on the live rows, 0 on the padding rows (the side vector of the update's Gram product: scfgp_condition)
+__global__ __launch_bounds__(256) void rowresidual_kernel(const double* __restrict__ mupart, int njt, const double* __restrict__ y,
+                                                          double* __restrict__ r, int64_t N, int64_t Np) {
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < Np; n += (int64_t)gridDim.x * 256) {
+        double mu = 0;
+        for (int t = 0; t < njt; ++t) mu += mupart[(int64_t)t * Np + n];
+        r[n] = n < N ? y[n] - mu : 0.0;
+    }
+}
+template <typename T>
+void ApplyKernels<T>::rowresidual(const Geom& g, const double* mupart, const double* y, double* r, hipStream_t st) {
+    const int nblocks = (int)((g.Np + 255) / 256 < 1024 ? (g.Np + 255) / 256 : 1024);
+    hipLaunchKernelGGL(rowresidual_kernel, dim3(nblocks), dim3(256), 0, st, mupart, apply_njt<T>(g), y, r, g.N, g.Np);
+}
 template struct ApplyKernels<double>;
 template struct ApplyKernels<float>;
 

@@ -132,6 +132,8 @@ struct ApplyKernels {
     // predictive mean / std                                          (SCFGP.py:143-144)
     static void rowpredict(const Geom& g, const double* mupart, const double* vpart, const Scal* sc, double* mu, double* sd,
                            hipStream_t st);
+    // residual of new rows under the old mean (scfgp_condition): r[n] = y[n] - sum_jt mupart[jt][n] for n < N, 0 on the padding rows
+    static void rowresidual(const Geom& g, const double* mupart, const double* y, double* r, hipStream_t st);
 };
 
 // ---- apply_f16.hip, gram_f16.hip: compute mode SCFGP_F16X3 -- the big products as a three-term fp16 split (a labelled secondary mode) ----
@@ -284,3 +286,24 @@ void kstage_adjoint(const KStage& k, const double* BWB, double* Abar, const Scal
 void kstage_adjoint_factor_form(const KStage& k, double* McBWB, double* Abar, const Scal* sc, hipStream_t st);
 // scalars[R_TRAG] = tr(Abar G), scalars[R_UTG] = ut^T Phi^T y from the summed packed G of exchange buffer 1 (after the adjoint)
 void kstage_bbar(const KStage& k, const double* packed, const double* Abar, double* part, hipStream_t st);
+
+// ---- posterior update (scfgp_condition): S = I + C^T C = M M^T, Li' = M^-1 Li, alpha' = alpha + Li^T S^-1 C^T r -----------------
+// All matrices Kp x Kp fp64 with identity padding; none of them is a buffer of KStage.
+struct KUpdate {
+    int K, Kp;
+    const double* packed;   // in: packed lower 128 x 128 tiles of C^T C, then C^T r (Kp) at packed + n_pk
+    int64_t n_pk;
+    const double* Li;       // in: the old factor (lower triangular, zeros above the diagonal: update_load_factor)
+    const double* alpha;    // in: the old weights (Kp, padding zero)
+    double *S;              // working matrix of the factorisation; on return Li' (lower triangular, zeros above the diagonal)
+    double *Lm, *Mi, *Si;   // M (diagonal blocks), M^-1 (its blocks above the diagonal must be zero on entry and stay so), S^-1
+    double *gamma, *alpha_out, *part;   // Kp, Kp, 32 Kp
+    int* flag;              // flag[0] = 1: S not positive definite (or NaN)
+};
+void kstage_update(const KUpdate& k, hipStream_t st);
+// host-layout K x K factor on the device (ld K, entries above the diagonal not read) <-> Kp x Kp lower triangular, identity padding
+void update_load_factor(const double* Li_host_layout, int K, int Kp, double* Li, hipStream_t st);
+void update_store_factor(const double* Li, int K, int Kp, double* Li_host_layout, hipStream_t st);
+// flag[1] = 1 if any of x[0..n) is NaN or Inf;  acc[0..n) += part[0..n)
+void update_check_finite(const double* x, int64_t n, int* flag, hipStream_t st);
+void update_accumulate(double* acc, const double* part, int64_t n, hipStream_t st);

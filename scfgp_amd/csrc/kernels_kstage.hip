@@ -682,3 +682,131 @@ void kstage_adjoint(const KStage& k, const double* BWB, double* Abar, const Scal
     hipLaunchKernelGGL(abar_kernel, dim3(1024), dim3(256), 0, st, k.B, BWB, Abar, k.h, k.alpha, Kp, sc);
     hipLaunchKernelGGL(adjoint_vec_kernel, dim3(1), dim3(256), 0, st, Abar, ld, k.K, Kp, k.h, k.alpha, k.ut, sc, k.scalars);
 }
+
+// ---------------------------------------------------------------------------
+// posterior update (scfgp_condition; derivation in include/scfgp_hip.h): with C = Phi_n Li^T of the new rows,
+//   S = I + C^T C = M M^T,  Li' = M^-1 Li,  gamma = S^-1 C^T r,  alpha' = alpha + Li^T gamma
+// on its own buffers (KUpdate): nothing of the evaluation's K x K stage is touched.
+// ---------------------------------------------------------------------------
+// host-layout K x K factor (ld K; entries above the diagonal are not read) -> Kp x Kp lower triangular, identity padding
+__global__ __launch_bounds__(256) void update_pad_lower_kernel(const double* __restrict__ src, int K, int Kp, double* __restrict__ dst) {
+    const int64_t total = (int64_t)Kp * Kp;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int i = (int)(e / Kp), j = (int)(e % Kp);
+        dst[e] = j > i ? 0.0 : (i < K ? src[(int64_t)i * K + j] : (i == j ? 1.0 : 0.0));
+    }
+}
+// ... and back: the K x K block of a Kp x Kp lower triangular matrix in host layout, zeros above the diagonal
+__global__ __launch_bounds__(256) void update_unpad_lower_kernel(const double* __restrict__ src, int K, int Kp, double* __restrict__ dst) {
+    const int64_t total = (int64_t)K * K;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int i = (int)(e / K), j = (int)(e % K);
+        dst[e] = j > i ? 0.0 : src[(int64_t)i * Kp + j];
+    }
+}
+// flag[1] = 1 if any of the n values is NaN or Inf
+__global__ __launch_bounds__(256) void update_nonfinite_kernel(const double* __restrict__ x, int64_t n, int* __restrict__ flag) {
+    bool bad = false;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) bad |= !isfinite(x[e]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) flag[1] = 1;
+}
+// acc += part (the Gram of one more chunk of rows)
+__global__ __launch_bounds__(256) void update_accumulate_kernel(double* __restrict__ acc, const double* __restrict__ part, int64_t n) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) acc[e] += part[e];
+}
+// packed lower 128 x 128 tiles of C^T C -> working matrix of the factorisation as kstage_unpack_kernel lays it out: lower 64 x 64
+// blocks of S = I + C^T C (the padding rows and columns of C^T C are zero, so the padding block is the identity by itself), the
+// strictly upper blocks := 0; padding blocks of Mi and of S^-1: identity
+__global__ __launch_bounds__(256) void update_unpack_kernel(const double* __restrict__ packed, int B, double* __restrict__ A, double* __restrict__ Mi,
+                                                            double* __restrict__ Si, int64_t ld, int nbk) {
+    const int t = blockIdx.x;
+    int ti = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    while (ti * (ti + 1) / 2 > t) --ti;
+    const int tj = t - ti * (ti + 1) / 2;
+    for (int e = blockIdx.y * 256 + threadIdx.x; e < B * B; e += gridDim.y * 256) {
+        const double v = packed[(int64_t)t * B * B + e];
+        const int i = ti * B + e / B, j = tj * B + e % B;
+        A[(int64_t)i * ld + j] = j / 64 > i / 64 ? 0.0 : (i == j ? v + 1.0 : v);
+        if (ti != tj) A[(int64_t)j * ld + i] = 0.0;
+        if (i / 64 >= nbk || j / 64 >= nbk) {
+            const double id = i == j ? 1.0 : 0.0;
+            Mi[(int64_t)i * ld + j] = id; Si[(int64_t)i * ld + j] = id;
+            if (ti != tj) { Mi[(int64_t)j * ld + i] = 0.0; Si[(int64_t)j * ld + i] = 0.0; }
+        }
+    }
+}
+// C = A . B of two LOWER TRIANGULAR matrices (A read [m][k], B read [k][n]; nb x nb blocks of 64, leading dimension ld), on the
+// fp64 MFMA tiles of gemm64: block (tm, tn), tn <= tm, contracts over k in [64 tn, 64 (tm + 1)) only -- A[m][k] = 0 beyond, B[k][n] = 0
+// before -- so the launch does K^3 / 3 flops where the full product does 2 K^3.  Every block of C is written: the blocks above
+// the diagonal and the upper halves of the diagonal blocks as zeros (block (tm, tn) writes its mirror block).  The blocks are
+// dealt longest contraction first.
+__global__ __launch_bounds__(KCfg::THREADS) void tri_ll_kernel(const double* __restrict__ A, const double* __restrict__ B, double* __restrict__ C,
+                                                               int64_t ld, int nb) {
+    typedef KCfg Cfg;
+    static_assert(Cfg::BM == 64 && Cfg::BN == 64, "64 x 64 blocks");
+    SMEM_DECL;
+    double* smem = reinterpret_cast<double*>(smem_raw);
+    // item t: diagonals d = tm - tn from nb - 1 down to 0; diagonal nb - 1 - s has s + 1 blocks
+    const int t = blockIdx.x;
+    int s = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
+    while ((s + 1) * (s + 2) / 2 <= t) ++s;
+    while (s * (s + 1) / 2 > t) --s;
+    const int tn = t - s * (s + 1) / 2, tm = tn + nb - 1 - s;
+    const int k0 = tn * Cfg::BN, nkt = ((tm + 1) * Cfg::BM - k0) / Cfg::BK;
+    v4d acc[Cfg::TM][Cfg::TN];
+    acc_zero<Cfg>(acc);
+    TrLoader<double, double, Cfg::BM, Cfg::BK, Cfg::LDA, Cfg::THREADS, false, false, 3> la(A + (int64_t)tm * Cfg::BM * ld + k0, ld, threadIdx.x);
+    NatLoader<double, double, Cfg::BN, Cfg::BK, Cfg::LDB, Cfg::THREADS, false, false, false, 3> lb(B + (int64_t)k0 * ld + tn * Cfg::BN, ld, threadIdx.x);
+    tile_mainloop_deep3<Cfg>(la, lb, nkt, acc, smem);
+    AccCoord<Cfg> co;
+#pragma unroll
+    for (int t1 = 0; t1 < Cfg::TM; ++t1)
+#pragma unroll
+        for (int r = 0; r < Cfg::MTr::NACC; ++r) {
+            const int row = co.row(t1, r);
+            double* c = C + (int64_t)(tm * Cfg::BM + row) * ld + tn * Cfg::BN;
+#pragma unroll
+            for (int t2 = 0; t2 < Cfg::TN; ++t2) {
+                const int col = co.col(t2);
+                c[col] = tm == tn && col > row ? 0.0 : acc[t1][t2][r];
+                if (tm != tn) C[(int64_t)(tn * Cfg::BN + row) * ld + tm * Cfg::BM + col] = 0.0;
+            }
+        }
+}
+// out[i] = base[i] + sum of the nparts partial sums of gemv_cols_part_kernel
+__global__ __launch_bounds__(256) void update_alpha_kernel(const double* __restrict__ base, const double* __restrict__ part, int nparts,
+                                                           double* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = 0;
+    for (int p = 0; p < nparts; ++p) s += part[(int64_t)p * n + i];
+    out[i] = base[i] + s;
+}
+
+void update_load_factor(const double* Li_host_layout, int K, int Kp, double* Li, hipStream_t st) {
+    hipLaunchKernelGGL(update_pad_lower_kernel, dim3(1024), dim3(256), 0, st, Li_host_layout, K, Kp, Li);
+}
+void update_store_factor(const double* Li, int K, int Kp, double* Li_host_layout, hipStream_t st) {
+    hipLaunchKernelGGL(update_unpad_lower_kernel, dim3(1024), dim3(256), 0, st, Li, K, Kp, Li_host_layout);
+}
+void update_check_finite(const double* x, int64_t n, int* flag, hipStream_t st) {
+    hipLaunchKernelGGL(update_nonfinite_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, x, n, flag);
+}
+void update_accumulate(double* acc, const double* part, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(update_accumulate_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, acc, part, n);
+}
+void kstage_update(const KUpdate& k, hipStream_t st) {
+    const int Kp = k.Kp, nts = Kp / 128, nbk = (k.K + 63) / 64, nb = Kp / 64;
+    const int64_t ld = Kp;
+    hipLaunchKernelGGL(update_unpack_kernel, dim3(nts * (nts + 1) / 2, 16), dim3(256), 0, st, k.packed, 128, k.S, k.Mi, k.Si, ld, nbk);
+    KStage f{}; f.K = k.K; f.Kp = Kp; f.A = k.S; f.T2 = k.Lm; f.Li = k.Mi; f.B = k.Si; f.flag = k.flag;
+    cholesky_inverse_gram(f, st);                                      // M in Lm's diagonal blocks, Mi = M^-1, Si = S^-1 = Mi^T Mi
+    // gamma = S^-1 (C^T r); alpha' = alpha + Li^T gamma (the OLD factor); Li' = Mi Li over S, which the factorisation is done with
+    hipLaunchKernelGGL(gemv_rows_kernel, dim3((Kp + 3) / 4), dim3(256), 0, st, k.Si, ld, k.packed + k.n_pk, k.gamma, Kp);
+    constexpr int PARTS = 32;
+    hipLaunchKernelGGL(gemv_cols_part_kernel, dim3((Kp + 255) / 256, PARTS), dim3(256), 0, st, k.Li, ld, k.gamma, k.part, Kp);
+    hipLaunchKernelGGL(update_alpha_kernel, dim3((Kp + 255) / 256), dim3(256), 0, st, k.alpha, k.part, PARTS, k.alpha_out, Kp);
+    allow_big_lds(tri_ll_kernel, KCfg::LDS_BYTES);
+    hipLaunchKernelGGL(tri_ll_kernel, dim3(nb * (nb + 1) / 2), dim3(KCfg::THREADS), KCfg::LDS_BYTES, st, k.Mi, k.Li, k.S, ld, nb);
+}

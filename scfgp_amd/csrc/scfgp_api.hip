@@ -183,6 +183,13 @@ struct scfgp_ctx {
     // ... and those of scfgp_predict_grad, allocated by its first call: FT = Fall^T typed; with the std gradient C = Phi* Li^T, V = C Li
     // (PRED_ROWS x Kp each, typed) and the typed Li
     void *p_FT = nullptr, *p_C = nullptr, *p_V = nullptr, *p_Li = nullptr;
+    // ... and those of scfgp_condition, allocated by its first call (ensure_update): the update stage's own K x K matrices (fp64: the old
+    // factor, S / Li', M, M^-1, S^-1; typed: Li^T), its vectors [alpha | gamma | alpha' | 32 partial sums] (Kp each), the summed and the
+    // per-chunk [packed C^T C | C^T r], targets and residuals of a chunk, the Gram launch's slabs, row weights and queue heads
+    // (u_flag: [0] Cholesky flag, [1] non-finite flag, [8..15] queue heads)
+    double *u_Li = nullptr, *u_S = nullptr, *u_Lm = nullptr, *u_Mi = nullptr, *u_Si = nullptr, *u_vec = nullptr, *u_acc = nullptr, *u_part = nullptr;
+    double *u_y = nullptr, *u_r = nullptr, *u_slabs = nullptr; size_t u_slabs_bytes = 0;
+    void* u_LiT = nullptr; float* u_ws2 = nullptr; int* u_flag = nullptr;
     // on-device optimiser + captured training iteration
     int opt_algo = -1; OptHyper opt_h{}; double *d_opt = nullptr, *d_tctr = nullptr, *d_hist = nullptr; int hist_cap = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; int64_t graph_N = -1; bool in_train = false, warm = false;
@@ -454,6 +461,8 @@ extern "C" void scfgp_destroy(scfgp_ctx* c) {
     dfree(c->d_flag); dfree(c->d_partial); dfree(c->d_work); dfree(c->d_grad);
     dfree(c->p_Xt); dfree(c->p_vpart); dfree(c->p_mupart); dfree(c->p_Phi);
     dfree(c->p_FT); dfree(c->p_C); dfree(c->p_V); dfree(c->p_Li);
+    dfree(c->u_Li); dfree(c->u_S); dfree(c->u_Lm); dfree(c->u_Mi); dfree(c->u_Si); dfree(c->u_vec); dfree(c->u_acc); dfree(c->u_part);
+    dfree(c->u_y); dfree(c->u_r); dfree(c->u_slabs); dfree(c->u_LiT); dfree(c->u_ws2); dfree(c->u_flag);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->graph) hipGraphDestroy(c->graph);
     dfree(c->d_opt); dfree(c->d_tctr); dfree(c->d_hist);
@@ -712,6 +721,23 @@ template <typename T> struct Impl {
     static int cov_factor_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, T* C) {
         SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
         SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart, c->st, 0);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // scfgp_condition: C = Phi_n Li^T of the chunk's rows as cov_factor_chunk forms it (mupart = slices of Phi_n alpha), the residual
+    // r = y - Phi_n alpha, then [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the
+    // chunk's geometry with the update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows
+    // (never the fp16 split: an f16x3 context runs fp32 mode's kernels here)
+    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, double* out) {
+        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
+        SK::apply_c(g, (const T*)c->p_Phi, (const T*)c->u_LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->u_vec, c->u_vec, c->p_mupart,
+                    c->st, 0);
+        SK::rowresidual(g, c->p_mupart, c->u_y, c->u_r, c->st);
+        const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
+        double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
+        SK::gram(g, (const T*)c->p_C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
+        reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
+        reduce_side(sidepart, rs.nsplit, g.Kp, g.gfull * g.tile + g.gstrip * 64, out + c->n_pk, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
@@ -1502,6 +1528,137 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// absorbing new observations into a fitted posterior (kernels_kstage.hip: kstage_update; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+// row splits of the update's Gram product over a chunk of Np rows, and the slabs they need
+static RowSplits update_splits(const scfgp_ctx* c, int64_t Np) {
+    const bool f32 = c->dtype == SCFGP_F32;
+    return gram_row_splits(f32 ? SweepKernels<float>::gram_jobs(c->g) : SweepKernels<double>::gram_jobs(c->g), Np, f32, 0, 1);
+}
+// the update stage's own buffers (first call only; the slabs grow to what the call's chunks need)
+static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
+    const int64_t Kp = c->g.Kp, K2 = Kp * Kp;
+    int rc;
+    if (!c->u_flag) {
+        if ((rc = dmalloc(c, &c->u_Li, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_S, sizeof(double) * K2)) ||
+            (rc = dmalloc(c, &c->u_Lm, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_Mi, sizeof(double) * K2)) ||
+            (rc = dmalloc(c, &c->u_Si, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_LiT, c->tsize() * K2)) ||
+            (rc = dmalloc(c, &c->u_vec, sizeof(double) * 35 * Kp)) || (rc = dmalloc(c, &c->u_acc, sizeof(double) * (c->n_pk + Kp))) ||
+            (rc = dmalloc(c, &c->u_part, sizeof(double) * (c->n_pk + Kp))) || (rc = dmalloc(c, &c->u_y, sizeof(double) * PRED_ROWS)) ||
+            (rc = dmalloc(c, &c->u_r, sizeof(double) * PRED_ROWS)) || (rc = dmalloc(c, &c->u_ws2, sizeof(float) * 2 * (PRED_ROWS + 32))))
+            return rc;
+        HIPCHK(c, hipMemsetAsync(c->u_Mi, 0, sizeof(double) * K2, c->st));       // its blocks above the diagonal stay zero for good
+        HIPCHK(c, hipMemsetAsync(c->u_ws2, 0, sizeof(float) * 2 * (PRED_ROWS + 32), c->st));
+        if ((rc = dmalloc(c, &c->u_flag, sizeof(int) * 16))) return rc;
+    }
+    if (slabs_bytes > c->u_slabs_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        dfree(c->u_slabs); c->u_slabs_bytes = 0;
+        if ((rc = dmalloc(c, &c->u_slabs, slabs_bytes))) return rc;
+        c->u_slabs_bytes = slabs_bytes;
+    }
+    return SCFGP_OK;
+}
+
+// A sibling of scfgp_predict_cov: the same double-buffered upload (the targets ride behind the rows of their chunk), pack_data (X
+// scaler in mode 1), feature map and C = Phi_n Li^T per chunk of PRED_ROWS rows; each chunk adds its C^T C and C^T r to a running
+// fp64 sum, and one K x K stage turns the sum into the new factors.  The outputs are fetched only when the stage succeeded.
+extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
+                               double* alpha_out, double* Li_out) {
+    if (!c) return SCFGP_EARG;
+    if (!Xn || !yn || !alpha || !Li || !alpha_out || !Li_out || mode < 0 || mode > 1) { c->err = "condition: bad arguments"; return SCFGP_EARG; }
+    if (n < 1) { c->err = "condition: n must be at least 1"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "condition: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "condition: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
+    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    {   // slabs of the widest split among the call's chunk shapes (full chunks and the ragged last one)
+        const int nts = Kp / g0.tile, ntiles = nts * (nts + 1) / 2;
+        size_t need = 0;
+        for (int64_t np : {round_up(std::min<int64_t>(n, PRED_ROWS), 256), round_up(n - (nchunks - 1) * PRED_ROWS, 256)})
+            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
+        if ((rc = ensure_update(c, need))) return rc;
+    }
+    DevTmp raw;                                                   // Li in host layout (in, then out) / two chunks of [X | y]
+    const int64_t rawstride = PRED_ROWS * (g0.D + 1);
+    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    double* d_alpha = c->u_vec; double* d_gamma = c->u_vec + Kp; double* d_alpha_out = c->u_vec + 2 * Kp; double* d_parts = c->u_vec + 3 * Kp;
+    HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
+    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
+    update_load_factor(raw, g0.K, g0.Kp, c->u_Li, c->st);
+    HIPCHK(c, hipMemsetAsync(d_alpha, 0, sizeof(double) * Kp, c->st));
+    HIPCHK(c, hipMemcpyAsync(d_alpha, alpha, sizeof(double) * g0.K, hipMemcpyHostToDevice, c->st));
+    update_check_finite(c->u_Li, K2, c->u_flag, c->st);
+    update_check_finite(d_alpha, Kp, c->u_flag, c->st);
+    if (c->dtype == SCFGP_F32) {
+        SweepKernels<float>::convert_transposed(c->u_Li, (float*)c->u_LiT, g0.K, g0.Kp, c->st);
+        SweepKernels<float>::convert(c->u_Li, (float*)c->p_Li, g0.K, g0.Kp, c->st);
+    } else {
+        SweepKernels<double>::convert_transposed(c->u_Li, (double*)c->u_LiT, g0.K, g0.Kp, c->st);
+        SweepKernels<double>::convert(c->u_Li, (double*)c->p_Li, g0.K, g0.Kp, c->st);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    struct Events {
+        hipEvent_t up[2] = {nullptr, nullptr}, fre[2] = {nullptr, nullptr};
+        ~Events() { for (int i = 0; i < 2; ++i) { if (up[i]) (void)hipEventDestroy(up[i]); if (fre[i]) (void)hipEventDestroy(fre[i]); } }
+    } ev;
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(c, hipEventCreateWithFlags(&ev.up[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&ev.fre[i], hipEventDisableTiming));
+    }
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) -> int {
+        const int64_t t0 = i * PRED_ROWS, m = rows_of(i);
+        const int h = (int)(i & 1);
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.fre[h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xn + t0 * g0.D, sizeof(double) * m * g0.D, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride + PRED_ROWS * g0.D, yn + t0, sizeof(double) * m, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(ev.up[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const int h = (int)(i & 1);
+        Geom g = g0;
+        g.N = rows_of(i); g.Np = round_up(g.N, 256);
+        HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
+        pack_data(g, raw + h * rawstride, raw + h * rawstride + PRED_ROWS * g0.D, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0,
+                  c->d_xscale);
+        HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
+        const RowSplits rs = update_splits(c, g.Np);
+        double* out = i == 0 ? c->u_acc : c->u_part;
+        rc = c->dtype == SCFGP_F32 ? Impl<float>::update_chunk(c, g, rs, out) : Impl<double>::update_chunk(c, g, rs, out);
+        if (rc) return rc;
+        if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    // non-finite rows or targets have reached C^T C or C^T r by now
+    update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
+    KUpdate k;
+    k.K = g0.K; k.Kp = g0.Kp; k.packed = c->u_acc; k.n_pk = c->n_pk; k.Li = c->u_Li; k.alpha = d_alpha; k.S = c->u_S; k.Lm = c->u_Lm;
+    k.Mi = c->u_Mi; k.Si = c->u_Si; k.gamma = d_gamma; k.alpha_out = d_alpha_out; k.part = d_parts; k.flag = c->u_flag;
+    kstage_update(k, c->st);
+    update_check_finite(c->u_S, K2, c->u_flag, c->st);
+    update_check_finite(d_alpha_out, Kp, c->u_flag, c->st);
+    update_store_factor(c->u_S, g0.K, g0.Kp, raw, c->st);
+    HIPCHK(c, hipGetLastError());
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (flags[1]) { c->err = "condition: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
+    if (flags[0]) { c->err = "condition: I + C^T C is not positive definite"; return SCFGP_ENOTPD; }
+    HIPCHK(c, hipMemcpyAsync(Li_out, raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(alpha_out, d_alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
     return SCFGP_OK;
 }
 

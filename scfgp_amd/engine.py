@@ -484,11 +484,47 @@ class HipEngine(object):
 
     CONDITION = ('cond_est', 'level', 'gram_fp64', 'alpha_err_fp32', 'threshold', 'threshold_w', 'Lmin2', 'Lmax2', 'Bmax')
 
-    def condition(self):
-        """Condition estimate of A and the precision level of the last finished evaluation (scfgp_get_condition)."""
+    CONDITION_MODES = {'scaled': 0, 'raw': 1}
+
+    def condition(self, Xn=None, yn=None, alpha=None, Li=None, mode='scaled'):
+        """Two things under one name.  Without arguments: the condition estimate of A and the precision level of the last finished
+        evaluation (scfgp_get_condition), a dict.  With rows: absorb the observations (Xn, yn) into the fitted posterior (alpha, Li)
+        (include/scfgp_hip.h: scfgp_condition) and return (alpha' (K,1), Li' (K,K)), the factors of the fit on the old rows and the new
+        ones together, at the context's current parameters.  mode 'scaled': Xn as predict takes it; 'raw': unscaled Xn through the
+        registered X scaler, as predict_raw.  yn (n,) or (n,1) is the SCALED target in either mode."""
+        if Xn is not None or yn is not None or alpha is not None or Li is not None:
+            return self._condition(Xn, yn, alpha, Li, mode)
         out = np.zeros(len(self.CONDITION))
         self._check(self.lib.scfgp_get_condition(self.ctx, dptr(out), out.size), 'get_condition')
         return dict(zip(self.CONDITION, out.tolist()))
+
+    def _condition(self, Xn, yn, alpha, Li, mode):
+        if mode not in self.CONDITION_MODES:
+            raise ValueError('condition: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        if Xn is None or yn is None or alpha is None or Li is None:
+            raise ValueError('condition: Xn, yn, alpha and Li are all needed')
+        m = self.CONDITION_MODES[mode]
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('condition: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        Xn = np.asarray(Xn, dtype=np.float64)
+        if Xn.ndim != 2:
+            raise TypeError('Xn must be a 2-d float64 array')
+        if cols is not None:
+            Xn = Xn[:, cols]
+        Xn = np.ascontiguousarray(Xn)
+        if Xn.shape[1] != self.D:
+            raise ValueError('Xn has %d columns, expected %d' % (Xn.shape[1], self.D))
+        yn = np.ascontiguousarray(yn, dtype=np.float64).reshape(-1)
+        if yn.size != Xn.shape[0]:
+            raise ValueError('yn has %d entries for %d rows' % (yn.size, Xn.shape[0]))
+        alpha, Li = self._factors(alpha, Li)
+        alpha_out = np.empty((self.K, 1)); Li_out = np.empty((self.K, self.K))
+        rc = self.lib.scfgp_condition(self.ctx, dptr(Xn), dptr(yn), Xn.shape[0], dptr(alpha), dptr(Li), m, dptr(alpha_out), dptr(Li_out))
+        if rc == -4:                # nothing was delivered (unlike an evaluation's NaN cost): an error whatever self.nonfinite says
+            raise FloatingPointError('condition: %s' % self.last_error())
+        self._check(rc, 'condition')
+        return alpha_out, Li_out
 
     def last_error(self):
         """Message of the last failure -- or refusal (a precision level whose buffers could not be had) -- on this context."""

@@ -295,6 +295,13 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.predict_cov(Xa_raw, Li, Xb=Xb_raw, mode='raw', noise=noise)
 
+    def condition_raw(self, X_raw, y_scaled, x_scaler, alpha, Li):
+        """The factors (alpha', Li') of the posterior (alpha, Li) after the observations (X_raw, y_scaled) are absorbed into it, at the
+        shared parameter vector: raw rows through the X scaler on the device, targets already scaled (engine.condition)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.condition(X_raw, y_scaled, alpha, Li, mode='raw')
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

@@ -288,6 +288,19 @@ class SCFGP(object):
             raise TypeError('predict_cov needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
         return owner.pred_cov_raw(Xs, self.X_scaler, self.Li, Xb_raw=Xs2, noise=noise)
 
+    def condition(self, X, y):
+        """Absorb the observations (X, y), raw inputs (n,D) and raw targets (n,1), into the fitted posterior: self.alpha and self.Li
+        become those of the fit on the rows seen so far and these together, at the current hyper-parameters, through a K x K update
+        that needs no old rows (include/scfgp_hip.h: scfgp_condition) -- so it works on a model restored by load() that never saw
+        set_data.  The scalers are the fitted ones: they are not refitted.  self.X / self.y are NOT touched: a later optimize() or
+        set_data() recomputes the factors from the training set it holds, without the absorbed rows.  Returns self."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('condition needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        ys = np.asarray(self.y_scaler.forward_transform(np.asarray(y, dtype=np.float64).reshape(-1, 1)), dtype=np.float64)
+        self.alpha, self.Li = owner.condition_raw(X, ys, self.X_scaler, self.alpha, self.Li)
+        return self
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
