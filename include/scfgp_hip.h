@@ -209,6 +209,36 @@ int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double
 int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                     double* alpha_out, double* Li_out);
 
+/* ---- exact leave-one-out / leave-block-out predictions of rows that are IN the fit (no reference counterpart: the reference refits) --
+ * How well does the fitted model predict rows it has not seen -- without a refit.  With A = Phi^T Phi + lam I = L L^T, Li = L^-1,
+ * alpha = A^-1 Phi^T y the fit on all rows and I a set of b of ITS rows (features Phi_I, targets y_I):
+ *     C = Phi_I Li^T (b x K)         H = C C^T = Phi_I A^-1 Phi_I^T  (eigenvalues in [0, 1): lam > 0)        r = y_I - Phi_I alpha
+ *     I - H = R R^T (R lower)        e = y_I - mu^{-I} = (I - H)^-1 r          Sigma^{-I} = kappa (I - H)^-1  (noise included, as predict)
+ *     log p(y_I | the other rows) = -1/2 [ |R^-1 r|^2 / kappa + b log(2 pi kappa) - 2 sum_i log R_ii ]         leverage h_i = H_ii
+ * (Woodbury on A - Phi_I^T Phi_I; b = 1: e = r / (1 - h), sigma^2 = kappa / (1 - h)).  mu^{-I} and sigma_i = sqrt(kappa [(I - H)^-1]_ii)
+ * are exactly what scfgp_predict returns for the rows I from the fit on the OTHER rows.
+ * X (n x D), y (n, the SCALED targets): rows that are in the fit (alpha, Li) was computed from, at the context's current parameters --
+ * the caller's contract, as in scfgp_condition.  mode 0: scaled rows; 1: column-selected raw rows through the registered X scaler.
+ * X == NULL && y == NULL: the rows made resident by scfgp_set_data (n is ignored, mode must be 0); they are featurised again chunk by
+ * chunk from the stored rows at the current parameters, never read from the evaluation's working set (which may hold a minibatch).
+ * block (1..64): the held-out sets are the consecutive rows [j block, min(n, (j + 1) block)) of the call's rows, the last one may be
+ * ragged; for other folds permute the rows.  Outputs: mu, std (n each): held-out mean and std of every row when its block is left out;
+ * lev (n, may be NULL): h_i; stats (8 doubles, may be NULL), with e = y - mu: [0] n, [1] sum e^2, [2] sum |e|, [3] sum_i log N(y_i; mu_i,
+ * std_i^2), [4] sum over blocks of the joint log density (block 1: the same number as [3], bit for bit), [5] max h_i, [6] number of
+ * blocks, [7] 0.  The sums are fp64, formed from the rounded outputs in block order by one thread: the same bits on every run.
+ * n >= 1 without limit: the rows go through in chunks of floor(32768 / block) whole blocks, so device memory does not grow with n.  A
+ * row's outputs depend on the rows of its own block only, bit for bit (not on n, the chunk or the block's position).  C runs in the
+ * context's precision (SCFGP_F16X3 contexts run fp32 mode's kernels and agree with it bit for bit); H = C C^T is formed by fp64 MFMA and
+ * everything after it is fp64.  The training state of the context survives (resident rows, exchange buffers, optimiser state, precision
+ * level).  SCFGP_EARG (with a scfgp_last_error text, before any device work) for bad pointers, mode or block, a missing X scaler in mode
+ * 1, no resident rows, or parameters not set; SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if some I - H has no
+ * Cholesky factor (the rows were not in the fit): the message names the first such block.  On these two stats is untouched and mu, std,
+ * lev hold nothing of use.  Row-sharded use needs no communicator: each rank calls it on its own rows with the common (alpha, Li) and
+ * the caller adds the stats ([5]: the maximum).  Out of scope: folds of more than 64 rows or of rows that are not consecutive (they want
+ * the K x K downdate), gradients of these numbers in the hyper-parameters, raw-y units, and factors kept on the device between calls. */
+int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode, int block,
+              double* mu, double* std, double* lev, double* stats);
+
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded
  * over ranks each sweep ends in one sum over ranks.  The host framework (torch.distributed
@@ -323,7 +353,8 @@ int scfgp_train(scfgp_ctx* ctx, int n_iters, double* cost_hist, double* alpha, d
 int scfgp_get_condition(scfgp_ctx* ctx, double* out, int n);
 
 /* ---- introspection ------------------------------------------------------------------------ */
-/* padded sizes the device buffers use: out[0]=K, out[1]=Kp, out[2]=Jp, out[3]=Dp, out[4]=Np, out[5]=P, out[6]=tile */
+/* padded sizes the device buffers use: out[0]=K, out[1]=Kp, out[2]=Jp, out[3]=Dp, out[4]=Np, out[5]=P, out[6]=tile (n >= 7),
+ * out[7]=rows made resident by scfgp_set_data, 0 without any (n >= 8) */
 int scfgp_get_dims(scfgp_ctx* ctx, int64_t* out, int n);
 /* profiling: enable per-stage hipEvent timing; after an evaluation read back up to n
  * (name, milliseconds) pairs.  Returns the number of stages recorded. */

@@ -44,6 +44,8 @@ SIGNATURES = {
                                _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
+    'scfgp_loo': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p,
+                            _c_double_p, _c_double_p]),
     'scfgp_pass1': (C.c_int, [C.c_void_p]),
     'scfgp_factor': (C.c_int, [C.c_void_p]),
     'scfgp_pass2': (C.c_int, [C.c_void_p, C.c_int]),

@@ -307,3 +307,11 @@ void update_store_factor(const double* Li, int K, int Kp, double* Li_host_layout
 // flag[1] = 1 if any of x[0..n) is NaN or Inf;  acc[0..n) += part[0..n)
 void update_check_finite(const double* x, int64_t n, int* flag, hipStream_t st);
 void update_accumulate(double* acc, const double* part, int64_t n, hipStream_t st);
+
+// ---- loo.hip: exact leave-block-out predictions of rows that are in the fit (scfgp_loo) ------------------------------------------
+// C (typed, ld Kp) = Phi_I Li^T, r = y - Phi_I alpha and y of the chunk's g.N rows, whose first block has the call-wide index blk0:
+// mu, sd, lev (may be NULL) of every row, one record of 5 doubles per block into rec, then the records added in block order into acc
+// ([0..3] sums, [4] max h).  bad[0] != 0: a non-finite h, r or y; bad[1]: the smallest block index whose I - H has no Cholesky factor.
+template <typename T>
+void loo_blocks(const Geom& g, const T* C, const double* r, const double* y, int block, int64_t blk0, const Scal* sc, double* mu,
+                double* sd, double* lev, double* rec, double* acc, unsigned long long* bad, hipStream_t st);

@@ -190,6 +190,10 @@ struct scfgp_ctx {
     double *u_Li = nullptr, *u_S = nullptr, *u_Lm = nullptr, *u_Mi = nullptr, *u_Si = nullptr, *u_vec = nullptr, *u_acc = nullptr, *u_part = nullptr;
     double *u_y = nullptr, *u_r = nullptr, *u_slabs = nullptr; size_t u_slabs_bytes = 0;
     void* u_LiT = nullptr; float* u_ws2 = nullptr; int* u_flag = nullptr;
+    // ... and those of scfgp_loo, allocated by its first call (ensure_loo): targets and residuals of a chunk, one record per block of a
+    // chunk, two staging halves of [mu | std | lev], the running stats ([0..3] sums, [4] max h) and the flags ([0] non-finite, [1] first
+    // block without a Cholesky factor)
+    double *l_y = nullptr, *l_r = nullptr, *l_rec = nullptr, *l_out = nullptr, *l_acc = nullptr; unsigned long long* l_bad = nullptr;
     // on-device optimiser + captured training iteration
     int opt_algo = -1; OptHyper opt_h{}; double *d_opt = nullptr, *d_tctr = nullptr, *d_hist = nullptr; int hist_cap = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; int64_t graph_N = -1; bool in_train = false, warm = false;
@@ -463,6 +467,7 @@ extern "C" void scfgp_destroy(scfgp_ctx* c) {
     dfree(c->p_FT); dfree(c->p_C); dfree(c->p_V); dfree(c->p_Li);
     dfree(c->u_Li); dfree(c->u_S); dfree(c->u_Lm); dfree(c->u_Mi); dfree(c->u_Si); dfree(c->u_vec); dfree(c->u_acc); dfree(c->u_part);
     dfree(c->u_y); dfree(c->u_r); dfree(c->u_slabs); dfree(c->u_LiT); dfree(c->u_ws2); dfree(c->u_flag);
+    dfree(c->l_y); dfree(c->l_r); dfree(c->l_rec); dfree(c->l_out); dfree(c->l_acc); dfree(c->l_bad);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->graph) hipGraphDestroy(c->graph);
     dfree(c->d_opt); dfree(c->d_tctr); dfree(c->d_hist);
@@ -738,6 +743,17 @@ template <typename T> struct Impl {
         SK::gram(g, (const T*)c->p_C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
         reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
         reduce_side(sidepart, rs.nsplit, g.Kp, g.gfull * g.tile + g.gstrip * 64, out + c->n_pk, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // scfgp_loo: C = Phi_I Li^T and r = y - Phi_I alpha of the chunk's rows as update_chunk forms them, then the block kernel and the
+    // ordered sum of its records (loo.hip)
+    static int loo_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, int block, int64_t blk0, double* mu, double* sd, double* lev) {
+        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
+        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart,
+                    c->st, 0);
+        SK::rowresidual(g, c->p_mupart, c->l_y, c->l_r, c->st);
+        loo_blocks<T>(g, (const T*)c->p_C, c->l_r, c->l_y, block, blk0, c->d_sc, mu, sd, lev, c->l_rec, c->l_acc, c->l_bad, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
@@ -1663,6 +1679,141 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
 }
 
 // ----------------------------------------------------------------------------------------------
+// exact leave-one-out / leave-block-out predictions of rows that are in the fit (loo.hip; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int LOO_MAX_BLOCK = 64;
+static int ensure_loo(scfgp_ctx* c) {
+    if (c->l_bad) return SCFGP_OK;
+    int rc;
+    if ((rc = dmalloc(c, &c->l_y, sizeof(double) * PRED_ROWS)) || (rc = dmalloc(c, &c->l_r, sizeof(double) * PRED_ROWS)) ||
+        (rc = dmalloc(c, &c->l_rec, sizeof(double) * 5 * PRED_ROWS)) || (rc = dmalloc(c, &c->l_out, sizeof(double) * 6 * PRED_ROWS)) ||
+        (rc = dmalloc(c, &c->l_acc, sizeof(double) * 8)) || (rc = dmalloc(c, &c->l_bad, sizeof(unsigned long long) * 2)))
+        return rc;
+    return SCFGP_OK;
+}
+
+// A sibling of scfgp_condition: the same double-buffered upload with the targets behind the rows of their chunk (resident rows are
+// read where they lie: d_Xraw / d_yraw, never the evaluation's working set), pack_data, feature map, C = Phi_I Li^T and the residual
+// per chunk; then the block kernel.  A chunk holds floor(32768 / block) whole blocks, so no block straddles two chunks.  mu | std | lev
+// leave through two staging halves on the copy stream; the stats and the flags are fetched once, at the end.
+extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode,
+                         int block, double* mu, double* sd, double* lev, double* stats) {
+    if (!c) return SCFGP_EARG;
+    const bool resident = !X && !y;
+    if ((!X) != (!y) || !alpha || !Li || !mu || !sd || mode < 0 || mode > 1) { c->err = "loo: bad arguments"; return SCFGP_EARG; }
+    if (block < 1 || block > LOO_MAX_BLOCK) { c->err = "loo: block must lie in 1..64"; return SCFGP_EARG; }
+    if (resident) {
+        if (mode != 0) { c->err = "loo: resident rows are scaled rows (mode must be 0)"; return SCFGP_EARG; }
+        if (!c->have_data || c->Nstore < 1) { c->err = "loo: no resident rows (scfgp_set_data)"; return SCFGP_EARG; }
+        n = c->Nstore;
+    }
+    if (n < 1) { c->err = "loo: n must be at least 1"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "loo: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "loo: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp;
+    const int64_t CH = PRED_ROWS / block * block;               // rows per chunk: whole blocks
+    const int64_t nchunks = (n + CH - 1) / CH;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    if ((rc = ensure_loo(c))) return rc;
+    DevTmp raw;                                                   // Li in host layout / two chunks of [X | y]
+    const int64_t rawstride = PRED_ROWS * (g0.D + 1);
+    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, resident ? 0 : 2 * rawstride)))) return rc;
+    // Li -> T1 (identity padding) -> the typed Li^T (AbarT: scratch outside adjoint..pass3) and Li; alpha, as predict_impl prepares them
+    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
+    pad_square(raw, g0.K, g0.Kp, c->d_T1, c->st);
+    HIPCHK(c, hipMemsetAsync(c->alpha_pred(), 0, sizeof(double) * Kp, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->alpha_pred(), alpha, sizeof(double) * g0.K, hipMemcpyHostToDevice, c->st));
+    if (c->dtype == SCFGP_F32) {
+        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
+    } else {
+        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
+    }
+    const unsigned long long bad0[2] = {0ull, ~0ull};
+    HIPCHK(c, hipMemsetAsync(c->l_acc, 0, sizeof(double) * 8, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->l_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    struct Events {
+        // up / fre: the two halves of raw (uploaded / free again); done / copied: the two staging halves (computed / copied out)
+        hipEvent_t e[4][2] = {};
+        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
+    for (auto& p : ev.e)
+        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(CH, n - i * CH); };
+    auto upload = [&](int64_t i) -> int {
+        if (resident) return SCFGP_OK;
+        const int64_t t0 = i * CH, m = rows_of(i);
+        const int h = (int)(i & 1);
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, X + t0 * g0.D, sizeof(double) * m * g0.D, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride + PRED_ROWS * g0.D, y + t0, sizeof(double) * m, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    auto download = [&](int64_t i) -> int {
+        const int64_t t0 = i * CH, m = rows_of(i);
+        const int h = (int)(i & 1);
+        const double* o = c->l_out + h * 3 * PRED_ROWS;
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
+        HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+        HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+        if (lev) HIPCHK(c, hipMemcpyAsync(lev + t0, o + 2 * PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    const void* Bt = c->d_AbarT;
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const int h = (int)(i & 1);
+        const int64_t t0 = i * CH;
+        Geom g = g0;
+        g.N = rows_of(i); g.Np = round_up(g.N, 256);
+        if (resident) {
+            pack_data(g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->p_Xt, c->l_y, c->st);
+        } else {
+            HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
+            pack_data(g, raw + h * rawstride, raw + h * rawstride + PRED_ROWS * g0.D, nullptr, c->p_Xt, c->l_y, c->st,
+                      mode == 1 ? c->xs_mode : 0, c->d_xscale);
+            HIPCHK(c, hipEventRecord(fre[h], c->st));
+        }
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[h], 0));
+        double* o = c->l_out + h * 3 * PRED_ROWS;
+        rc = c->dtype == SCFGP_F32 ? Impl<float>::loo_chunk(c, g, (const float*)Bt, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS)
+                                   : Impl<double>::loo_chunk(c, g, (const double*)Bt, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS);
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(done[h], c->st));
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i >= 1 && (rc = download(i - 1))) return rc;
+    }
+    if ((rc = download(nchunks - 1))) return rc;
+    double acc[8]; unsigned long long bad[2];
+    HIPCHK(c, hipMemcpyAsync(acc, c->l_acc, sizeof(acc), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(bad, c->l_bad, sizeof(bad), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (bad[0]) { c->err = "loo: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
+    if (bad[1] != ~0ull) {
+        const long long j = (long long)bad[1];
+        c->err = "loo: I - H of block " + std::to_string(j) + " (rows " + std::to_string(j * block) + ".." +
+                 std::to_string(std::min<long long>((j + 1) * block, n) - 1) + ") is not positive definite: these rows are not in the fit";
+        return SCFGP_ENOTPD;
+    }
+    if (stats) {
+        stats[0] = (double)n; stats[1] = acc[0]; stats[2] = acc[1]; stats[3] = acc[2]; stats[4] = acc[3]; stats[5] = acc[4];
+        stats[6] = (double)((n + block - 1) / block); stats[7] = 0.0;
+    }
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // on-device optimiser and the captured training iteration
 // ----------------------------------------------------------------------------------------------
 extern "C" int scfgp_opt_init(scfgp_ctx* c, int algo, const double* hyper, int nhyper, double momentum) {
@@ -1897,6 +2048,7 @@ extern "C" int scfgp_get_dims(scfgp_ctx* c, int64_t* out, int n) {
     if (!c || !out || n < 6) return SCFGP_EARG;
     out[0] = c->g.K; out[1] = c->g.Kp; out[2] = c->g.Jp; out[3] = c->g.Dp; out[4] = c->g.Np; out[5] = c->g.P;
     if (n >= 7) out[6] = c->g.tile;
+    if (n >= 8) out[7] = c->have_data ? c->Nstore : 0;          // rows made resident by scfgp_set_data
     return SCFGP_OK;
 }
 

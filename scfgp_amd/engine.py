@@ -526,6 +526,52 @@ class HipEngine(object):
         self._check(rc, 'condition')
         return alpha_out, Li_out
 
+    LOO_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'sum_log_joint', 'max_leverage', 'blocks')
+
+    def loo(self, X=None, y=None, alpha=None, Li=None, block=1, mode='scaled'):
+        """Exact leave-block-out predictions of rows that are IN the fit (alpha, Li), without a refit (include/scfgp_hip.h: scfgp_loo):
+        (mu (n,1), std (n,), lev (n,), stats dict).  Row i's mu / std are what predict would return for it from the fit on all rows but
+        the `block` consecutive rows of its block ([j block, (j+1) block); block 1: leave-one-out); lev is the leverage h_i.  X=None and
+        y=None: the rows made resident by set_data.  mode 'scaled': X as predict takes it; 'raw': unscaled X through the registered X
+        scaler.  y (n,) or (n,1) is the SCALED target in either mode.  stats: LOO_STATS, sums over the call's rows with e = y - mu."""
+        if mode not in self.CONDITION_MODES:
+            raise ValueError('loo: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        if alpha is None or Li is None:
+            raise ValueError('loo: alpha and Li are needed')
+        if (X is None) != (y is None):
+            raise ValueError('loo: X and y go together (both None: the resident rows)')
+        m = self.CONDITION_MODES[mode]
+        alpha, Li = self._factors(alpha, Li)
+        if X is None:
+            d = (C.c_int64 * 8)()
+            self._check(self.lib.scfgp_get_dims(self.ctx, d, 8), 'get_dims')
+            n = int(d[7])                                   # the rows made resident by set_data (0: the library refuses)
+        else:
+            cols = getattr(self, '_xcols', None) if m else None
+            if m and cols is None:
+                raise ValueError('loo: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim != 2:
+                raise TypeError('X must be a 2-d float64 array')
+            if cols is not None:
+                X = X[:, cols]
+            X = np.ascontiguousarray(X)
+            if X.shape[1] != self.D:
+                raise ValueError('X has %d columns, expected %d' % (X.shape[1], self.D))
+            y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+            if y.size != X.shape[0]:
+                raise ValueError('y has %d entries for %d rows' % (y.size, X.shape[0]))
+            n = X.shape[0]
+        mu = np.empty((n, 1)); sd = np.empty(n); lev = np.empty(n); stats = np.zeros(8)
+        rc = self.lib.scfgp_loo(self.ctx, dptr(X), dptr(y), n, dptr(alpha), dptr(Li), m, int(block), dptr(mu), dptr(sd), dptr(lev),
+                                dptr(stats))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('loo: %s' % self.last_error())
+        self._check(rc, 'loo')
+        out = dict(zip(self.LOO_STATS, stats.tolist()))
+        out['n'] = int(out['n']); out['blocks'] = int(out['blocks'])
+        return mu, sd, lev, out
+
     def last_error(self):
         """Message of the last failure -- or refusal (a precision level whose buffers could not be had) -- on this context."""
         return self.lib.scfgp_last_error(self.ctx).decode()

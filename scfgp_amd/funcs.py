@@ -302,6 +302,20 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.condition(X_raw, y_scaled, alpha, Li, mode='raw')
 
+    def loo_raw(self, X_raw, y_scaled, x_scaler, alpha, Li, block=1):
+        """Leave-block-out predictions (mu, std, lev, stats) of the rows (X_raw, y_scaled), which must be rows of the fit (alpha, Li), at
+        the shared parameter vector: raw rows through the X scaler on the device, targets already scaled (engine.loo)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.loo(X_raw, y_scaled, alpha, Li, block=block, mode='raw')
+
+    def loo_func(self, X, y, alpha, Li, block=1):
+        """loo_raw for the scaled training set (X, y) train_func takes: it becomes (or stays) the resident data set and the device
+        reads the rows where they lie."""
+        self._sync_params()
+        self._sync_data(X, y)
+        return self.engine.loo(None, None, alpha, Li, block=block)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

@@ -301,6 +301,41 @@ class SCFGP(object):
         self.alpha, self.Li = owner.condition_raw(X, ys, self.X_scaler, self.alpha, self.Li)
         return self
 
+    def loo(self, X=None, y=None, block=1):
+        """Exact leave-block-out predictions of training rows, without a refit: (mu_y (n,1), std_y (n,1), metrics).  Row i is predicted
+        from the fit on all training rows except the `block` consecutive rows of its block (block=1: leave-one-out; 1..64; permute the
+        rows for other folds) at the current hyper-parameters and with the fitted scalers (include/scfgp_hip.h: scfgp_loo).  Without
+        arguments the rows are the model's own training set; raw (X, y) -- rows that ARE in the fit -- may be passed instead, which
+        is the only way for a model restored by load(), which holds no rows.  mu_y / std_y are in raw y units, through the y scaler
+        exactly as predict does it; metrics holds predict's six numbers (MAE, NMAE, MSE, NMSE, MNLP, SCORE) of the held-out
+        predictions against y, and 'LOO_LPD', the mean log predictive density of the scaled targets.  Neither self.evals nor
+        self.alpha / self.Li are touched."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('loo needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        if (X is None) != (y is None):
+            raise ValueError('loo: X and y go together (both None: the training set)')
+        if X is None:
+            if getattr(self, "X", None) is None or getattr(self, "y", None) is None:
+                raise ValueError('loo: the model holds no training rows (restored by load()?): pass the raw (X, y) of the fit')
+            mu_f, std_f, _, stats = owner.loo_func(self.X, self.y, self.alpha, self.Li, block=block)
+            ys = self.y_scaler.backward_transform(np.asarray(self.y, dtype=np.float64))
+        else:
+            ys = np.asarray(y, dtype=np.float64).reshape(-1, 1)
+            fy = np.asarray(self.y_scaler.forward_transform(ys), dtype=np.float64)
+            mu_f, std_f, _, stats = owner.loo_raw(X, fy, self.X_scaler, self.alpha, self.Li, block=block)
+        mu_y = self.y_scaler.backward_transform(mu_f)
+        up_bnd_y = self.y_scaler.backward_transform(mu_f + std_f[:, None])
+        dn_bnd_y = self.y_scaler.backward_transform(mu_f - std_f[:, None])
+        std_y = 0.5 * (up_bnd_y - dn_bnd_y)
+        err = mu_y - ys
+        mae, mse = np.mean(np.abs(err)), np.mean(err ** 2.)
+        mnlp = 0.5 * np.mean((err / std_y) ** 2 + np.log(2 * np.pi * std_y ** 2))
+        nmse = mse / np.var(ys)
+        metrics = {'MAE': mae, 'NMAE': mae / np.std(ys), 'MSE': mse, 'NMSE': nmse, 'MNLP': mnlp, 'SCORE': nmse / (1 + np.exp(-mnlp)),
+                   'LOO_LPD': stats['sum_log_marginal'] / stats['n']}
+        return mu_y, std_y, metrics
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
