@@ -239,6 +239,41 @@ int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t 
 int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode, int block,
               double* mu, double* std, double* lev, double* stats);
 
+/* ---- greedy maximum-information choice of m rows from a pool (no reference counterpart) ----------------------------------------------
+ * Which rows should be observed next?  The posterior of a Fourier-feature model is a Bayesian linear model in K weights, and the
+ * posterior variance after an observation does not depend on the observed value, so the exact greedy batch needs neither targets nor
+ * a refit per pick.  With Li of a fit, kappa = softplus(c), pool rows Xc (T x D), C = Phi_c Li^T (T x K) and d_i^(0) = |c_i|^2
+ * (scfgp_predict_cov's diagonal divided by kappa), step j = 0 .. m-1 does
+ *     p_j = argmax over the rows not yet taken with w_i > 0 of  w_i d_i^(j)                 (ties: the lowest index)
+ *     t   = c_p - sum_{l<j} u_l (u_l . c_p)        dp = c_p . t        u_j = t / sqrt(1 + dp)
+ *     d_i^(j+1) = max(d_i^(j) - (c_i . u_j)^2, 0)   for every i
+ * kappa d_i^(j) is the posterior variance of f(x_i) given noisy observations (noise variance kappa, as scfgp_predict) at p_0 .. p_{j-1}:
+ * (I + C_S^T C_S)^-1 = I - sum_l u_l u_l^T by Sherman-Morrison, one rank per pick.  sqrt(kappa (1 + d_i^(m))) is exactly what
+ * scfgp_predict returns as std after scfgp_condition has absorbed the picked rows, whatever their targets are, and
+ * sum_j log1p(dp_j) / 2 = log det(I + C_S C_S^T) / 2 is the information gain of the batch, of which the greedy choice is a (1 - 1/e)
+ * maximiser (submodularity).
+ * Xc (T x D): the pool; mode 0: scaled rows (as scfgp_predict), 1: column-selected raw rows through the registered X scaler (as
+ * scfgp_predict_raw).  w (T, may be NULL = ones): non-negative weights of the criterion; w_i = 0 excludes row i from being picked (its
+ * std_after is still reported).  Li as scfgp_eval returns it (entries above the diagonal are not read); alpha is not needed.  Points that
+ * are pending (chosen, not yet observed) are handled by conditioning on them first with ANY targets (scfgp_condition): only Li' is used.
+ * Outputs: idx (m): the picks in order, indices into the pool; var (m, may be NULL): kappa dp_j, the posterior variance of f at pick j
+ * when it was picked; gain (m, may be NULL): log1p(dp_j) / 2; std_after (T, may be NULL): sqrt(kappa (1 + d_i^(m))) of every pool row.
+ * Bounds: 1 <= m <= min(4096, number of rows with w_i > 0), 1 <= T <= 2^20, K <= 8192 (u_j is held in LDS).  The call owns a T x Kp
+ * buffer of C in the context's type for its duration (a failed allocation is SCFGP_EHIP with the size in the message) and m x Kp
+ * doubles of the u_l; nothing stays resident between calls.
+ * Guarantees: the picks of a call with m1 < m2 are a prefix of those with m2, bit for bit, in idx, var and gain (step j does the same
+ * arithmetic whatever m is).  A row's c_i . u has one summation order whatever T is and wherever the row sits, so appending rows with
+ * w = 0 changes nothing and std_after of the original rows keeps its bits.  C runs in the context's precision (SCFGP_F16X3 contexts run
+ * fp32 mode's kernels and agree with it bit for bit); d, t, dp, u and every sum over k are fp64, C is converted on load.  No step
+ * returns to the host: m picks are eager launches on the context's stream, fetched once at the end.  The training state of the context
+ * survives (resident rows, exchange buffers, optimiser state, precision level).
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL pointers, a bad m, T or mode, a missing X scaler in mode 1,
+ * parameters not set, a negative weight, or fewer than m rows with a positive weight; SCFGP_ENONFINITE for non-finite rows, weights or
+ * factors: the outputs are untouched in both cases.  Out of scope: integrated-variance criteria (ALC / A-optimal), a row-sharded pool,
+ * raw-y units (the criterion is in scaled-y units), and factors kept on the device between calls. */
+int scfgp_select(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Li, int m, int mode, int64_t* idx,
+                 double* var, double* gain, double* std_after);
+
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded
  * over ranks each sweep ends in one sum over ranks.  The host framework (torch.distributed

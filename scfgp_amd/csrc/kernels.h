@@ -315,3 +315,23 @@ void update_accumulate(double* acc, const double* part, int64_t n, hipStream_t s
 template <typename T>
 void loo_blocks(const Geom& g, const T* C, const double* r, const double* y, int block, int64_t blk0, const Scal* sc, double* mu,
                 double* sd, double* lev, double* rec, double* acc, unsigned long long* bad, hipStream_t st);
+
+// ---- select.hip: greedy maximum-information choice of m rows from a pool (scfgp_select) ---------------------------------------------
+// C (typed, ld Kp, Trows rows) = Phi_c Li^T of the pool.  Device state of one call: w (Trows: the weights; a picked row's is set to 0),
+// d (Trows: the running |c_i|^2 downdated by every pick), pval / pidx (select_partials(Trows) argmax partials of the last sweep), U
+// (m x Kp: the u_l), cp (Kp: the picked row in fp64), a (m: u_l . c_p), part (ceil(m / 64) x Kp: chunk sums of the projection), idx /
+// var / gain (m each), flag (bit 0: a non-finite |c_i|^2, bit 1: a step found no eligible row).
+struct SelectBufs {
+    int Kp; int64_t Trows;
+    double *w, *d, *pval; long long* pidx;
+    double *U, *cp, *a, *part;
+    long long* idx; double *var, *gain; int* flag;
+};
+int select_partials(int64_t Trows);
+void select_ones(double* w, int64_t Trows, hipStream_t st);
+// d = rowsum(C^2) and the first argmax partials
+template <typename T> void select_init(const SelectBufs& b, const T* C, hipStream_t st);
+// pick j: idx[j], var[j] = kappa dp, gain[j] = log1p(dp) / 2, u_j into U, then the sweep that downdates d and leaves the next partials
+template <typename T> void select_step(const SelectBufs& b, const T* C, int j, const Scal* sc, hipStream_t st);
+// sd[i] = sqrt(kappa (1 + d[i]))
+void select_std(const SelectBufs& b, const Scal* sc, double* sd, hipStream_t st);

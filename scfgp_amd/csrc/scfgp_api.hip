@@ -1814,6 +1814,155 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
 }
 
 // ----------------------------------------------------------------------------------------------
+// greedy maximum-information choice of m rows from a pool (select.hip; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int SELECT_MAX_M = 4096;
+static constexpr int64_t SELECT_MAX_T = (int64_t)1 << 20;
+static constexpr int SELECT_MAX_KP = 8192;                        // u_j lives in LDS as fp64: 64 KB
+// A sibling of scfgp_predict_cov: the same double-buffered upload, pack_data (X scaler in mode 1), feature map and C = Phi_c Li^T per
+// chunk of PRED_ROWS rows -- each chunk's C written to its place in a T x Kp buffer that this call owns.  Then d = rowsum(C^2) and
+// m picks, every one of them a handful of eager launches on the context's stream (select.hip); the host waits once before the picks
+// (for the non-finite flag of d) and once after them.  idx / var / gain are fetched at the end, std_after leaves on the copy stream.
+extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Li, int m, int mode, int64_t* idx,
+                            double* var, double* gain, double* std_after) {
+    if (!c) return SCFGP_EARG;
+    if (!Xc || !Li || !idx || mode < 0 || mode > 1) { c->err = "select: bad arguments"; return SCFGP_EARG; }
+    if (T < 1 || T > SELECT_MAX_T) { c->err = "select: T must lie in 1..1048576"; return SCFGP_EARG; }
+    if (m < 1 || m > SELECT_MAX_M) { c->err = "select: m must lie in 1..4096"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "select: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "select: parameters not set"; return SCFGP_EARG; }
+    if (c->g.Kp > SELECT_MAX_KP) { c->err = "select: K above 8192 is not supported"; return SCFGP_EARG; }
+    int64_t eligible = T;
+    if (w) {
+        bool nonfinite = false;
+        eligible = 0;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "select: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) ++eligible;
+        }
+        if (nonfinite) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    }
+    if (m > eligible) {
+        c->err = "select: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
+        return SCFGP_EARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp;
+    const size_t ts = c->tsize();
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    // the last chunk's product writes whole 256-row blocks
+    const int64_t Crows = (nchunks - 1) * PRED_ROWS + round_up(T - (nchunks - 1) * PRED_ROWS, 256);
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    DevTmp raw, Cbuf, rows, picks;                                // Li / two chunks of X | C | w, d, std, partials | U, cp, a, part, idx, var, gain, flag
+    const int64_t rawstride = PRED_ROWS * g0.D;
+    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = "select: no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
+                 std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)";
+        return SCFGP_EHIP;
+    }
+    const int npart = select_partials(T), nlchunk = (m + 63) / 64;
+    const int64_t npp = round_up(npart, 8), mp = round_up(m, 8);
+    if ((rc = dmalloc(c, &rows.p, sizeof(double) * (3 * T + 2 * npp)))) return rc;
+    if ((rc = dmalloc(c, &picks.p, sizeof(double) * ((int64_t)m * Kp + Kp + (int64_t)nlchunk * Kp + 4 * mp + 8)))) return rc;
+    SelectBufs b;
+    b.Kp = (int)Kp; b.Trows = T;
+    b.w = rows; b.d = rows + T; double* d_sd = rows + 2 * T; b.pval = rows + 3 * T; b.pidx = (long long*)(rows + 3 * T + npp);
+    b.U = picks; b.cp = b.U + (int64_t)m * Kp; b.part = b.cp + Kp; b.a = b.part + (int64_t)nlchunk * Kp;
+    b.idx = (long long*)(b.a + mp); b.var = b.a + 2 * mp; b.gain = b.a + 3 * mp; b.flag = (int*)(b.a + 4 * mp);
+    HIPCHK(c, hipMemsetAsync(Cbuf.p, 0, ts * Crows * Kp, c->st));   // the product leaves the padding columns K.. as they are: zero
+    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
+    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
+    else select_ones(b.w, T, c->st);
+    // Li -> T1 (lower triangle only, identity padding: update_load_factor, so that entries above the diagonal are never read) -> the
+    // typed Li^T (AbarT: scratch outside adjoint..pass3) and Li, as scfgp_predict_cov prepares them
+    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
+    update_load_factor(raw, g0.K, g0.Kp, c->d_T1, c->st);
+    if (c->dtype == SCFGP_F32) {
+        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
+    } else {
+        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
+        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    struct Events {
+        hipEvent_t up[2] = {nullptr, nullptr}, fre[2] = {nullptr, nullptr}, done = nullptr;
+        ~Events() {
+            for (int i = 0; i < 2; ++i) { if (up[i]) (void)hipEventDestroy(up[i]); if (fre[i]) (void)hipEventDestroy(fre[i]); }
+            if (done) (void)hipEventDestroy(done);
+        }
+    } ev;
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(c, hipEventCreateWithFlags(&ev.up[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&ev.fre[i], hipEventDisableTiming));
+    }
+    HIPCHK(c, hipEventCreateWithFlags(&ev.done, hipEventDisableTiming));
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) -> int {
+        const int h = (int)(i & 1);
+        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.fre[h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xc + i * PRED_ROWS * g0.D, sizeof(double) * rows_of(i) * g0.D, hipMemcpyHostToDevice,
+                                 c->copy_st));
+        HIPCHK(c, hipEventRecord(ev.up[h], c->copy_st));
+        return SCFGP_OK;
+    };
+    const void* Bt = c->d_AbarT;
+    char* Call = (char*)Cbuf.p;
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const int h = (int)(i & 1);
+        Geom g = g0;
+        g.N = rows_of(i); g.Np = round_up(g.N, 256);
+        HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
+        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
+        void* Ci = Call + ts * (size_t)(i * PRED_ROWS) * Kp;
+        rc = c->dtype == SCFGP_F32 ? Impl<float>::cov_factor_chunk(c, g, (const float*)Bt, (float*)Ci)
+                                   : Impl<double>::cov_factor_chunk(c, g, (const double*)Bt, (double*)Ci);
+        if (rc) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    const bool f32 = c->dtype == SCFGP_F32;
+    if (f32) select_init<float>(b, (const float*)Cbuf.p, c->st);
+    else select_init<double>(b, (const double*)Cbuf.p, c->st);
+    HIPCHK(c, hipGetLastError());
+    int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    for (int j = 0; j < m; ++j) {
+        if (f32) select_step<float>(b, (const float*)Cbuf.p, j, c->d_sc, c->st);
+        else select_step<double>(b, (const double*)Cbuf.p, j, c->d_sc, c->st);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (std_after) {
+        select_std(b, c->d_sc, d_sd, c->st);
+        HIPCHK(c, hipEventRecord(ev.done, c->st));
+    }
+    HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    if (std_after) {
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.done, 0));
+        HIPCHK(c, hipMemcpyAsync(std_after, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->copy_st));
+    }
+    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
+    if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    if (gain) HIPCHK(c, hipMemcpyAsync(gain, b.gain, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // on-device optimiser and the captured training iteration
 // ----------------------------------------------------------------------------------------------
 extern "C" int scfgp_opt_init(scfgp_ctx* c, int algo, const double* hyper, int nhyper, double momentum) {

@@ -572,6 +572,43 @@ class HipEngine(object):
         out['n'] = int(out['n']); out['blocks'] = int(out['blocks'])
         return mu, sd, lev, out
 
+    def select(self, Xc, Li, m, w=None, raw=False, return_std=False):
+        """Greedy maximum-information choice of m rows from the pool Xc (include/scfgp_hip.h: scfgp_select): (idx (m,) int64, var (m,),
+        gain (m,)) and, with return_std, std_after (T,).  idx: the picks in order, indices into Xc; var[j]: the posterior variance of f
+        at pick j when it was picked (scaled-y units, noise excluded); gain[j]: its information gain log1p(var / kappa) / 2;
+        std_after: what predict reports as std at every pool row once the picks have been observed (condition), whatever their
+        targets.  w (T,): non-negative weights of the criterion, 0 excludes a row.  raw: unscaled Xc through the registered X scaler,
+        as predict_raw.  Only Li is needed; condition on pending points first, with any targets."""
+        cols = getattr(self, '_xcols', None) if raw else None
+        if raw and cols is None:
+            raise ValueError('select: raw rows need a registered X scaler (set_x_scaler)')
+        Xc = np.asarray(Xc, dtype=np.float64)
+        if Xc.ndim != 2:
+            raise TypeError('Xc must be a 2-d float64 array')
+        if cols is not None:
+            Xc = Xc[:, cols]
+        Xc = np.ascontiguousarray(Xc)
+        if Xc.shape[1] != self.D:
+            raise ValueError('Xc has %d columns, expected %d' % (Xc.shape[1], self.D))
+        T = Xc.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if Li.shape != (self.K, self.K):
+            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        m = int(m)
+        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
+        idx = np.empty(n, dtype=np.int64); var = np.empty(n); gain = np.empty(n)
+        sd = np.empty(T) if return_std else None
+        rc = self.lib.scfgp_select(self.ctx, dptr(Xc), T, dptr(w), dptr(Li), m, int(bool(raw)), idx.ctypes.data_as(_lib._c_i64_p),
+                                   dptr(var), dptr(gain), dptr(sd))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('select: %s' % self.last_error())
+        self._check(rc, 'select')
+        return (idx, var, gain, sd) if return_std else (idx, var, gain)
+
     def last_error(self):
         """Message of the last failure -- or refusal (a precision level whose buffers could not be had) -- on this context."""
         return self.lib.scfgp_last_error(self.ctx).decode()

@@ -316,6 +316,13 @@ class CompiledFuncs(object):
         self._sync_data(X, y)
         return self.engine.loo(None, None, alpha, Li, block=block)
 
+    def select_raw(self, X_raw, x_scaler, Li, m, weights=None, return_std=False):
+        """Greedy maximum-information choice of m of the raw pool rows X_raw under the posterior with factor Li, at the shared parameter
+        vector: (idx, var, gain[, std_after]) in scaled-y units, raw rows through the X scaler on the device (engine.select)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.select(X_raw, Li, m, w=weights, raw=True, return_std=return_std)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

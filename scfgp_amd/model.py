@@ -336,6 +336,20 @@ class SCFGP(object):
                    'LOO_LPD': stats['sum_log_marginal'] / stats['n']}
         return mu_y, std_y, metrics
 
+    def select(self, X_pool, m, weights=None):
+        """Which m rows of the raw pool X_pool (T,D) to observe next: (idx (m,) indices into the pool in the order they are picked,
+        std (m,), gain (m,)).  Pick j is the row whose function value is most uncertain (times its weight) given the training set and
+        the picks before it -- the exact greedy maximiser of the batch's information gain, without targets and without a refit per
+        pick (include/scfgp_hip.h: scfgp_select).  std[j] is the posterior std of f at pick j when it was picked, in scaled-y units
+        (noise excluded); gain[j] its information gain in nats.  weights (T,) >= 0 scale the criterion, 0 excludes a row.  Points that
+        are pending (chosen but not yet observed) are handled by condition(X_pending, any y) on a copy of the model first: the
+        choice depends on Li alone.  The library's message is raised on error.  Nothing of the model is touched."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('select needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        idx, var, gain = owner.select_raw(X_pool, self.X_scaler, self.Li, m, weights=weights)
+        return idx, np.sqrt(var), gain
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
