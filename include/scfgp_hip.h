@@ -96,7 +96,10 @@ int scfgp_set_data(scfgp_ctx* ctx, const double* X, const double* y, int64_t N, 
  * want_grad=0 is train_func (forward only); want_grad=1 additionally returns
  * d cost / d params (P) -- what TT.grad (SCFGP/SCFGP.py:129) feeds the update rule.
  * Outputs (any may be NULL): cost (1), grad (P), alpha (K), Li (K*K row-major, lower
- * triangular, zeros above the diagonal). */
+ * triangular, zeros above the diagonal).
+ * Range of the phases, here and in every entry point that evaluates the feature map (predict, predict_grad, predict_cov, sample,
+ * condition, loo, select): sin / cos are good to the last bit or so for |z| < 2^31 pi/2 = 3.37e9 rad in both modes; beyond that
+ * (unscaled X, parameters blown up by a large step) Phi is finite, of the right magnitude and in the wrong quadrant, silently. */
 int scfgp_eval(scfgp_ctx* ctx, const double* X, const double* y, int64_t N, int want_grad,
                double* cost, double* grad, double* alpha, double* Li);
 
@@ -396,7 +399,8 @@ int scfgp_get_dims(scfgp_ctx* ctx, int64_t* out, int n);
 int scfgp_set_profiling(scfgp_ctx* ctx, int enable);
 int scfgp_get_timings(scfgp_ctx* ctx, double* ms, const char** names, int n);
 /* copy an internal device buffer to the host for tests ("Phi","V","G","W","XZ","Li","B","Abar",
- * "p","q","vecs","Fall","Xt","scalars"); returns the number of bytes copied or <0.  "G" is exchange buffer 1 unpacked
+ * "p","q","vecs","Fall","Lall","Rall","Xt","Tt","scalars"); returns the number of bytes copied or <0.  "Lall" (Dp x round_up(Sp,64))
+ * and "Rall" (Sp x Jp) are the factors of the rank-S projection, defined only where it runs (Sp < Dp).  "G" is exchange buffer 1 unpacked
  * (the summed Gram, Phi^T y, y^T y and the status word) at any stage; "W" is exchange buffer 2 as the adjoint stage left it.
  * Compute mode SCFGP_F16X3 only (elsewhere an error with a message): "Phi16", "V16g", "qV16g" the Np x Kp plane-form arrays of
  * Phi, V and diag(q) V (4 bytes per element, per 16 columns 16 fp16 h's then 16 l's; without the padding behind them); "B16"

@@ -2320,6 +2320,8 @@ extern "C" int64_t scfgp_debug_read(scfgp_ctx* c, const char* name, void* host, 
     else if (s == "q") { src = c->d_q; bytes = 8 * g.Np; }
     else if (s == "vecs") { src = c->d_vecs; bytes = 8 * 5 * g.Kp; }
     else if (s == "Fall") { src = c->d_Fall; bytes = 8 * (int64_t)g.Dp * g.Jp; }
+    else if (s == "Lall") { src = c->d_Lall; bytes = 8 * (int64_t)g.Dp * round_up(g.Sp, 64); }   // factors of the rank-S form; written
+    else if (s == "Rall") { src = c->d_Rall; bytes = 8 * (int64_t)g.Sp * g.Jp; }                  // only where it is used (Sp < Dp)
     else if (s == "Xt") { src = c->d_Xt; bytes = 8 * g.Np * g.Dp; }
     else if (s == "scalars") { src = c->d_scalars; bytes = 8 * 32; }
     else if (s == "C") {                                         // factor form: C = Phi Li^T of the last pass 2 at level 2

@@ -3,10 +3,14 @@
 #include "common.h"
 
 // --------------------------------------------------------------------------
-// sin/cos for |z| up to ~1e5 rad: two-term Cody-Waite reduction by pi/2 in fp64 (fdlibm's
-// medium-argument constants: exact n*pio2_1 for |n| < 2^20) and fdlibm's kernel polynomials on
-// [-pi/4, pi/4] (< 1 ulp).  Branch-free; the library sincos carries a Payne-Hanek path the
-// phases of this model never need (|FF| is tens to hundreds of radians).
+// sin/cos for |fn| = |rint(z 2/pi)| < 2^31, |z| < 3.37e9 rad: two-term Cody-Waite reduction by pi/2 in fp64 (fdlibm's
+// medium-argument constants) and fdlibm's kernel polynomials on [-pi/4, pi/4].  The first step is a fused operation and
+// z - fn*pio2_1 is a multiple of 2^-32 below 2 in magnitude, so it is exact at every such fn, not only for |fn| < 2^20 where
+// the product alone fits a double; what ends the domain is (int)fn, which no longer holds fn from 2^31 on: the values stay
+// finite and inside the unit circle but carry the wrong quadrant.  Absolute error against mpmath, emulation and kernels alike
+// (tests/test_sincos_ref.py, tests/test_gpu_phase_range.py): <= 0.77 * 2^-53 over the hard cases up to |fn| = 2^20 (multiples of
+// pi/2, quadrant flips, ties of rint) and no larger out to |z| = 1e9.  Branch-free; the library sincos carries a Payne-Hanek
+// path the phases of this model never need (|FF| is tens to hundreds of radians).
 // --------------------------------------------------------------------------
 __device__ __forceinline__ void fast_sincos(double z, double& sn, double& cs) {
     const double fn = rint(z * 6.36619772367581382433e-01);              // 2/pi
@@ -36,7 +40,8 @@ __device__ __forceinline__ void fast_sincos(double z, double& sn, double& cs) {
 
 // fp32 outputs: the same fp64 reduction (the phase itself needs it: |z| ~ 1e2 rad at 2^-24 would already be
 // 1e-5), then the reduced argument in fp32 with the cephes sinf / cosf kernel polynomials on [-pi/4, pi/4]
-// (~1 ulp of fp32, the precision Phi is stored in): a third of the VALU work of the fp64 kernels.
+// (the precision Phi is stored in; absolute error <= 1.6 * 2^-24 measured over the same domain, |z| up to 1e9): a third of the
+// VALU work of the fp64 kernels.
 __device__ __forceinline__ void fast_sincos(double z, float& sn, float& cs) {
     const double fn = rint(z * 6.36619772367581382433e-01);
     const double r = fma(-fn, 6.07710050650619224932e-11, fma(-fn, 1.57079632673412561417e+00, z));
