@@ -700,43 +700,64 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    static int predict_chunk(scfgp_ctx* c, const Geom& g, const T* Bt, double* mu, double* sd) {
+    // ---- chunk bodies of the posterior entry points (the pipeline that feeds them is described at RowFeed below) ----
+    // typed operands arrive as void*: both arms of DISPATCH get the same arguments
+    // Phi of the chunk's packed rows (p_Xt -> p_Phi)
+    static void features(scfgp_ctx* c, const Geom& g) {
         SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-        SK::apply_predict(g, (const T*)c->p_Phi, Bt, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);           // Bt = Li^T
+    }
+    // C = Phi Li^T by pass 2's level-2 product (loader-staged tiles); its by-products land in the chunk's partials: vpart (slices of
+    // rowsum(C^2)) and mupart (slices of Phi avec)
+    static void factor_c(scfgp_ctx* c, const Geom& g, const T* LiT, const double* avec, T* C) {
+        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, C, c->p_vpart, avec, avec, c->p_mupart, c->st, 0);
+    }
+    // typed copies of a padded fp64 factor: its transpose into LiT and / or the factor itself into Li (either may be NULL)
+    static void type_factor(scfgp_ctx* c, const double* L64, void* LiT, void* Li) {
+        if (LiT) SK::convert_transposed(L64, (T*)LiT, c->g.K, c->g.Kp, c->st);
+        if (Li) SK::convert(L64, (T*)Li, c->g.K, c->g.Kp, c->st);
+    }
+    static int predict_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, double* mu, double* sd) {
+        features(c, g);
+        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
         SK::rowpredict(g, c->p_mupart, c->p_vpart, c->d_sc, mu, sd, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // FT = F_all^T in the context's type, the operand of predict_grad_chunk (once per call)
+    static void grad_operand(scfgp_ctx* c) { predgrad_operand(c->g, c->d_Fall, (T*)c->p_FT, c->st); }
     // after predict_chunk: d mu / d x~ and (dstd != NULL) d sigma / d x~ of the chunk's rows (predgrad.hip).  V* = Phi* B in the factor
-    // form C = Phi* Li^T, V = C Li (pass 2's level-2 products, loader-staged tiles): its rounding errors grow with sqrt(cond(A)) where
-    // those of V = Phi* B formed directly grow with cond(A).  The by-products vpart / mupart of apply_c land in the chunk's partials,
-    // which rowpredict has consumed.
-    static int predict_grad_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, const double* sd, double* dmu, double* dstd) {
+    // form C = Phi* Li^T, V = C Li: its rounding errors grow with sqrt(cond(A)) where those of V = Phi* B formed directly grow with
+    // cond(A).  factor_c's by-products land in the chunk's partials, which rowpredict has consumed.
+    static int predict_grad_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const double* sd, double* dmu, double* dstd) {
         if (dstd) {
-            SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart,
-                        c->st, 0);
-            SK::apply_vc(g, (const T*)c->p_C, (const T*)c->p_Li, LiT, (T*)c->p_V, c->st, 0);
+            factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
+            SK::apply_vc(g, (const T*)c->p_C, (const T*)c->p_Li, (const T*)LiT, (T*)c->p_V, c->st, 0);
         }
         predgrad<T>(g, (const T*)c->p_Phi, (const T*)c->p_V, c->alpha_pred(), (const T*)c->p_FT, sd, c->d_sc, dmu, dstd, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    // scfgp_predict_cov: the chunk's Phi* as predict_chunk forms it, then C = Phi* Li^T as predict_grad_chunk does (vpart / mupart land
-    // in the chunk's partials and are ignored)
-    static int cov_factor_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, T* C) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart, c->st, 0);
+    // scfgp_predict_cov, scfgp_select: C = Phi* Li^T of the chunk's rows (the by-products are ignored)
+    static int cov_factor_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, void* C) {
+        features(c, g);
+        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)C);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    // scfgp_condition: C = Phi_n Li^T of the chunk's rows as cov_factor_chunk forms it (mupart = slices of Phi_n alpha), the residual
-    // r = y - Phi_n alpha, then [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the
-    // chunk's geometry with the update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows
-    // (never the fp16 split: an f16x3 context runs fp32 mode's kernels here)
+    static void cov_panel(scfgp_ctx* c, const void* Ca, const void* Cb, int64_t nrows, int64_t Tb, int64_t row_base, int noise, double* out) {
+        predcov<T>(c->g, (const T*)Ca, (const T*)Cb, nrows, Tb, row_base, noise, c->d_sc, out, c->st);
+    }
+    static void pick_init(scfgp_ctx* c, const SelectBufs& b, const void* C) { select_init<T>(b, (const T*)C, c->st); }
+    static void pick(scfgp_ctx* c, const SelectBufs& b, const void* C, int j) { select_step<T>(b, (const T*)C, j, c->d_sc, c->st); }
+    // workgroups per row split of the Gram launch on the context's geometry (update_splits)
+    static int gram_jobs(const scfgp_ctx* c) { return SK::gram_jobs(c->g); }
+    // scfgp_condition: C = Phi_n Li^T with the update's own factor and alpha (u_LiT, u_vec), the residual r = y - Phi_n alpha, then
+    // [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the chunk's geometry with the
+    // update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows (never the fp16 split: an
+    // f16x3 context runs fp32 mode's kernels here)
     static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, double* out) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-        SK::apply_c(g, (const T*)c->p_Phi, (const T*)c->u_LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->u_vec, c->u_vec, c->p_mupart,
-                    c->st, 0);
+        features(c, g);
+        factor_c(c, g, (const T*)c->u_LiT, c->u_vec, (T*)c->p_C);
         SK::rowresidual(g, c->p_mupart, c->u_y, c->u_r, c->st);
         const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
         double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
@@ -746,22 +767,24 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    // scfgp_loo: C = Phi_I Li^T and r = y - Phi_I alpha of the chunk's rows as update_chunk forms them, then the block kernel and the
-    // ordered sum of its records (loo.hip)
-    static int loo_chunk(scfgp_ctx* c, const Geom& g, const T* LiT, int block, int64_t blk0, double* mu, double* sd, double* lev) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(), c->p_mupart,
-                    c->st, 0);
+    // scfgp_loo: C = Phi_I Li^T and r = y - Phi_I alpha of the chunk's rows, then the block kernel and the ordered sum of its records
+    // (loo.hip)
+    static int loo_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int block, int64_t blk0, double* mu, double* sd, double* lev) {
+        features(c, g);
+        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
         SK::rowresidual(g, c->p_mupart, c->l_y, c->l_r, c->st);
         loo_blocks<T>(g, (const T*)c->p_C, c->l_r, c->l_y, block, blk0, c->d_sc, mu, sd, lev, c->l_rec, c->l_acc, c->l_bad, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    // scfgp_sample: the chunk's Phi* as predict_chunk forms it, then out (N x nsamp) = Phi* W and the epilogue (sample.hip)
-    static int sample_chunk(scfgp_ctx* c, const Geom& g, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode,
+    // scfgp_sample: the weights of the sample functions (sample.hip), then per chunk out (N x nsamp) = Phi* W and the epilogue
+    static void weights(scfgp_ctx* c, const double* Li, const double* alpha, int nsamp, uint64_t seed, double* Z, double* W, void* Wt) {
+        sample_weights<T>(c->g, Li, alpha, c->d_sc, nsamp, seed, Z, W, (T*)Wt, c->st);
+    }
+    static int sample_chunk(scfgp_ctx* c, const Geom& g, const void* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode,
                             double* out) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-        sample_product<T>(g, (const T*)c->p_Phi, Wt, nsamp, t0, seed, noise, ymode, c->d_yscale, c->d_sc, out, c->st);
+        features(c, g);
+        sample_product<T>(g, (const T*)c->p_Phi, (const T*)Wt, nsamp, t0, seed, noise, ymode, c->d_yscale, c->d_sc, out, c->st);
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
@@ -1150,9 +1173,110 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
     return SCFGP_OK;
 }
 
+// ----------------------------------------------------------------------------------------------
+// the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_predict_cov, scfgp_condition, scfgp_loo
+// and scfgp_select
+// ----------------------------------------------------------------------------------------------
+// Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
+// the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
+// RowFeed owns the two halves that the uploads alternate between and the events that order a half between the streams: up (the rows
+// are there: st waits before pack_data reads them) and fre (they have been read: the copy stream waits before job i + 2 overwrites
+// them).  The caller places release(): right after pack_data, or after the last kernel that still reads the raw rows.
+// Results that do not stay on the device leave through two staging slots of the caller, ordered by an OutRing: done (slot k is
+// computed: the copy stream waits before it copies the slot out) and copied (st waits before slot k + 2 overwrites it).  Each loop
+// enqueues in the order "compute slot k, upload job k + 1, drain slot k - 1" and drains the last slot behind the loop: the host's
+// blocking copies in both directions fall under the next chunk's kernels, and device memory does not grow with the row count.
+// The waits for reuse run from the third job or slot on.
+template <int N> struct Events {                                  // call-scoped events: released on every return path
+    hipEvent_t e[N] = {};
+    int create(scfgp_ctx* c) {
+        for (hipEvent_t& x : e) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+        return SCFGP_OK;
+    }
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+struct RowFeed {
+    scfgp_ctx* c = nullptr;
+    DevTmp raw;                                                   // two halves of `stride` doubles: rows (n x D), targets at PRED_ROWS * D
+    int64_t stride = 0;
+    Events<4> ev;                                                 // up[2] | fre[2]
+    // also_holds: what else the buffer is used for (the host layout of Li, before the first job); stride 0: no rows will be fed
+    int open(scfgp_ctx* c_, int64_t stride_, int64_t also_holds = 0) {
+        c = c_; stride = stride_;
+        if (int rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>(also_holds, 2 * stride))) return rc;
+        return ev.create(c);
+    }
+    int upload(int64_t job, const double* X, const double* y, int64_t rows) {
+        const int h = (int)(job & 1);
+        if (job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[2 + h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * stride, X, sizeof(double) * rows * c->g.D, hipMemcpyHostToDevice, c->copy_st));
+        if (y) HIPCHK(c, hipMemcpyAsync(raw + h * stride + PRED_ROWS * c->g.D, y, sizeof(double) * rows, hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
+        return SCFGP_OK;
+    }
+    int acquire(int64_t job, const double** x, const double** y = nullptr) {
+        const int h = (int)(job & 1);
+        HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[h], 0));
+        *x = raw + h * stride;
+        if (y) *y = raw + h * stride + PRED_ROWS * c->g.D;
+        return SCFGP_OK;
+    }
+    int release(int64_t job) {
+        HIPCHK(c, hipEventRecord(ev.e[2 + (int)(job & 1)], c->st));
+        return SCFGP_OK;
+    }
+};
+struct OutRing {
+    scfgp_ctx* c = nullptr;
+    Events<4> ev;                                                 // done[2] | copied[2]
+    int open(scfgp_ctx* c_) { c = c_; return ev.create(c); }
+    int acquire(int64_t k) {
+        if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[2 + (int)(k & 1)], 0));
+        return SCFGP_OK;
+    }
+    int computed(int64_t k) {
+        HIPCHK(c, hipEventRecord(ev.e[(int)(k & 1)], c->st));
+        return SCFGP_OK;
+    }
+    // copies: the caller's hipMemcpyAsync calls on the copy stream (pageable: the host waits in them while the next slot computes)
+    template <typename F> int drain(int64_t k, F copies) {
+        const int h = (int)(k & 1);
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[h], 0));
+        if (int rc = copies()) return rc;
+        HIPCHK(c, hipEventRecord(ev.e[2 + h], c->copy_st));
+        return SCFGP_OK;
+    }
+};
+static Geom chunk_geom(const Geom& g0, int64_t rows) {
+    Geom g = g0;
+    g.N = rows; g.Np = round_up(rows, 256);
+    return g;
+}
+// The factor pass.  Li (K x K, host) -> raw -> L64 (Kp x Kp fp64) by `pad` (pad_square: identity padding; update_load_factor: the
+// lower triangle only, so that entries above the diagonal are never read) -> the typed Li^T into LiT and, Li_typed != NULL, the typed
+// Li.  alpha != NULL: zero-padded into avec.  finite != NULL: scfgp_condition's checks of what was loaded.  raw may be reused once the
+// stream has been synchronised.
+typedef void (*PadFn)(const double*, int, int, double*, hipStream_t);
+static int load_factor(scfgp_ctx* c, double* raw, const double* Li, PadFn pad, double* L64, void* LiT, void* Li_typed,
+                       const double* alpha = nullptr, double* avec = nullptr, int* finite = nullptr) {
+    const Geom& g = c->g;
+    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g.K * g.K, hipMemcpyHostToDevice, c->st));
+    pad(raw, g.K, g.Kp, L64, c->st);
+    if (alpha) {
+        HIPCHK(c, hipMemsetAsync(avec, 0, sizeof(double) * g.Kp, c->st));
+        HIPCHK(c, hipMemcpyAsync(avec, alpha, sizeof(double) * g.K, hipMemcpyHostToDevice, c->st));
+    }
+    if (finite) {
+        update_check_finite(L64, (int64_t)g.Kp * g.Kp, finite, c->st);
+        update_check_finite(avec, g.Kp, finite, c->st);
+    }
+    DISPATCH(c, type_factor, c, L64, LiT, Li_typed);
+    return SCFGP_OK;
+}
+
 // raw_mode: apply the registered X scaler while packing; post: y-scaler backward transform of the outputs on
 // the device and, with targets ys, the six validation metrics; dmu != NULL: also the gradients of mu (and, dstd != NULL, of std) in
-// the inputs, T x D each (scfgp_predict_grad)
+// the inputs, T x D each (scfgp_predict_grad).  mu and sd of all T rows stay on the device until the end.
 static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
                         double* mu, double* sd, int raw_mode, int post = 0, const double* ys = nullptr,
                         double* metrics = nullptr, double* dmu = nullptr, double* dstd = nullptr) {
@@ -1160,35 +1284,22 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     if (!c->have_params) { c->err = "predict: parameters not set"; return SCFGP_EARG; }
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
     int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     const bool grad = dmu != nullptr;
     if (grad && (rc = ensure_pred_grad(c, dstd != nullptr))) return rc;
-    // Li (K x K host) -> T1 (Kp x Kp, identity padding); typed transposed copy -> AbarT scratch
-    DevTmp raw, d_out, d_ys, d_part;                              // Li / two chunks of Xs | mu, sd of all T rows | targets, mean, metrics | chunk partials
-    const int64_t rawstride = PRED_ROWS * g0.D;
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    RowFeed feed; DevTmp d_out, d_ys, d_part;                     // Li / two chunks of Xs | mu, sd of all T rows | targets, mean, metrics | chunk partials
+    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
     if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 2 * T))) return rc;
     double* d_mu = d_out; double* d_sd = d_out + T;
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
-    pad_square(raw, g0.K, g0.Kp, c->d_T1, c->st);
-    HIPCHK(c, hipMemsetAsync(c->alpha_pred(), 0, sizeof(double) * Kp, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->alpha_pred(), alpha, sizeof(double) * g0.K, hipMemcpyHostToDevice, c->st));
     // the sweep operand is Li^T itself: sigma* needs rowsum((Phi* Li^T)^2) (SCFGP/SCFGP.py:144), a triangular product
-    const void* Bt = c->d_AbarT;                                  // AbarT is scratch outside adjoint..pass3
-    if (c->dtype == SCFGP_F32) SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
-    else SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, nullptr, alpha, c->alpha_pred()))) return rc;
     DevTmp d_grad;                                                // dmu | dstd of all T rows (T x D each)
     if (grad) {
         if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D * (dstd ? 2 : 1)))) return rc;
-        if (c->dtype == SCFGP_F32) {
-            predgrad_operand(g0, c->d_Fall, (float*)c->p_FT, c->st);
-            if (dstd) SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
-        } else {
-            predgrad_operand(g0, c->d_Fall, (double*)c->p_FT, c->st);
-            if (dstd) SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
-        }
+        DISPATCH(c, grad_operand, c);
+        if (dstd) DISPATCH(c, type_factor, c, c->d_T1, nullptr, c->p_Li);      // p_Li exists with the std gradient only
     }
     double* d_dmu = d_grad; double* d_dsd = grad && dstd ? d_grad + T * g0.D : nullptr;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
@@ -1199,46 +1310,25 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
         HIPCHK(c, hipMemcpyAsync(d_ys, ys, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
         ypost_mean(d_ys, T, d_ys + T, c->st);
     }
-    // chunk i+1 is uploaded (pageable host memory: the call blocks the host while it stages) on the copy stream while the
-    // kernels of chunk i run; raw holds two chunks, ev_up / ev_free order its two halves between the streams
-    struct Events {
-        hipEvent_t up[2] = {nullptr, nullptr}, fre[2] = {nullptr, nullptr};
-        ~Events() { for (int i = 0; i < 2; ++i) { if (up[i]) (void)hipEventDestroy(up[i]); if (fre[i]) (void)hipEventDestroy(fre[i]); } }
-    } ev;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipEventCreateWithFlags(&ev.up[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&ev.fre[i], hipEventDisableTiming));
-    }
-    auto upload = [&](int64_t i) -> int {
-        const int64_t t0 = i * PRED_ROWS, n = std::min<int64_t>(PRED_ROWS, T - t0);
-        const int h = (int)(i & 1);
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xs + t0 * g0.D, sizeof(double) * n * g0.D, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(ev.up[h], c->copy_st));
-        return SCFGP_OK;
-    };
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
     if ((rc = upload(0))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
         const int64_t t0 = i * PRED_ROWS;
-        const int h = (int)(i & 1);
-        Geom g = g0;
-        g.N = std::min<int64_t>(PRED_ROWS, T - t0); g.Np = round_up(g.N, 256);
-        HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
-        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, raw_mode ? c->xs_mode : 0, c->d_xscale);
-        if (!grad) HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::predict_chunk(c, g, (const float*)Bt, d_mu + t0, d_sd + t0)
-                                   : Impl<double>::predict_chunk(c, g, (const double*)Bt, d_mu + t0, d_sd + t0);
-        if (rc) return rc;
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double* x;
+        if ((rc = feed.acquire(i, &x))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, raw_mode ? c->xs_mode : 0, c->d_xscale);
+        if (!grad && (rc = feed.release(i))) return rc;
+        if ((rc = DISPATCH(c, predict_chunk, c, g, LiT, d_mu + t0, d_sd + t0))) return rc;
         if (grad) {
-            // the gradients in x~, then the scalers' chain rules: the X scaler's at the raw inputs (still in raw's half h: its
-            // release is recorded after them), the y scaler's at the scaled mu, sigma (before ypost_chunk transforms them in place)
+            // the gradients in x~, then the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is
+            // released after them), the y scaler's at the scaled mu, sigma (before ypost_chunk transforms them in place)
             double* gm = d_dmu + t0 * g0.D; double* gs = d_dsd ? d_dsd + t0 * g0.D : nullptr;
-            rc = c->dtype == SCFGP_F32 ? Impl<float>::predict_grad_chunk(c, g, (const float*)Bt, d_sd + t0, gm, gs)
-                                       : Impl<double>::predict_grad_chunk(c, g, (const double*)Bt, d_sd + t0, gm, gs);
-            if (rc) return rc;
-            if (raw_mode && c->xs_mode) xgrad_chunk(raw + h * rawstride, g.N, g0.D, c->xs_mode, c->d_xscale, gm, gs, c->st);
+            if ((rc = DISPATCH(c, predict_grad_chunk, c, g, LiT, d_sd + t0, gm, gs))) return rc;
+            if (raw_mode && c->xs_mode) xgrad_chunk(x, g.N, g0.D, c->xs_mode, c->d_xscale, gm, gs, c->st);
             if (post) ygrad_chunk(d_mu + t0, d_sd + t0, g.N, g0.D, c->ys_mode, c->d_yscale, gm, gs, c->st);
-            HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
+            if ((rc = feed.release(i))) return rc;
         }
         if (post)
             ypost_chunk(d_mu + t0, d_sd + t0, d_ys.p ? d_ys + t0 : nullptr, g.N, c->ys_mode, c->d_yscale, d_ys.p ? d_ys + T : nullptr,
@@ -1333,8 +1423,7 @@ static int sample_weights_dev(scfgp_ctx* c, const double* alpha, const double* L
     if ((rc = dmalloc(c, &sw.wt.p, c->tsize() * n))) return rc;
     HIPCHK(c, hipMemcpyAsync(dli, Li, sizeof(double) * g.K * g.K, hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipMemcpyAsync(dal, alpha, sizeof(double) * g.K, hipMemcpyHostToDevice, c->st));
-    if (c->dtype == SCFGP_F32) sample_weights<float>(g, dli, dal, c->d_sc, nsamp, seed, sw.z, sw.w, (float*)sw.wt.p, c->st);
-    else sample_weights<double>(g, dli, dal, c->d_sc, nsamp, seed, sw.z, sw.w, sw.wt, c->st);
+    DISPATCH(c, weights, c, dli.p, dal.p, nsamp, seed, sw.z.p, sw.w.p, sw.wt.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->st));                     // dli, dal are released on return
     return SCFGP_OK;
@@ -1358,9 +1447,8 @@ extern "C" int scfgp_sample_weights(scfgp_ctx* c, const double* alpha, const dou
     return SCFGP_OK;
 }
 
-// A sibling of predict_impl: the same double-buffered upload of Xs on the copy stream, pack_data (with the X scaler in modes 1, 2) and
-// feature map per chunk of PRED_ROWS rows, then Phi* W.  The samples of a chunk land in one of two staging buffers and go to their
-// place in `out` on the copy stream while the next chunk computes: device memory is two chunks of samples whatever T is.
+// The chunk pipeline (RowFeed, OutRing) with the X scaler in modes 1, 2; per chunk Phi* W into one of two staging buffers: device memory
+// is two chunks of samples whatever T is.
 extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp, uint64_t seed,
                             int mode, int noise, double* out) {
     if (!c) return SCFGP_EARG;
@@ -1374,52 +1462,31 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
     if ((rc = ensure_pred_chunk(c))) return rc;
     SampleW sw;
     if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    const int64_t rawstride = PRED_ROWS * g0.D, rows = std::min<int64_t>(T, PRED_ROWS);
-    DevTmp raw, stage;                                            // two chunks of Xs | two chunks of samples
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * 2 * rawstride))) return rc;
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    RowFeed feed; OutRing ring; DevTmp stage;                     // two chunks of Xs | two chunks of samples
+    if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * nsamp))) return rc;
-    struct Events {
-        // up / fre: the two halves of raw (uploaded / free again); done / out: the two staging buffers (computed / copied out)
-        hipEvent_t e[4][2] = {};
-        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
-    for (auto& p : ev.e)
-        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
-    auto upload = [&](int64_t i) -> int {
-        const int64_t t0 = i * PRED_ROWS, n = std::min<int64_t>(PRED_ROWS, T - t0);
-        const int h = (int)(i & 1);
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xs + t0 * g0.D, sizeof(double) * n * g0.D, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
-        return SCFGP_OK;
-    };
-    // chunk i's samples to the host (pageable: the host waits in this call while chunk i + 1 computes)
-    auto download = [&](int64_t i) -> int {
-        const int64_t t0 = i * PRED_ROWS, n = std::min<int64_t>(PRED_ROWS, T - t0);
-        const int h = (int)(i & 1);
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
-        HIPCHK(c, hipMemcpyAsync(out + t0 * nsamp, stage + h * rows * nsamp, sizeof(double) * n * nsamp, hipMemcpyDeviceToHost, c->copy_st));
-        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
-        return SCFGP_OK;
+    if ((rc = ring.open(c))) return rc;
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto slot = [&](int64_t i) { return stage + (i & 1) * rows * nsamp; };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
+    auto download = [&](int64_t i) {
+        return ring.drain(i, [&]() -> int {
+            HIPCHK(c, hipMemcpyAsync(out + i * PRED_ROWS * nsamp, slot(i), sizeof(double) * rows_of(i) * nsamp, hipMemcpyDeviceToHost, c->copy_st));
+            return SCFGP_OK;
+        });
     };
     const int ymode = mode == 2 ? c->ys_mode : -1;
     if ((rc = upload(0))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = i * PRED_ROWS;
-        const int h = (int)(i & 1);
-        Geom g = g0;
-        g.N = std::min<int64_t>(PRED_ROWS, T - t0); g.Np = round_up(g.N, 256);
-        HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
-        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
-        HIPCHK(c, hipEventRecord(fre[h], c->st));
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[h], 0));
-        double* o = stage + h * rows * nsamp;
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::sample_chunk(c, g, (const float*)sw.wt.p, nsamp, t0, seed, noise, ymode, o)
-                                   : Impl<double>::sample_chunk(c, g, (const double*)sw.wt.p, nsamp, t0, seed, noise, ymode, o);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(done[h], c->st));
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double* x;
+        if ((rc = feed.acquire(i, &x))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        if ((rc = ring.acquire(i))) return rc;
+        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, i * PRED_ROWS, seed, noise, ymode, slot(i)))) return rc;
+        if ((rc = ring.computed(i))) return rc;
         if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
@@ -1433,12 +1500,10 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
 // ----------------------------------------------------------------------------------------------
 // joint posterior covariance between test points (predcov.hip; contract in include/scfgp_hip.h)
 // ----------------------------------------------------------------------------------------------
-// A sibling of predict_impl and scfgp_sample: the same double-buffered upload, pack_data (X scaler in mode 1) and feature map per
-// chunk of PRED_ROWS rows, then C = Phi* Li^T by apply_c.  Cb (the rows of Xb) is formed once, into p_V; each chunk of Xa gives Ca
-// in p_C; in the symmetric case (Ta <= PRED_ROWS) Ca is both operands.  A chunk's rows of the result are computed in panels of R
-// rows x Tb, full rows in the symmetric case too (its symmetry comes from the commutativity of the products, predcov.hip), into one
-// of two staging panels that the copy stream drains into `cov` while the next panel computes: device memory does not grow with
-// Ta x Tb.
+// The chunk pipeline (RowFeed, OutRing) with the X scaler in mode 1; the chunk body is C = Phi* Li^T.  Cb (the rows of Xb) is formed
+// once, into p_V, by job 0 of the feed; each chunk of Xa gives Ca in p_C; in the symmetric case (Ta <= PRED_ROWS) Ca is both operands.
+// A chunk's rows of the result are computed in panels of R rows x Tb, full rows in the symmetric case too (its symmetry comes from the
+// commutativity of the products, predcov.hip); the ring's slots are panels, not chunks: device memory does not grow with Ta x Tb.
 static constexpr int64_t COV_PANEL_BYTES = (int64_t)128 << 20;   // per staging panel: the size scfgp_sample stages per chunk at 512 samples
 extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, const double* Xb, int64_t Tb, const double* Li, int mode,
                                  int noise, double* cov) {
@@ -1464,78 +1529,48 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
     // panel height: whole 128-row tiles within COV_PANEL_BYTES, no more than a chunk holds
     const int64_t R = std::min<int64_t>(round_up(std::min<int64_t>(Ta, PRED_ROWS), 128),
                                         std::max<int64_t>(128, COV_PANEL_BYTES / ((int64_t)sizeof(double) * Tb) / 128 * 128));
-    DevTmp raw, stage;                                            // Li / two chunks of X | two panels of the result
-    const int64_t rawstride = PRED_ROWS * g0.D;
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    RowFeed feed; OutRing ring; DevTmp stage;                     // Li / two chunks of X | two panels of the result
+    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * R * Tb))) return rc;
-    // Li -> T1 (identity padding) -> the typed Li^T (AbarT: scratch outside adjoint..pass3) and Li, as predict_impl prepares them
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
-    pad_square(raw, g0.K, g0.Kp, c->d_T1, c->st);
-    if (c->dtype == SCFGP_F32) {
-        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
-    } else {
-        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
-    }
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    struct Events {
-        // up / fre: the two halves of raw (uploaded / free again); done / out: the two staging panels (computed / copied out)
-        hipEvent_t e[4][2] = {};
-        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
-    for (auto& p : ev.e)
-        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    if ((rc = ring.open(c))) return rc;
     // uploads: job 0 is Xb in the cross form, the chunks of Xa follow
     const int64_t nchunks = (Ta + PRED_ROWS - 1) / PRED_ROWS, first = sym ? 0 : 1, njobs = nchunks + first;
     auto job_rows = [&](int64_t job) { return job < first ? Tb : std::min<int64_t>(PRED_ROWS, Ta - (job - first) * PRED_ROWS); };
-    auto upload = [&](int64_t job) -> int {
-        const double* src = job < first ? Xb : Xa + (job - first) * PRED_ROWS * g0.D;
-        const int h = (int)(job & 1);
-        if (job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, src, sizeof(double) * job_rows(job) * g0.D, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
-        return SCFGP_OK;
+    auto upload = [&](int64_t job) {
+        return feed.upload(job, job < first ? Xb : Xa + (job - first) * PRED_ROWS * g0.D, nullptr, job_rows(job));
     };
-    // panel p (rows [row0, row0 + n) of the result) to the host (pageable: the host waits in this call while the next panel computes)
+    // panel p: rows [row0, row0 + n) of the result
     struct Panel { int64_t row0, n; };
-    auto download = [&](int64_t p, Panel pn) -> int {
-        const int h = (int)(p & 1);
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
-        HIPCHK(c, hipMemcpyAsync(cov + pn.row0 * Tb, stage + h * R * Tb, sizeof(double) * pn.n * Tb, hipMemcpyDeviceToHost, c->copy_st));
-        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
-        return SCFGP_OK;
+    auto slot = [&](int64_t p) { return stage + (p & 1) * R * Tb; };
+    auto download = [&](int64_t p, Panel pn) {
+        return ring.drain(p, [&]() -> int {
+            HIPCHK(c, hipMemcpyAsync(cov + pn.row0 * Tb, slot(p), sizeof(double) * pn.n * Tb, hipMemcpyDeviceToHost, c->copy_st));
+            return SCFGP_OK;
+        });
     };
-    const void* Bt = c->d_AbarT;
     int64_t npanel = 0;
     Panel prev = {0, 0};
     if ((rc = upload(0))) return rc;
     for (int64_t job = 0; job < njobs; ++job) {
-        const int h = (int)(job & 1);
-        Geom g = g0;
-        g.N = job_rows(job); g.Np = round_up(g.N, 256);
-        HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
-        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        HIPCHK(c, hipEventRecord(fre[h], c->st));
-        void* C = job < first ? c->p_V : c->p_C;
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::cov_factor_chunk(c, g, (const float*)Bt, (float*)C)
-                                   : Impl<double>::cov_factor_chunk(c, g, (const double*)Bt, (double*)C);
-        if (rc) return rc;
+        const Geom g = chunk_geom(g0, job_rows(job));
+        const double* x;
+        if ((rc = feed.acquire(job, &x))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(job))) return rc;
+        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, job < first ? c->p_V : c->p_C))) return rc;
         if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
         if (job < first) continue;
         const int64_t t0 = (job - first) * PRED_ROWS;
-        const char* Cb = (const char*)(sym ? c->p_C : c->p_V);
+        const void* Cb = sym ? c->p_C : c->p_V;
         for (int64_t r0 = 0; r0 < g.N; r0 += R, ++npanel) {
             const Panel pn = {t0 + r0, std::min<int64_t>(R, g.N - r0)};
-            const int ph = (int)(npanel & 1);
-            if (npanel >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[ph], 0));
-            const char* Ca = (const char*)c->p_C + ts * r0 * Kp;
-            double* o = stage + ph * R * Tb;
-            if (c->dtype == SCFGP_F32) predcov<float>(g0, (const float*)Ca, (const float*)Cb, pn.n, Tb, pn.row0, noise, c->d_sc, o, c->st);
-            else predcov<double>(g0, (const double*)Ca, (const double*)Cb, pn.n, Tb, pn.row0, noise, c->d_sc, o, c->st);
+            if ((rc = ring.acquire(npanel))) return rc;
+            DISPATCH(c, cov_panel, c, (const char*)c->p_C + ts * r0 * Kp, Cb, pn.n, Tb, pn.row0, noise, slot(npanel));
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(done[ph], c->st));
+            if ((rc = ring.computed(npanel))) return rc;
             if (npanel >= 1 && (rc = download(npanel - 1, prev))) return rc;
             prev = pn;
         }
@@ -1552,8 +1587,7 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
 // ----------------------------------------------------------------------------------------------
 // row splits of the update's Gram product over a chunk of Np rows, and the slabs they need
 static RowSplits update_splits(const scfgp_ctx* c, int64_t Np) {
-    const bool f32 = c->dtype == SCFGP_F32;
-    return gram_row_splits(f32 ? SweepKernels<float>::gram_jobs(c->g) : SweepKernels<double>::gram_jobs(c->g), Np, f32, 0, 1);
+    return gram_row_splits(DISPATCH(c, gram_jobs, c), Np, c->dtype == SCFGP_F32, 0, 1);
 }
 // the update stage's own buffers (first call only; the slabs grow to what the call's chunks need)
 static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
@@ -1580,9 +1614,9 @@ static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
     return SCFGP_OK;
 }
 
-// A sibling of scfgp_predict_cov: the same double-buffered upload (the targets ride behind the rows of their chunk), pack_data (X
-// scaler in mode 1), feature map and C = Phi_n Li^T per chunk of PRED_ROWS rows; each chunk adds its C^T C and C^T r to a running
-// fp64 sum, and one K x K stage turns the sum into the new factors.  The outputs are fetched only when the stage succeeded.
+// The chunk pipeline (RowFeed) with the targets behind the rows of their chunk and the X scaler in mode 1.  Each chunk adds its C^T C
+// and C^T r to a running fp64 sum, and one K x K stage turns the sum into the new factors, which leave through the feed's buffer.  The
+// outputs are fetched only when the stage succeeded.
 extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                                double* alpha_out, double* Li_out) {
     if (!c) return SCFGP_EARG;
@@ -1604,56 +1638,22 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
             need = std::max(need, sizeof(double) * (size_t)update_splits(c, np).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
         if ((rc = ensure_update(c, need))) return rc;
     }
-    DevTmp raw;                                                   // Li in host layout (in, then out) / two chunks of [X | y]
-    const int64_t rawstride = PRED_ROWS * (g0.D + 1);
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    RowFeed feed;                                                 // Li in host layout (in, then out) / two chunks of [X | y]
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
     double* d_alpha = c->u_vec; double* d_gamma = c->u_vec + Kp; double* d_alpha_out = c->u_vec + 2 * Kp; double* d_parts = c->u_vec + 3 * Kp;
     HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
-    update_load_factor(raw, g0.K, g0.Kp, c->u_Li, c->st);
-    HIPCHK(c, hipMemsetAsync(d_alpha, 0, sizeof(double) * Kp, c->st));
-    HIPCHK(c, hipMemcpyAsync(d_alpha, alpha, sizeof(double) * g0.K, hipMemcpyHostToDevice, c->st));
-    update_check_finite(c->u_Li, K2, c->u_flag, c->st);
-    update_check_finite(d_alpha, Kp, c->u_flag, c->st);
-    if (c->dtype == SCFGP_F32) {
-        SweepKernels<float>::convert_transposed(c->u_Li, (float*)c->u_LiT, g0.K, g0.Kp, c->st);
-        SweepKernels<float>::convert(c->u_Li, (float*)c->p_Li, g0.K, g0.Kp, c->st);
-    } else {
-        SweepKernels<double>::convert_transposed(c->u_Li, (double*)c->u_LiT, g0.K, g0.Kp, c->st);
-        SweepKernels<double>::convert(c->u_Li, (double*)c->p_Li, g0.K, g0.Kp, c->st);
-    }
+    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->u_Li, c->u_LiT, c->p_Li, alpha, d_alpha, c->u_flag))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    struct Events {
-        hipEvent_t up[2] = {nullptr, nullptr}, fre[2] = {nullptr, nullptr};
-        ~Events() { for (int i = 0; i < 2; ++i) { if (up[i]) (void)hipEventDestroy(up[i]); if (fre[i]) (void)hipEventDestroy(fre[i]); } }
-    } ev;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipEventCreateWithFlags(&ev.up[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&ev.fre[i], hipEventDisableTiming));
-    }
     auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) -> int {
-        const int64_t t0 = i * PRED_ROWS, m = rows_of(i);
-        const int h = (int)(i & 1);
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xn + t0 * g0.D, sizeof(double) * m * g0.D, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride + PRED_ROWS * g0.D, yn + t0, sizeof(double) * m, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(ev.up[h], c->copy_st));
-        return SCFGP_OK;
-    };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xn + i * PRED_ROWS * g0.D, yn + i * PRED_ROWS, rows_of(i)); };
     if ((rc = upload(0))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int h = (int)(i & 1);
-        Geom g = g0;
-        g.N = rows_of(i); g.Np = round_up(g.N, 256);
-        HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
-        pack_data(g, raw + h * rawstride, raw + h * rawstride + PRED_ROWS * g0.D, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0,
-                  c->d_xscale);
-        HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
-        const RowSplits rs = update_splits(c, g.Np);
-        double* out = i == 0 ? c->u_acc : c->u_part;
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::update_chunk(c, g, rs, out) : Impl<double>::update_chunk(c, g, rs, out);
-        if (rc) return rc;
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *y;
+        if ((rc = feed.acquire(i, &x, &y))) return rc;
+        pack_data(g, x, y, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        if ((rc = DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), i == 0 ? c->u_acc : c->u_part))) return rc;
         if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
         if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
     }
@@ -1665,14 +1665,14 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
     kstage_update(k, c->st);
     update_check_finite(c->u_S, K2, c->u_flag, c->st);
     update_check_finite(d_alpha_out, Kp, c->u_flag, c->st);
-    update_store_factor(c->u_S, g0.K, g0.Kp, raw, c->st);
+    update_store_factor(c->u_S, g0.K, g0.Kp, feed.raw, c->st);
     HIPCHK(c, hipGetLastError());
     int flags[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (flags[1]) { c->err = "condition: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
     if (flags[0]) { c->err = "condition: I + C^T C is not positive definite"; return SCFGP_ENOTPD; }
-    HIPCHK(c, hipMemcpyAsync(Li_out, raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(Li_out, feed.raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(alpha_out, d_alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SCFGP_OK;
@@ -1692,10 +1692,10 @@ static int ensure_loo(scfgp_ctx* c) {
     return SCFGP_OK;
 }
 
-// A sibling of scfgp_condition: the same double-buffered upload with the targets behind the rows of their chunk (resident rows are
-// read where they lie: d_Xraw / d_yraw, never the evaluation's working set), pack_data, feature map, C = Phi_I Li^T and the residual
-// per chunk; then the block kernel.  A chunk holds floor(32768 / block) whole blocks, so no block straddles two chunks.  mu | std | lev
-// leave through two staging halves on the copy stream; the stats and the flags are fetched once, at the end.
+// The chunk pipeline (RowFeed, OutRing) with the targets behind the rows of their chunk; resident rows bypass the feed and are read
+// where they lie (d_Xraw / d_yraw, never the evaluation's working set).  Per chunk C = Phi_I Li^T, the residual and the block kernel.  A
+// chunk holds floor(32768 / block) whole blocks, so no block straddles two chunks.  mu | std | lev leave through the two halves of
+// l_out; the stats and the flags are fetched once, at the end.
 extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode,
                          int block, double* mu, double* sd, double* lev, double* stats) {
     if (!c) return SCFGP_EARG;
@@ -1712,83 +1712,50 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
     if (!c->have_params) { c->err = "loo: parameters not set"; return SCFGP_EARG; }
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
     const int64_t CH = PRED_ROWS / block * block;               // rows per chunk: whole blocks
     const int64_t nchunks = (n + CH - 1) / CH;
     int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     if ((rc = ensure_loo(c))) return rc;
-    DevTmp raw;                                                   // Li in host layout / two chunks of [X | y]
-    const int64_t rawstride = PRED_ROWS * (g0.D + 1);
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, resident ? 0 : 2 * rawstride)))) return rc;
-    // Li -> T1 (identity padding) -> the typed Li^T (AbarT: scratch outside adjoint..pass3) and Li; alpha, as predict_impl prepares them
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
-    pad_square(raw, g0.K, g0.Kp, c->d_T1, c->st);
-    HIPCHK(c, hipMemsetAsync(c->alpha_pred(), 0, sizeof(double) * Kp, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->alpha_pred(), alpha, sizeof(double) * g0.K, hipMemcpyHostToDevice, c->st));
-    if (c->dtype == SCFGP_F32) {
-        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
-    } else {
-        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
-    }
+    RowFeed feed; OutRing ring;                                   // Li in host layout / two chunks of [X | y] (resident rows: Li only)
+    if ((rc = feed.open(c, resident ? 0 : PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
     const unsigned long long bad0[2] = {0ull, ~0ull};
     HIPCHK(c, hipMemsetAsync(c->l_acc, 0, sizeof(double) * 8, c->st));
     HIPCHK(c, hipMemcpyAsync(c->l_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    struct Events {
-        // up / fre: the two halves of raw (uploaded / free again); done / copied: the two staging halves (computed / copied out)
-        hipEvent_t e[4][2] = {};
-        ~Events() { for (auto& p : e) for (hipEvent_t x : p) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    hipEvent_t(&up)[2] = ev.e[0]; hipEvent_t(&fre)[2] = ev.e[1]; hipEvent_t(&done)[2] = ev.e[2]; hipEvent_t(&copied)[2] = ev.e[3];
-    for (auto& p : ev.e)
-        for (hipEvent_t& x : p) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    if ((rc = ring.open(c))) return rc;
     auto rows_of = [&](int64_t i) { return std::min<int64_t>(CH, n - i * CH); };
-    auto upload = [&](int64_t i) -> int {
-        if (resident) return SCFGP_OK;
-        const int64_t t0 = i * CH, m = rows_of(i);
-        const int h = (int)(i & 1);
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, X + t0 * g0.D, sizeof(double) * m * g0.D, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride + PRED_ROWS * g0.D, y + t0, sizeof(double) * m, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(up[h], c->copy_st));
-        return SCFGP_OK;
+    auto upload = [&](int64_t i) { return resident ? SCFGP_OK : feed.upload(i, X + i * CH * g0.D, y + i * CH, rows_of(i)); };
+    auto slot = [&](int64_t i) { return c->l_out + (i & 1) * 3 * PRED_ROWS; };
+    auto download = [&](int64_t i) {
+        return ring.drain(i, [&]() -> int {
+            const int64_t t0 = i * CH, m = rows_of(i);
+            const double* o = slot(i);
+            HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+            HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+            if (lev) HIPCHK(c, hipMemcpyAsync(lev + t0, o + 2 * PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+            return SCFGP_OK;
+        });
     };
-    auto download = [&](int64_t i) -> int {
-        const int64_t t0 = i * CH, m = rows_of(i);
-        const int h = (int)(i & 1);
-        const double* o = c->l_out + h * 3 * PRED_ROWS;
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, done[h], 0));
-        HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-        HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-        if (lev) HIPCHK(c, hipMemcpyAsync(lev + t0, o + 2 * PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-        HIPCHK(c, hipEventRecord(copied[h], c->copy_st));
-        return SCFGP_OK;
-    };
-    const void* Bt = c->d_AbarT;
     if ((rc = upload(0))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int h = (int)(i & 1);
         const int64_t t0 = i * CH;
-        Geom g = g0;
-        g.N = rows_of(i); g.Np = round_up(g.N, 256);
+        const Geom g = chunk_geom(g0, rows_of(i));
         if (resident) {
             pack_data(g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->p_Xt, c->l_y, c->st);
         } else {
-            HIPCHK(c, hipStreamWaitEvent(c->st, up[h], 0));
-            pack_data(g, raw + h * rawstride, raw + h * rawstride + PRED_ROWS * g0.D, nullptr, c->p_Xt, c->l_y, c->st,
-                      mode == 1 ? c->xs_mode : 0, c->d_xscale);
-            HIPCHK(c, hipEventRecord(fre[h], c->st));
+            const double *xi, *yi;
+            if ((rc = feed.acquire(i, &xi, &yi))) return rc;
+            pack_data(g, xi, yi, nullptr, c->p_Xt, c->l_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+            if ((rc = feed.release(i))) return rc;
         }
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, copied[h], 0));
-        double* o = c->l_out + h * 3 * PRED_ROWS;
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::loo_chunk(c, g, (const float*)Bt, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS)
-                                   : Impl<double>::loo_chunk(c, g, (const double*)Bt, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS);
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(done[h], c->st));
+        if ((rc = ring.acquire(i))) return rc;
+        double* o = slot(i);
+        if ((rc = DISPATCH(c, loo_chunk, c, g, LiT, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS))) return rc;
+        if ((rc = ring.computed(i))) return rc;
         if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
@@ -1819,10 +1786,10 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
 static constexpr int SELECT_MAX_M = 4096;
 static constexpr int64_t SELECT_MAX_T = (int64_t)1 << 20;
 static constexpr int SELECT_MAX_KP = 8192;                        // u_j lives in LDS as fp64: 64 KB
-// A sibling of scfgp_predict_cov: the same double-buffered upload, pack_data (X scaler in mode 1), feature map and C = Phi_c Li^T per
-// chunk of PRED_ROWS rows -- each chunk's C written to its place in a T x Kp buffer that this call owns.  Then d = rowsum(C^2) and
-// m picks, every one of them a handful of eager launches on the context's stream (select.hip); the host waits once before the picks
-// (for the non-finite flag of d) and once after them.  idx / var / gain are fetched at the end, std_after leaves on the copy stream.
+// The chunk pipeline (RowFeed) with the X scaler in mode 1; the chunk body is C = Phi_c Li^T, each chunk's C written to its place in a
+// T x Kp buffer that this call owns.  Then d = rowsum(C^2) and m picks, every one of them a handful of eager launches on the context's
+// stream (select.hip); the host waits once before the picks (for the non-finite flag of d) and once after them.  idx / var / gain are
+// fetched at the end, std_after leaves on the copy stream.
 extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Li, int m, int mode, int64_t* idx,
                             double* var, double* gain, double* std_after) {
     if (!c) return SCFGP_EARG;
@@ -1857,9 +1824,9 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
-    DevTmp raw, Cbuf, rows, picks;                                // Li / two chunks of X | C | w, d, std, partials | U, cp, a, part, idx, var, gain, flag
-    const int64_t rawstride = PRED_ROWS * g0.D;
-    if ((rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>((int64_t)g0.K * g0.K, 2 * rawstride)))) return rc;
+    RowFeed feed; DevTmp Cbuf, rows, picks;                       // Li / two chunks of X | C | w, d, std, partials | U, cp, a, part, idx, var, gain, flag
+    Events<1> sd_done;                                            // std_after is computed
+    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
     if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
         (void)hipGetLastError();
         c->err = "select: no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
@@ -1879,79 +1846,41 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
     if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
     else select_ones(b.w, T, c->st);
-    // Li -> T1 (lower triangle only, identity padding: update_load_factor, so that entries above the diagonal are never read) -> the
-    // typed Li^T (AbarT: scratch outside adjoint..pass3) and Li, as scfgp_predict_cov prepares them
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g0.K * g0.K, hipMemcpyHostToDevice, c->st));
-    update_load_factor(raw, g0.K, g0.Kp, c->d_T1, c->st);
-    if (c->dtype == SCFGP_F32) {
-        SweepKernels<float>::convert_transposed(c->d_T1, (float*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<float>::convert(c->d_T1, (float*)c->p_Li, g0.K, g0.Kp, c->st);
-    } else {
-        SweepKernels<double>::convert_transposed(c->d_T1, (double*)c->d_AbarT, g0.K, g0.Kp, c->st);
-        SweepKernels<double>::convert(c->d_T1, (double*)c->p_Li, g0.K, g0.Kp, c->st);
-    }
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    struct Events {
-        hipEvent_t up[2] = {nullptr, nullptr}, fre[2] = {nullptr, nullptr}, done = nullptr;
-        ~Events() {
-            for (int i = 0; i < 2; ++i) { if (up[i]) (void)hipEventDestroy(up[i]); if (fre[i]) (void)hipEventDestroy(fre[i]); }
-            if (done) (void)hipEventDestroy(done);
-        }
-    } ev;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipEventCreateWithFlags(&ev.up[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&ev.fre[i], hipEventDisableTiming));
-    }
-    HIPCHK(c, hipEventCreateWithFlags(&ev.done, hipEventDisableTiming));
+    if ((rc = sd_done.create(c))) return rc;
     auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) -> int {
-        const int h = (int)(i & 1);
-        if (i >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.fre[h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * rawstride, Xc + i * PRED_ROWS * g0.D, sizeof(double) * rows_of(i) * g0.D, hipMemcpyHostToDevice,
-                                 c->copy_st));
-        HIPCHK(c, hipEventRecord(ev.up[h], c->copy_st));
-        return SCFGP_OK;
-    };
-    const void* Bt = c->d_AbarT;
-    char* Call = (char*)Cbuf.p;
+    auto upload = [&](int64_t i) { return feed.upload(i, Xc + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
     if ((rc = upload(0))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int h = (int)(i & 1);
-        Geom g = g0;
-        g.N = rows_of(i); g.Np = round_up(g.N, 256);
-        HIPCHK(c, hipStreamWaitEvent(c->st, ev.up[h], 0));
-        pack_data(g, raw + h * rawstride, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        HIPCHK(c, hipEventRecord(ev.fre[h], c->st));
-        void* Ci = Call + ts * (size_t)(i * PRED_ROWS) * Kp;
-        rc = c->dtype == SCFGP_F32 ? Impl<float>::cov_factor_chunk(c, g, (const float*)Bt, (float*)Ci)
-                                   : Impl<double>::cov_factor_chunk(c, g, (const double*)Bt, (double*)Ci);
-        if (rc) return rc;
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double* x;
+        if ((rc = feed.acquire(i, &x))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, (char*)Cbuf.p + ts * (size_t)(i * PRED_ROWS) * Kp))) return rc;
         if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
     }
-    const bool f32 = c->dtype == SCFGP_F32;
-    if (f32) select_init<float>(b, (const float*)Cbuf.p, c->st);
-    else select_init<double>(b, (const double*)Cbuf.p, c->st);
+    DISPATCH(c, pick_init, c, b, Cbuf.p);
     HIPCHK(c, hipGetLastError());
     int flag = 0;
     HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    for (int j = 0; j < m; ++j) {
-        if (f32) select_step<float>(b, (const float*)Cbuf.p, j, c->d_sc, c->st);
-        else select_step<double>(b, (const double*)Cbuf.p, j, c->d_sc, c->st);
-    }
+    for (int j = 0; j < m; ++j) DISPATCH(c, pick, c, b, Cbuf.p, j);
     HIPCHK(c, hipGetLastError());
     if (std_after) {
         select_std(b, c->d_sc, d_sd, c->st);
-        HIPCHK(c, hipEventRecord(ev.done, c->st));
+        HIPCHK(c, hipEventRecord(sd_done.e[0], c->st));
     }
     HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
     if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
     if (std_after) {
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.done, 0));
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, sd_done.e[0], 0));
         HIPCHK(c, hipMemcpyAsync(std_after, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->copy_st));
     }
     HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));

@@ -17,6 +17,7 @@ from tests import pred_cov_ref
 ABC = (-1.0, 0.0, -1.0)
 CASES = [(5, 4, 60, 1000, 1000, 40), (3, 1, 20, 150, 150, 150), (20, 20, 280, 3000, 700, 64), (64, 32, 1024, 1500, 600, 24)]
 LONG = (5, 4, 60, 1000, 32768 + 300, 8)         # two chunks; w = 0 on all but 50 rows that straddle row 32768
+LONG3 = (5, 4, 60, 1000, 65536 + 300, 8)        # three chunks (a buffer of the row feed is reused); 50 such rows at each of 32768 and 65536
 
 
 def kappa(params):
@@ -25,7 +26,8 @@ def kappa(params):
 
 def long_weights(T=LONG[4]):
     w = np.zeros(T)
-    w[32768 - 25:32768 + 25] = 1.0
+    for b in range(32768, T, 32768):
+        w[b - 25:b + 25] = 1.0
     return w
 
 
@@ -89,7 +91,7 @@ def replay(C, w, idx):
 
 
 def problem(case):
-    """(params, X0, y0, Xpool) of a row of CASES / LONG"""
+    """(params, X0, y0, Xpool) of a row of CASES / LONG / LONG3"""
     from tests import loo_ref
     D, S, M, N0, T, m = case
     params, X, y = loo_ref.problem(D, S, M, N0 + T, ABC)

@@ -15,9 +15,10 @@ from tests import parity
 
 pytestmark = pytest.mark.gpu
 
-# tests/test_condition_ref.py's shapes and one whose new rows fill a chunk of 32 768 and leave a ragged second one
+# tests/test_condition_ref.py's shapes and two whose new rows fill one / two chunks of 32 768 and leave a ragged last one (with three
+# chunks a half of the upload buffer is reused)
 SHAPES = [(5, 4, 60, 1000, 300), (5, 4, 60, 1000, 1), (20, 20, 280, 3000, 700), (64, 32, 1024, 4000, 900), (3, 1, 20, 150, 400),
-          (40, 4, 100, 2000, 129), (5, 4, 60, 1000, 32768 + 300)]
+          (40, 4, 100, 2000, 129), (5, 4, 60, 1000, 32768 + 300), (5, 4, 60, 1000, 65536 + 300)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -113,6 +113,34 @@ def test_chunk_boundary_lands_on_a_block_boundary(dtype):
     eng.close()
 
 
+@functools.lru_cache(maxsize=None)
+def _long3():
+    D, S, M, n, block = 5, 4, 60, 65536 + 300, 7
+    params, X, y = R.problem(D, S, M, n, (-1.0, 0.0, -1.0))
+    _, alpha, Li = O.forward(X, y, params, S, M, gauss_hermite=False)
+    return (D, S, M, n, block), params, X, y, alpha, Li
+
+
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_third_chunk_starts_on_a_block_boundary(dtype):
+    """three chunks of 32767 rows: the third one reuses the first one's upload half and output half, and starts at row 65534 = 7 x 9362.
+    65836 = 7 x 9405 + 1: the ragged last block is one row."""
+    (D, S, M, n, block), params, X, y, alpha, Li = _long3()
+    eng = _engine(D, S, M, dtype, params)
+    mu, sd, lev, st = eng.loo(X, y, alpha, Li, block=block)
+    lo, hi = 7 * 9360, 7 * 9370                                       # blocks 9360 .. 9369 around row 65534
+    assert lo < 65534 < hi and st['blocks'] == 9406 and st['n'] == n
+    ref = R.loo(X[lo:hi], y[lo:hi], alpha, Li, params, S, M, block)
+    lm = R.row_lmax(ref, hi - lo, block)
+    r = (parity.predict_ratio(mu[lo:hi], sd[lo:hi], ref['mu'], ref['std'], 'f64') if dtype == 'f64' else
+         _ratio32(mu[lo:hi], sd[lo:hi], ref['mu'], ref['std'], lm))
+    print('third chunk %s: ratio %.3g' % (dtype, r))
+    assert r <= 1.0
+    mu2, sd2, lev2, _ = eng.loo(X[lo:hi], y[lo:hi], alpha, Li, block=block)
+    assert np.array_equal(mu2, mu[lo:hi]) and np.array_equal(sd2, sd[lo:hi]) and np.array_equal(lev2, lev[lo:hi])
+    eng.close()
+
+
 def _host_stats(mu, sd, lev, y):
     e = np.ravel(y) - np.ravel(mu)
     var = sd * sd

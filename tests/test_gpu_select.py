@@ -24,7 +24,7 @@ EPS = {'f64': parity.TOL['f64']['eps'], 'f32': parity.TOL['f32']['eps']}
 # gives f16x3 over fp32.
 MEASURED_PICK, MEASURED_VAR = 0.0, 0.0418
 ETA = 4.0 * max(MEASURED_PICK, MEASURED_VAR) * EPS['f32']
-ALL = R.CASES + [R.LONG]
+ALL = R.CASES + [R.LONG, R.LONG3]
 
 
 @functools.lru_cache(maxsize=None)
@@ -33,7 +33,7 @@ def _setup(case):
     params, X0, y0, Xp = R.problem(case)
     _, alpha, Li = O.forward(X0, y0, params, S, M, gauss_hermite=False)
     C = pred_cov_ref.factor(Xp, Li, params, S, M)
-    w = R.long_weights() if case == R.LONG else None
+    w = R.long_weights(T) if case in (R.LONG, R.LONG3) else None
     return params, X0, y0, Xp, alpha, Li, C, w, R.select(C, m, w=w, kap=R.kappa(params))
 
 
@@ -76,6 +76,8 @@ def test_fp64_picks_equal_the_reference(case):
     parity.check_predict(sd0, sd, sd0, sd0, 'f64')
     if case == R.LONG:
         assert idx.min() < 32768 <= idx.max() and np.all(w[idx] > 0)
+    if case == R.LONG3:
+        assert idx.min() < 32768 and np.any((idx >= 32768) & (idx < 65536)) and idx.max() >= 65536 and np.all(w[idx] > 0)
 
 
 def fp32_ratios(case, idx, var):

@@ -104,12 +104,24 @@ def test_weights():
         R.select(C, 4, w=w3)
 
 
-def test_long_case_picks_from_both_sides_of_the_chunk_boundary():
-    D, S, M, N0, T, m = R.LONG
-    params, X0, y0, Xp = R.problem(R.LONG)
+def _long_reference(case):
+    D, S, M, N0, T, m = case
+    params, X0, y0, Xp = R.problem(case)
     _, alpha, Li = O.forward(X0, y0, params, S, M, gauss_hermite=False)
     C = pred_cov_ref.factor(Xp, Li, params, S, M)
-    w = R.long_weights()
-    ref = R.select(C, m, w=w, kap=R.kappa(params))
+    w = R.long_weights(T)
+    return w, R.select(C, m, w=w, kap=R.kappa(params))
+
+
+def test_long_case_picks_from_both_sides_of_the_chunk_boundary():
+    w, ref = _long_reference(R.LONG)
     assert np.all(w[ref['idx']] > 0) and ref['idx'].min() < 32768 <= ref['idx'].max()
+    assert ref['gap'].min() > 1e-8
+
+
+def test_three_chunk_case_picks_from_every_chunk():
+    w, ref = _long_reference(R.LONG3)
+    idx = ref['idx']
+    print('select ref %s: picks %s, smallest gap %.3g' % (R.LONG3, idx.tolist(), ref['gap'].min()))
+    assert np.all(w[idx] > 0) and idx.min() < 32768 and np.any((idx >= 32768) & (idx < 65536)) and idx.max() >= 65536
     assert ref['gap'].min() > 1e-8

@@ -1,0 +1,125 @@
+"""Bit identity of the posterior entry points between two builds of the library (default: '_head', the parent commit's build made by
+tools/build_head.sh, and '', the working tree's).  For each variant in turn a fresh child process -- one on the GPU at a time, under a
+time limit of its own; this process never opens the GPU -- runs a fixed, seeded list of calls and writes a SHA-256 per output array.
+Then a table, and exit status 1 on any difference.  A child that fails or runs out of time ends the run.
+
+The list, for f32 and f64, at (D, S, M) = (5, 4, 60) with 65 836 rows (three chunks of 32 768: the buffers of the chunk pipeline are
+reused) and at (20, 20, 280) with 5000 rows: predict, predict_raw, predict_y with targets (metrics included); predict_grad in its three
+modes with and without the std gradient; sample_weights; sample in its three modes with and without noise, 3 samples; predict_cov
+symmetric at 2500 rows, cross at all rows x 50 and at 2500 x 9000 (two panels per chunk); condition in both modes; loo with blocks
+1, 7, 64 from host rows and block 7 on resident rows; select without weights and with weights around the chunk boundaries, with
+std_after.  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
+Usage: python tools/posterior_ab.py [--variants _head,] [--limit SECONDS]        (default limit: 300 per child)
+       python tools/posterior_ab.py --child OUT.json                             (the list, in this process, on SCFGP_LIB_VARIANT)"""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SHAPES = [(5, 4, 60, 65536 + 300), (20, 20, 280, 5000)]
+
+
+def digest(a):
+    if isinstance(a, dict):
+        a = np.array([a[k] for k in sorted(a)], np.float64)
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def calls(D, S, M, n, dt):
+    """yields (name, tuple of output arrays)"""
+    from scfgp_amd import synth
+    from scfgp_amd.engine import HipEngine
+    from scfgp_amd.scaler import Scaler
+    K = 2 * (S + M)
+    rng = np.random.default_rng(7)
+    params = synth.make_params(11, D, S, M, abc=(-1.0, 0.0, -1.0))
+    X = synth.make_X(3, n, D)
+    y = np.sin(3 * X[:, :1]) + 0.1 * rng.standard_normal((n, 1))
+    Li = 0.02 * (np.tril(rng.standard_normal((K, K))) / np.sqrt(K) + np.eye(K))
+    alpha = rng.standard_normal(K) / np.sqrt(K)
+    Xr = 1.5 * X + 0.25                                         # "raw" rows whose scaler maps them back near X
+    xs = Scaler('normal'); xs.fit(Xr)
+    ys = Scaler('min-max'); ys.fit(y)
+    eng = HipEngine(D, S, M, dtype=dt)
+    eng.set_params(params)
+    eng.set_x_scaler(xs); eng.set_y_scaler(ys)
+    yield 'predict', eng.predict(X, alpha, Li)
+    yield 'predict_raw', eng.predict_raw(Xr, alpha, Li)
+    yield 'predict_y', eng.predict_y(Xr, alpha, Li, ys=y)
+    for mode in ('scaled', 'raw', 'y'):
+        for want_std in (False, True):
+            out = eng.predict_grad(Xr if mode != 'scaled' else X, alpha, Li, mode=mode, want_std=want_std)
+            yield 'predict_grad %s std=%d' % (mode, want_std), out[:3] + ((out[3],) if want_std else ())
+    yield 'sample_weights', (eng.sample_weights(alpha, Li, 3, seed=5),)
+    for mode in ('scaled', 'raw', 'y'):
+        for noise in (False, True):
+            yield 'sample %s noise=%d' % (mode, noise), (eng.sample(Xr if mode != 'scaled' else X, alpha, Li, 3, seed=5, mode=mode, noise=noise),)
+    yield 'predict_cov sym 2500', (eng.predict_cov(X[:2500], Li, noise=True),)
+    yield 'predict_cov cross %d x 50' % n, (eng.predict_cov(X, Li, Xb=X[100:150]),)
+    Xb = synth.make_X(4, 9000, D)
+    yield 'predict_cov cross 2500 x 9000 raw', (eng.predict_cov(Xr[:2500], Li, Xb=1.5 * Xb + 0.25, mode='raw'),)
+    yield 'condition scaled', eng.condition(X, y, alpha, Li)
+    yield 'condition raw', eng.condition(Xr, y, alpha, Li, mode='raw')
+    for block in (1, 7, 64):
+        out = eng.loo(X, y, alpha, Li, block=block)
+        yield 'loo block %d' % block, out[:3] + (out[3],)
+    eng.set_data(X, y)
+    out = eng.loo(None, None, alpha, Li, block=7)
+    yield 'loo resident block 7', out[:3] + (out[3],)
+    yield 'select', eng.select(X, Li, 8, return_std=True)
+    w = np.zeros(n)
+    for b in range(32768, n, 32768):
+        w[b - 25:b + 25] = 1.0
+    if not w.any():
+        w[n // 2 - 25:n // 2 + 25] = 1.0
+    yield 'select weights raw', eng.select(Xr, Li, 8, w=w, raw=True, return_std=True)
+    eng.close()
+
+
+def child(out_path):
+    res = {}
+    for D, S, M, n in SHAPES:
+        for dt in ('f32', 'f64'):
+            for name, arrays in calls(D, S, M, n, dt):
+                for k, a in enumerate(arrays):
+                    res['%s (%d,%d,%d) n=%d | %s | %d' % (dt, D, S, M, n, name, k)] = digest(a)
+    with open(out_path, 'w') as f:
+        json.dump(res, f)
+    return 0
+
+
+def main(argv):
+    if argv[:1] == ['--child']:
+        return child(argv[1])
+    variants = argv[argv.index('--variants') + 1].split(',') if '--variants' in argv else ['_head', '']
+    limit = argv[argv.index('--limit') + 1] if '--limit' in argv else '300'
+    got = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for v in variants:
+            out = os.path.join(tmp, 'hashes%s.json' % v)
+            r = subprocess.run(['timeout', '-k', '10', limit, sys.executable, os.path.abspath(__file__), '--child', out], cwd=ROOT,
+                               env=dict(os.environ, SCFGP_LIB_VARIANT=v))
+            if r.returncode != 0:
+                print('variant %r failed: exit status %d' % (v, r.returncode), flush=True)
+                return r.returncode
+            with open(out) as f:
+                got.append(json.load(f))
+    a, b = got
+    bad = 0
+    print('%-78s %-14s %-14s' % ('dtype shape | call | output', repr(variants[0]), repr(variants[1])))
+    for key in sorted(set(a) | set(b)):
+        same = a.get(key) == b.get(key)
+        bad += not same
+        print('%-78s %-14s %-14s %s' % (key, a.get(key, '-')[:12], b.get(key, '-')[:12], 'same' if same else 'DIFFERENT'))
+    print('%d outputs, %d different' % (len(set(a) | set(b)), bad), flush=True)
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main(sys.argv[1:]) or 0)
