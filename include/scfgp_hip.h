@@ -272,10 +272,46 @@ int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const
  * survives (resident rows, exchange buffers, optimiser state, precision level).
  * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL pointers, a bad m, T or mode, a missing X scaler in mode 1,
  * parameters not set, a negative weight, or fewer than m rows with a positive weight; SCFGP_ENONFINITE for non-finite rows, weights or
- * factors: the outputs are untouched in both cases.  Out of scope: integrated-variance criteria (ALC / A-optimal), a row-sharded pool,
+ * factors: the outputs are untouched in both cases.  Integrated-variance criteria (ALC / A-optimal): scfgp_select_iv.  Out of scope: a row-sharded pool,
  * raw-y units (the criterion is in scaled-y units), and factors kept on the device between calls. */
 int scfgp_select(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Li, int m, int mode, int64_t* idx,
                  double* var, double* gain, double* std_after);
+
+/* ---- greedy choice of m pool rows by integrated variance reduction (ALC / A-optimal; no reference counterpart) -------------------------
+ * scfgp_select asks where the model is most uncertain; this entry point asks which observation most reduces the uncertainty WHERE THE
+ * MODEL WILL BE USED: a reference set Xr (R x D) with non-negative weights omega.  Notation as scfgp_select: C = Phi_c Li^T of the pool,
+ * d_i = |c_i|^2, u_l the Sherman-Morrison directions of the picks so far, P = I - sum_{l<j} u_l u_l^T.  With C_R = Phi_r Li^T,
+ * Q = C_R^T diag(omega) C_R (K x K, symmetric positive semi-definite, formed once) and a_i = c_i^T P Q P c_i, observing pool row i with
+ * noise kappa lowers sum_r omega_r Var[f(x_r)] by kappa a_i / (1 + d_i), and the integrated variance itself is kappa tr(P Q).  Step j:
+ *     p_j = argmax over the rows not yet taken with w_i > 0 of  w_i a_i / (1 + d_i)           (ties: the lowest index)
+ *     t, dp, u_j exactly as scfgp_select
+ *     h = Q u_j       q = u_j . h                       (q = a_p / (1 + d_p): the reduction achieved, in units of kappa)
+ *     g = h - sum_{l<j} u_l (u_l . h)                   (= P Q u_j, with P from before this pick)
+ *     v = g - (q / 2) u_j
+ *     for every i:  s_i = c_i . u_j,  z_i = c_i . v,   a_i <- max(a_i - 2 s_i z_i, 0),   d_i <- max(d_i - s_i^2, 0)
+ * from a_i^(0) = c_i^T Q c_i, d_i^(0) = |c_i|^2: with P' = P - u u^T, c^T P' Q P' c = a - 2 s (c . P Q u) + s^2 q = a - 2 s (c . v).
+ * Xc, T, w, Li, m, mode, idx, var (= kappa dp_j) and std_after (= sqrt(kappa (1 + d_i^(m)))) mean what they mean in scfgp_select.  Xr
+ * (R x D, same mode as Xc): the reference rows; Xr == NULL: the pool is its own reference (R is ignored; wr, if given, has T entries).
+ * wr (may be NULL = ones): non-negative finite weights omega, at least one positive.  R >= 1 without limit: the reference rows go through
+ * the chunk pipeline and only Q is kept.  Outputs: red (m, may be NULL): kappa q_j, the reduction of the integrated variance by pick j;
+ * ivar (2 doubles, may be NULL): [0] kappa tr(Q), the integrated variance before the picks (noise excluded), [1] = [0] - sum_j red[j],
+ * subtracted in pick order by one thread.
+ * Bounds: 1 <= m <= min(4096, number of rows with w_i > 0), 1 <= T <= 2^20, K <= 4096 (u_j and v are held in LDS together).  The call
+ * owns a T x Kp buffer of C in the context's type, Kp x Kp doubles of Q (and a copy in the context's type), (4 + Kp / 128) T doubles
+ * per-row state and m x Kp doubles of the u_l for its duration; it shares scfgp_condition's Gram slabs.
+ * Guarantees: the picks of a call with m1 < m2 are a prefix of those with m2, bit for bit, in idx, red and var.  With an explicit Xr,
+ * appending pool rows of weight 0 changes no bit of idx, red, var, or std_after of the original rows: a_i, s_i and z_i depend on row i,
+ * Kp and Q only (a_i^(0) is the sum of its Kp / 128 column-tile shares in tile order; s_i and z_i have scfgp_select's summation order).
+ * With Xr == NULL the appended rows enter Q, so nothing is claimed.  C and the product C Q of the start values run in the context's
+ * precision (SCFGP_F16X3 contexts run fp32 mode's kernels and agree with it bit for bit; the weights omega are rounded to fp32 by fp32
+ * mode's Gram); Q is summed over the chunks in fp64, and a, d, h, g, v and every sum over k of the picks are fp64.  Nothing returns to
+ * the host between picks.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) as scfgp_select, and for a negative wr, an all-zero wr, R < 1 with
+ * Xr given, or K above the bound; SCFGP_ENONFINITE for non-finite rows, weights or factors: the outputs are untouched in both cases.
+ * Out of scope: a row-sharded pool or reference, raw-y units, factors or Q kept on the device between calls, continuous optimisation of
+ * the candidate, K above the LDS bound. */
+int scfgp_select_iv(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* wr,
+                    const double* Li, int m, int mode, int64_t* idx, double* red, double* var, double* ivar, double* std_after);
 
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded

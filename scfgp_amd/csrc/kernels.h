@@ -335,3 +335,19 @@ template <typename T> void select_init(const SelectBufs& b, const T* C, hipStrea
 template <typename T> void select_step(const SelectBufs& b, const T* C, int j, const Scal* sc, hipStream_t st);
 // sd[i] = sqrt(kappa (1 + d[i]))
 void select_std(const SelectBufs& b, const Scal* sc, double* sd, hipStream_t st);
+
+// ---- select.hip: the integrated-variance criterion (scfgp_select_iv) ------------------------------------------------------------------
+// Beside SelectBufs: Q (Kp x Kp fp64, symmetric: C_R^T diag(omega) C_R of the reference rows), a (Trows: the running c_i^T P Q P c_i),
+// apart (select_iv_tiles(Kp) x Trows: the column-tile shares of the start values), h, v (Kp each), red (m), ivar (2: kappa tr(Q), and that minus
+// the reductions so far).  SelectBufs::flag bit 0 also reports a non-finite start value.
+struct SelectIvBufs {
+    const double* Q;
+    double *a, *apart, *h, *v, *red, *ivar;
+};
+int select_iv_tiles(int Kp);                                      // column tiles of the start values' product: the rows of apart
+// d = rowsum(C^2), a = rowsum((C Qt) o C) (Qt: Q in C's type, K live columns), ivar, and the first argmax partials of w a / (1 + d)
+template <typename T>
+void select_iv_init(const SelectBufs& b, const SelectIvBufs& iv, const T* C, const T* Qt, int K, const Scal* sc, hipStream_t st);
+// pick j: idx[j], var[j], u_j as select_step; red[j] = kappa u_j . Q u_j, ivar[1] -= red[j]; then the sweep that downdates a and d and
+// leaves the next partials
+template <typename T> void select_iv_step(const SelectBufs& b, const SelectIvBufs& iv, const T* C, int j, const Scal* sc, hipStream_t st);

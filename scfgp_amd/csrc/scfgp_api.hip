@@ -749,6 +749,23 @@ template <typename T> struct Impl {
     }
     static void pick_init(scfgp_ctx* c, const SelectBufs& b, const void* C) { select_init<T>(b, (const T*)C, c->st); }
     static void pick(scfgp_ctx* c, const SelectBufs& b, const void* C, int j) { select_step<T>(b, (const T*)C, j, c->d_sc, c->st); }
+    // scfgp_select_iv: packed lower tiles of C^T diag(w) C of a chunk (w == NULL: C^T C) into `out`, by the Gram tiles update_chunk
+    // uses, with the update's slabs (fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs: never the fp16 split)
+    static int iv_gram_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const void* C, const double* w, double* out) {
+        const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
+        double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
+        SK::gram(g, (const T*)C, w, nullptr, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
+        reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    static void iv_init(scfgp_ctx* c, const SelectBufs& b, const SelectIvBufs& iv, const void* C, void* Qt) {
+        SK::convert(iv.Q, (T*)Qt, c->g.K, c->g.Kp, c->st);
+        select_iv_init<T>(b, iv, (const T*)C, (const T*)Qt, c->g.K, c->d_sc, c->st);
+    }
+    static void iv_pick(scfgp_ctx* c, const SelectBufs& b, const SelectIvBufs& iv, const void* C, int j) {
+        select_iv_step<T>(b, iv, (const T*)C, j, c->d_sc, c->st);
+    }
     // workgroups per row split of the Gram launch on the context's geometry (update_splits)
     static int gram_jobs(const scfgp_ctx* c) { return SK::gram_jobs(c->g); }
     // scfgp_condition: C = Phi_n Li^T with the update's own factor and alpha (u_LiT, u_vec), the residual r = y - Phi_n alpha, then
@@ -1886,6 +1903,159 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
     if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
     if (gain) HIPCHK(c, hipMemcpyAsync(gain, b.gain, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// greedy choice of m pool rows by integrated variance reduction (select.hip; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int SELECT_IV_MAX_KP = 4096;                     // u_j and v live in LDS as fp64: 64 KB
+// scfgp_select's pipeline with one more product per chunk: the chunks of the reference rows (their weights travel as the feed's
+// targets) go C = Phi_r Li^T -> packed C^T diag(omega) C, summed in fp64 over the chunks into Q; with Xr == NULL the pool's own chunks
+// do, in the pass that fills the pool's C.  Then d, a = rowsum((C Q) o C) and m picks of eager launches (select.hip); the host waits
+// once before the picks (for the non-finite flags) and once after them.
+extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* wr,
+                               const double* Li, int m, int mode, int64_t* idx, double* red, double* var, double* ivar, double* std_after) {
+    if (!c) return SCFGP_EARG;
+    if (!Xc || !Li || !idx || mode < 0 || mode > 1) { c->err = "select_iv: bad arguments"; return SCFGP_EARG; }
+    if (T < 1 || T > SELECT_MAX_T) { c->err = "select_iv: T must lie in 1..1048576"; return SCFGP_EARG; }
+    if (m < 1 || m > SELECT_MAX_M) { c->err = "select_iv: m must lie in 1..4096"; return SCFGP_EARG; }
+    if (Xr && R < 1) { c->err = "select_iv: R must be at least 1"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "select_iv: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "select_iv: parameters not set"; return SCFGP_EARG; }
+    if (c->g.Kp > SELECT_IV_MAX_KP) { c->err = "select_iv: K above 4096 is not supported"; return SCFGP_EARG; }
+    const int64_t Rn = Xr ? R : T;
+    bool nonfinite = false;
+    int64_t eligible = T;
+    if (w) {
+        eligible = 0;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "select_iv: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) ++eligible;
+        }
+    }
+    if (wr) {
+        bool positive = false;
+        for (int64_t i = 0; i < Rn; ++i) {
+            if (wr[i] < 0.0) { c->err = "select_iv: negative reference weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(wr[i])) nonfinite = true;
+            else if (wr[i] > 0.0) positive = true;
+        }
+        if (!nonfinite && !positive) { c->err = "select_iv: no reference row has a positive weight"; return SCFGP_EARG; }
+    }
+    if (nonfinite) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    if (m > eligible) {
+        c->err = "select_iv: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
+        return SCFGP_EARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
+    const size_t ts = c->tsize();
+    const int64_t npool = (T + PRED_ROWS - 1) / PRED_ROWS, nref = Xr ? (R + PRED_ROWS - 1) / PRED_ROWS : 0, njobs = nref + npool;
+    const int64_t nqchunks = (Rn + PRED_ROWS - 1) / PRED_ROWS;
+    // the last chunk's product writes whole 256-row blocks
+    const int64_t Crows = (npool - 1) * PRED_ROWS + round_up(T - (npool - 1) * PRED_ROWS, 256);
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    const int nts = (int)(Kp / g0.tile), ntiles = nts * (nts + 1) / 2;
+    {   // slabs of the widest split among the chunk shapes of the reference rows (full chunks and the ragged last one)
+        size_t need = 0;
+        for (int64_t np : {round_up(std::min<int64_t>(Rn, PRED_ROWS), 256), round_up(Rn - (nqchunks - 1) * PRED_ROWS, 256)})
+            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
+        if ((rc = ensure_update(c, need))) return rc;
+    }
+    RowFeed feed; DevTmp Cbuf, Qbuf, rows, picks;                 // Li / two chunks of [X | omega] | C | Q, typed Q | per row | per pick
+    Events<1> sd_done;                                            // std_after is computed
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
+    if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = "select_iv: no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
+                 std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)";
+        return SCFGP_EHIP;
+    }
+    if ((rc = dmalloc(c, &Qbuf.p, (sizeof(double) + ts) * K2))) return rc;
+    const int npart = select_partials(T), nlchunk = (m + 63) / 64;
+    const int64_t npp = round_up(npart, 8), mp = round_up(m, 8), nat = select_iv_tiles((int)Kp);   // nat: the rows of apart
+    if ((rc = dmalloc(c, &rows.p, sizeof(double) * ((4 + nat) * T + 2 * npp)))) return rc;
+    if ((rc = dmalloc(c, &picks.p, sizeof(double) * ((int64_t)m * Kp + 3 * Kp + (int64_t)nlchunk * Kp + 5 * mp + 16)))) return rc;
+    SelectBufs b; SelectIvBufs iv;
+    b.Kp = (int)Kp; b.Trows = T;
+    b.w = rows; b.d = rows + T; double* d_sd = rows + 2 * T; iv.a = rows + 3 * T; iv.apart = rows + 4 * T;
+    b.pval = rows + (4 + nat) * T; b.pidx = (long long*)(b.pval + npp);
+    b.U = picks; b.cp = b.U + (int64_t)m * Kp; iv.h = b.cp + Kp; iv.v = iv.h + Kp; b.part = iv.v + Kp; b.a = b.part + (int64_t)nlchunk * Kp;
+    b.idx = (long long*)(b.a + mp); b.var = b.a + 2 * mp; b.gain = b.a + 3 * mp; iv.red = b.a + 4 * mp; iv.ivar = b.a + 5 * mp;
+    b.flag = (int*)(iv.ivar + 8);                                 // [0]: select.hip's bits, [1]: update_check_finite's
+    iv.Q = Qbuf;
+    void* Qt = (void*)(Qbuf.p + K2);
+    HIPCHK(c, hipMemsetAsync(Cbuf.p, 0, ts * Crows * Kp, c->st));   // the product leaves the padding columns K.. as they are: zero
+    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
+    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
+    else select_ones(b.w, T, c->st);
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    if ((rc = sd_done.create(c))) return rc;
+    // jobs 0 .. nref - 1: the chunks of the reference rows; then the pool's
+    auto rows_of = [&](int64_t job) {
+        return job < nref ? std::min<int64_t>(PRED_ROWS, R - job * PRED_ROWS) : std::min<int64_t>(PRED_ROWS, T - (job - nref) * PRED_ROWS);
+    };
+    auto upload = [&](int64_t job) {
+        if (job < nref) return feed.upload(job, Xr + job * PRED_ROWS * g0.D, wr ? wr + job * PRED_ROWS : nullptr, rows_of(job));
+        const int64_t i = job - nref;
+        return feed.upload(job, Xc + i * PRED_ROWS * g0.D, !Xr && wr ? wr + i * PRED_ROWS : nullptr, rows_of(job));
+    };
+    if ((rc = upload(0))) return rc;
+    int64_t nq = 0;                                               // chunks summed into Q so far
+    for (int64_t job = 0; job < njobs; ++job) {
+        const Geom g = chunk_geom(g0, rows_of(job));
+        const bool in_q = job < nref || !Xr, weighted = in_q && wr;
+        const double *x, *om;
+        if ((rc = feed.acquire(job, &x, &om))) return rc;
+        pack_data(g, x, weighted ? om : nullptr, nullptr, c->p_Xt, weighted ? c->u_y : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(job))) return rc;
+        void* Cj = job < nref ? c->p_C : (void*)((char*)Cbuf.p + ts * (size_t)((job - nref) * PRED_ROWS) * Kp);
+        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, Cj))) return rc;
+        if (in_q) {
+            if ((rc = DISPATCH(c, iv_gram_chunk, c, g, update_splits(c, g.Np), Cj, weighted ? c->u_y : nullptr, nq == 0 ? c->u_acc : c->u_part)))
+                return rc;
+            if (nq > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk, c->st);
+            ++nq;
+        }
+        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
+    }
+    // non-finite reference rows have reached Q by now; the pool's show in d and a
+    update_check_finite(c->u_acc, c->n_pk, b.flag, c->st);
+    unpack_tri_tiles(c->u_acc, nts, g0.tile, Qbuf, Kp, c->st);
+    DISPATCH(c, iv_init, c, b, iv, Cbuf.p, Qt);
+    HIPCHK(c, hipGetLastError());
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, b.flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (flags[0] || flags[1]) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    for (int j = 0; j < m; ++j) DISPATCH(c, iv_pick, c, b, iv, Cbuf.p, j);
+    HIPCHK(c, hipGetLastError());
+    if (std_after) {
+        select_std(b, c->d_sc, d_sd, c->st);
+        HIPCHK(c, hipEventRecord(sd_done.e[0], c->st));
+    }
+    HIPCHK(c, hipMemcpyAsync(flags, b.flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (flags[0] || flags[1]) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    if (std_after) {
+        HIPCHK(c, hipStreamWaitEvent(c->copy_st, sd_done.e[0], 0));
+        HIPCHK(c, hipMemcpyAsync(std_after, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->copy_st));
+    }
+    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
+    if (red) HIPCHK(c, hipMemcpyAsync(red, iv.red, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    if (ivar) HIPCHK(c, hipMemcpyAsync(ivar, iv.ivar, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SCFGP_OK;

@@ -609,6 +609,54 @@ class HipEngine(object):
         self._check(rc, 'select')
         return (idx, var, gain, sd) if return_std else (idx, var, gain)
 
+    def select_iv(self, Xc, Li, m, Xr=None, w=None, wr=None, raw=False, return_std=False):
+        """Greedy choice of m rows from the pool Xc by integrated variance reduction (include/scfgp_hip.h: scfgp_select_iv): (idx (m,)
+        int64, red (m,), var (m,), ivar (2,)) and, with return_std, std_after (T,).  Pick j is the row whose observation most reduces
+        sum_r wr_r Var[f(Xr_r)] given the picks before it; red[j] is that reduction, var[j] the posterior variance of f at the pick
+        when it was picked, ivar = (integrated variance before the picks, after them), all in scaled-y units, noise excluded.  Xr
+        None: the pool is its own reference (wr then has T entries).  w (T,): non-negative weights of the criterion, 0 excludes a row;
+        wr: non-negative weights of the reference rows.  raw: unscaled Xc and Xr through the registered X scaler."""
+        cols = getattr(self, '_xcols', None) if raw else None
+        if raw and cols is None:
+            raise ValueError('select_iv: raw rows need a registered X scaler (set_x_scaler)')
+
+        def rows_of(X, name):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim != 2:
+                raise TypeError('%s must be a 2-d float64 array' % name)
+            if cols is not None:
+                X = X[:, cols]
+            X = np.ascontiguousarray(X)
+            if X.shape[1] != self.D:
+                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
+            return X
+
+        def weights_of(v, n, name):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if v.size != n:
+                raise ValueError('%s has %d entries for %d rows' % (name, v.size, n))
+            return v
+        Xc = rows_of(Xc, 'Xc')
+        T = Xc.shape[0]
+        Xr = None if Xr is None else rows_of(Xr, 'Xr')
+        R = T if Xr is None else Xr.shape[0]
+        w = weights_of(w, T, 'w'); wr = weights_of(wr, R, 'wr')
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if Li.shape != (self.K, self.K):
+            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        m = int(m)
+        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
+        idx = np.empty(n, dtype=np.int64); red = np.empty(n); var = np.empty(n); ivar = np.empty(2)
+        sd = np.empty(T) if return_std else None
+        rc = self.lib.scfgp_select_iv(self.ctx, dptr(Xc), T, dptr(w), dptr(Xr), R, dptr(wr), dptr(Li), m, int(bool(raw)),
+                                      idx.ctypes.data_as(_lib._c_i64_p), dptr(red), dptr(var), dptr(ivar), dptr(sd))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('select_iv: %s' % self.last_error())
+        self._check(rc, 'select_iv')
+        return (idx, red, var, ivar, sd) if return_std else (idx, red, var, ivar)
+
     def last_error(self):
         """Message of the last failure -- or refusal (a precision level whose buffers could not be had) -- on this context."""
         return self.lib.scfgp_last_error(self.ctx).decode()

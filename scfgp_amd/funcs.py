@@ -323,6 +323,14 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.select(X_raw, Li, m, w=weights, raw=True, return_std=return_std)
 
+    def select_iv_raw(self, X_raw, x_scaler, Li, m, Xr_raw=None, weights=None, ref_weights=None, return_std=False):
+        """Greedy choice of m of the raw pool rows X_raw by integrated variance reduction over the raw reference rows Xr_raw (None: the
+        pool itself) under the posterior with factor Li, at the shared parameter vector: (idx, red, var, ivar[, std_after]) in scaled-y
+        units, raw rows through the X scaler on the device (engine.select_iv)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.select_iv(X_raw, Li, m, Xr=Xr_raw, w=weights, wr=ref_weights, raw=True, return_std=return_std)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

@@ -350,6 +350,20 @@ class SCFGP(object):
         idx, var, gain = owner.select_raw(X_pool, self.X_scaler, self.Li, m, weights=weights)
         return idx, np.sqrt(var), gain
 
+    def select_iv(self, X_pool, m, X_ref=None, weights=None, ref_weights=None):
+        """Which m rows of the raw pool X_pool (T,D) to observe next so that the model is most certain over X_ref (R,D; None: the
+        pool itself): (idx (m,) indices into the pool in the order they are picked, red (m,), ivar (2,)).  Pick j is the row whose
+        observation most reduces the posterior variance of f summed over the reference rows (times ref_weights), given the training
+        set and the picks before it -- integrated variance reduction (ALC / A-optimal), without targets and without a refit per pick
+        (include/scfgp_hip.h: scfgp_select_iv).  red[j] is the reduction pick j achieved and ivar the summed variance before and
+        after the m picks, in squared scaled-y units (noise excluded).  weights (T,) >= 0 scale the criterion, 0 excludes a row.
+        Pending points: condition(X_pending, any y) on a copy of the model first.  Nothing of the model is touched."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('select_iv needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        idx, red, _, ivar = owner.select_iv_raw(X_pool, self.X_scaler, self.Li, m, Xr_raw=X_ref, weights=weights, ref_weights=ref_weights)
+        return idx, red, ivar
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
