@@ -166,6 +166,36 @@ int scfgp_predict_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double
 int scfgp_sample_weights(scfgp_ctx* ctx, const double* alpha, const double* Li, int nsamp, uint64_t seed, double* W);
 int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp,
                  uint64_t seed, int mode, int noise, double* out);
+/* scfgp_sample_argmax: for each of nsamp sample functions, the pool row that maximises it and its value there -- Thompson sampling, and
+ * the sampled maxima f* of max-value entropy search and "probability of being the best row".  The sample functions are scfgp_sample's:
+ * the same generator, W and seed contract.  With out[t][s] what scfgp_sample(..., noise = 0) returns for these rows in mode
+ * min(mode, 1), and row t eligible iff w == NULL or w[t] > 0:
+ *     idx[s] = the lowest eligible t at which out[t][s] is largest (minimize != 0: smallest)        val[s] = out[idx[s]][s], bit for bit
+ * val may be NULL, idx may not.  There is no noise argument: the maximiser of a noisy draw means nothing.  w (T, may be NULL = every row
+ * is eligible) has scfgp_select's meaning "0 excludes"; positive values are not multiplied in.  mode 0: scaled rows; 1: column-selected
+ * raw rows through the registered X scaler; 2: mode 1, and val[s] is the y scaler's backward transform of the mode-1 value by the device
+ * function scfgp_sample mode 2 applies (equal bits; with the inv-normal y scalers it may be non-finite, as there), while idx is chosen in
+ * scaled units and equals mode 1's.
+ * The product Phi* W is scfgp_sample's kernel with a second epilogue: its feature loop, its fp64 folding of the fp32 accumulators and its
+ * launch plan are shared, so every value has scfgp_sample's bits, and nothing of size T x nsamp is written anywhere.  Each workgroup
+ * reduces its rows to one (value, row) record per sample, and one thread per sample merges the records into a running best that stays on
+ * the device across chunks.  One rule at every level: record a = (v, t) beats b iff key(a) > key(b), or the keys are equal and
+ * a.t < b.t, with key = v, or -v when minimising (exact).  On the eligible records that is a total order, so the result does not depend
+ * on how the records are grouped: lanes, waves, workgroups, column-tile launches or chunks.
+ * Bounds: 1 <= nsamp <= 1024; T >= 1 without limit: the rows go through in chunks, and device memory holds the per-workgroup records of
+ * two chunks, never a T x nsamp buffer.
+ * Guarantees: idx[s] and val[s] do not depend on nsamp (a call with fewer samples returns a prefix).  A value depends on its row only
+ * and ties go to the lowest index, so appending rows, or duplicating rows later in the pool, changes nothing.  SCFGP_F16X3 contexts run
+ * fp32 mode's kernels and agree with it bit for bit.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xs, alpha, Li or idx, T < 1, nsamp out of range, a bad
+ * mode, a missing X scaler (modes 1, 2) or y scaler (mode 2), parameters not set, a negative w, or no row with w > 0; SCFGP_ENONFINITE for
+ * a non-finite w, and for a non-finite value of an eligible row in any sample (a non-finite row with w = 0 is not an error): the outputs
+ * are untouched in both cases.  Row-sharded use needs no communicator: each rank calls it on its rows and the caller merges the
+ * (val, idx + offset) pairs by the rule above (for mode 2, merge mode-1 values and transform afterwards, or rely on the transform being
+ * monotone).  Out of scope: top-k per sample, continuous optimisation of the maximiser, and weights or factors kept on the device
+ * between calls. */
+int scfgp_sample_argmax(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
+                        uint64_t seed, int mode, int minimize, int64_t* idx, double* val);
 
 /* ---- joint posterior covariance between test points (no reference counterpart: the reference reports the marginals only) -------
  * Under the weight posterior w ~ N(alpha, kappa A^-1) above, two function values have covariance kappa phi(x)^T A^-1 phi(x'); with

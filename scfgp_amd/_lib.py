@@ -42,6 +42,8 @@ SIGNATURES = {
     'scfgp_sample_weights': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int, C.c_uint64, _c_double_p]),
     'scfgp_sample': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                _c_double_p]),
+    'scfgp_sample_argmax': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_uint64, C.c_int,
+                                      C.c_int, _c_i64_p, _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_loo': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p,
@@ -90,7 +92,10 @@ def load():
             "scfgp_amd: %s not found. The HIP extension is the product path and has no "
             "fallback; build it with `make -C scfgp_amd/csrc` (or __graft_entry__.build())." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
+    variant = os.environ.get('SCFGP_LIB_VARIANT', '')
     for name, (res, args) in SIGNATURES.items():
+        if variant and not hasattr(lib, name):
+            continue                     # an A/B build of an older commit (tools/posterior_ab.py) lacks newer entry points: calling one raises
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

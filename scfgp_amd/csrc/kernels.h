@@ -254,6 +254,20 @@ void sample_weights(const Geom& g, const double* Li, const double* alpha, const 
 template <typename T>
 void sample_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode, const double* ysp,
                     const Scal* sc, double* out, hipStream_t st);
+// scfgp_sample_argmax: the product's workgroups cover sample_block_rows rows each and leave one record per sample column
+constexpr int sample_block_rows(size_t tsize) { return tsize == 4 ? 128 : 64; }
+inline int64_t sample_blocks(int64_t Np, size_t tsize) { return Np / sample_block_rows(tsize); }
+// pv, pt: the records of one chunk's workgroups (sample_blocks x nsamp: value, chunk-local row or -1 for none); bestv, bestt (nsamp): the
+// running best over the chunks so far (value, row index in the call's Xs); flag: set where an eligible row's value is not finite
+struct SampleArgmaxBufs { double* pv; long long* pt; double* bestv; long long* bestt; int* flag; };
+// Phi Wt as sample_product forms it, reduced per sample column in the product's epilogue: over the rows n < N with w[n] > 0 (w == NULL:
+// all; w: Np entries) the largest value (minimize: the smallest), ties to the lowest row; then the chunk's records are merged into
+// bestv / bestt with rows counted from t0 (`first`: the running best starts empty)
+template <typename T>
+void sample_argmax_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, const double* w, int minimize, int64_t t0, int first,
+                           const SampleArgmaxBufs& b, hipStream_t st);
+// bestv (nsamp) <- the y scaler's backward transform of mode ymode, by the kernel sample_product applies it with
+void sample_argmax_finalize(double* bestv, int nsamp, int ymode, const double* ysp, const Scal* sc, hipStream_t st);
 
 // ---- predcov.hip, joint posterior covariance between test points (scfgp_predict_cov) ---------------------------------------------------
 // out[n][j] (n < nrows, j < Tb; row-major, leading dimension Tb, fp64) = kappa sum_k Ca[n][k] Cb[j][k] over the K features, + kappa

@@ -15,6 +15,9 @@
 // Kernels: Z from the generator; W = alpha 1^T + sqrt(kappa) Li^T Z in fp64 (LDS tiles, the triangle of Li only) with its typed copy;
 // per chunk of test rows Out = Phi* W on the matrix pipe (fp64 MFMA in fp64 contexts, exact fp32 MFMA with fp64 partial sums
 // otherwise) and an fp64 epilogue (observation noise, the y scaler's backward transform).
+// scfgp_sample_argmax: the same product with a second epilogue that keeps, per sample column, the best (value, row) of the workgroup's
+// rows instead of storing the block; sample_argmax_merge_kernel folds the workgroups' records into a running best across chunks.
+#include <type_traits>
 #include "kernels.h"
 #include "tile_engine.h"
 #include "yscale.h"
@@ -124,10 +127,37 @@ __device__ __forceinline__ void load_row4(const double* __restrict__ p, double (
 // the accumulators are added into fp64 partial sums every SAMPLE_FLUSH features (exact fp32 products, fp32 sums over 128 features
 // only).  out: the chunk's N x nsamp block, row-major, in fp64; noise and the y scaler follow in sample_post_kernel (in the product's
 // own epilogue the generator and the transform cost the main loop its registers).
+// Out selects the epilogue: double* is that store; SampleArgmaxOut is scfgp_sample_argmax's reduction (below).  The main loop is the
+// same text for both, so the value of an element is the same bits in both.
 constexpr int SAMPLE_FLUSH = 128;
-template <typename T, int NST>
+
+// One merge rule for every level of scfgp_sample_argmax (lanes, waves, workgroups, column-tile launches, chunks; ranks on the caller's
+// side): record a = (v, t) beats b iff key(a) > key(b), or the keys are equal and a.t < b.t; key = v, or -v when minimising (exact).
+// t < 0 marks the empty record, which loses to everything.  On records with finite values the rule is a total order, so the winner
+// does not depend on how the records are grouped.
+__device__ __forceinline__ bool argmax_beats(double va, long long ta, double vb, long long tb, bool minimize) {
+    if (ta < 0) return false;
+    if (tb < 0) return true;
+    const double ka = minimize ? -va : va, kb = minimize ? -vb : vb;
+    return ka > kb || (ka == kb && ta < tb);
+}
+// the argmax epilogue's destination: w the chunk's weights (NULL: every row is eligible; row n is eligible iff w[n] > 0), pv / pt the
+// workgroups' records ([gridDim.x][nsamp]: value, chunk-local row or -1), flag set where an eligible row's value is not finite
+struct SampleArgmaxOut {
+    const double* w;
+    double* pv;
+    long long* pt;
+    int* flag;
+    int minimize;
+};
+
+// the kernel's last parameter: the store epilogue keeps its restrict qualifier
+template <typename Out> struct SampleDst { typedef Out type; };
+template <> struct SampleDst<double*> { typedef double* __restrict__ type; };
+
+template <typename T, int NST, typename Out>
 __global__ __launch_bounds__(256) void sample_fw_kernel(const T* __restrict__ Phi, const T* __restrict__ Wt, int ldw, int s0, int Kq, int Kp,
-                                                        int64_t N, int nsamp, double* __restrict__ out) {
+                                                        int64_t N, int nsamp, typename SampleDst<Out>::type dst) {
     typedef MT<T, 16> M;
     constexpr bool F32 = sizeof(T) == 4;
     constexpr int TM = F32 ? 2 : 1;
@@ -167,17 +197,91 @@ __global__ __launch_bounds__(256) void sample_fw_kernel(const T* __restrict__ Ph
                     for (int r = 0; r < 4; ++r) { part[tm][tn][r] += (double)acc[tm][tn][r]; acc[tm][tn][r] = 0; }
         }
     }
+    if constexpr (std::is_same<Out, double*>::value) {
+        double* __restrict__ out = dst;                           // scfgp_sample's store, unchanged
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
+        for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t n = row0 + tm * 16 + M::crow(lane, r);
+            for (int r = 0; r < 4; ++r) {
+                const int64_t n = row0 + tm * 16 + M::crow(lane, r);
 #pragma unroll
-            for (int tn = 0; tn < NST; ++tn) {
-                const int s = s0 + tn * 16 + i;
-                if (n < N && s < nsamp) out[n * nsamp + s] = F32 ? part[tm][tn][r] : (double)acc[tm][tn][r];
+                for (int tn = 0; tn < NST; ++tn) {
+                    const int s = s0 + tn * 16 + i;
+                    if (n < N && s < nsamp) out[n * nsamp + s] = F32 ? part[tm][tn][r] : (double)acc[tm][tn][r];
+                }
             }
+    } else {
+        // the lane's 4 TM rows of each column tile -> the four q-groups of a column (lanes i, i + 16, i + 32, i + 48) by shuffles -> the
+        // four waves through LDS -> one record per column of the workgroup
+        const bool mini = dst.minimize != 0;
+        __shared__ double sv[4][16 * NST];
+        __shared__ long long sl[4][16 * NST];
+        bool eligible[TM][4];
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t n = row0 + tm * 16 + M::crow(lane, r);
+                eligible[tm][r] = n < N && (!dst.w || dst.w[n] > 0.0);
+            }
+        bool bad = false;
+#pragma unroll
+        for (int tn = 0; tn < NST; ++tn) {                          // one column tile at a time: one record live per lane
+            const bool live = s0 + tn * 16 + i < nsamp;
+            double bv = 0.0;
+            long long bt = -1;
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = F32 ? part[tm][tn][r] : (double)acc[tm][tn][r];
+                    const long long n = row0 + tm * 16 + M::crow(lane, r);
+                    if (eligible[tm][r] && live) {
+                        bad |= !isfinite(v);
+                        if (argmax_beats(v, n, bv, bt, mini)) { bv = v; bt = n; }
+                    }
+                }
+#pragma unroll
+            for (int off = 16; off <= 32; off <<= 1) {
+                const double ov = __shfl_xor(bv, off);
+                const long long ot = __shfl_xor(bt, off);
+                if (argmax_beats(ov, ot, bv, bt, mini)) { bv = ov; bt = ot; }
+            }
+            if (q == 0) { sv[wave][tn * 16 + i] = bv; sl[wave][tn * 16 + i] = bt; }
         }
+        __syncthreads();
+        const int col = threadIdx.x, s = s0 + col;
+        if (col < 16 * NST && s < nsamp) {
+            double v = sv[0][col];
+            long long t = sl[0][col];
+#pragma unroll
+            for (int wv = 1; wv < 4; ++wv)
+                if (argmax_beats(sv[wv][col], sl[wv][col], v, t, mini)) { v = sv[wv][col]; t = sl[wv][col]; }
+            dst.pv[(int64_t)blockIdx.x * nsamp + s] = v;
+            dst.pt[(int64_t)blockIdx.x * nsamp + s] = t;
+        }
+        if (bad) *dst.flag = 1;
+    }
+}
+
+// One thread per sample column folds the chunk's workgroup records, in block order, into the running best (bestv, bestt: value, row
+// index in the call's Xs) that stays on the device across chunks; `first`: the running best starts empty.  t0: the chunk's first row.
+__global__ __launch_bounds__(256) void sample_argmax_merge_kernel(const double* __restrict__ pv, const long long* __restrict__ pt, int nblocks,
+                                                                  int nsamp, int64_t t0, int first, int minimize, double* __restrict__ bestv,
+                                                                  long long* __restrict__ bestt) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nsamp) return;
+    const bool mini = minimize != 0;
+    double v = first ? 0.0 : bestv[s];
+    long long t = first ? -1 : bestt[s];
+#pragma unroll 8
+    for (int b = 0; b < nblocks; ++b) {
+        const double cv = pv[(int64_t)b * nsamp + s];
+        const long long cl = pt[(int64_t)b * nsamp + s], ct = cl < 0 ? -1 : t0 + cl;
+        if (argmax_beats(cv, ct, v, t, mini)) { v = cv; t = ct; }
+    }
+    bestv[s] = v;
+    bestt[s] = t;
 }
 
 // the epilogue of the product, in place on the chunk's N x nsamp block (fp64): + sqrt(kappa) eps[t0 + n][s] (noise), then the y scaler's
@@ -202,25 +306,43 @@ template <typename T> static int sample_tiles(int rem) {
     return rem >= top ? top : (rem >= 4 ? 4 : (rem >= 2 ? 2 : 1));
 }
 
-template <typename T>
-void sample_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode, const double* ysp,
-                    const Scal* sc, double* out, hipStream_t st) {
-    constexpr int ROWS = 4 * 16 * (sizeof(T) == 4 ? 2 : 1);            // rows per workgroup: Np (a multiple of 256) is covered exactly
-    const dim3 grid((unsigned)(g.Np / ROWS));
+// the launch plan of Phi* W, shared by both epilogues (dst: double* or SampleArgmaxOut)
+template <typename T, typename Out>
+static void sample_launches(const Geom& g, const T* Phi, const T* Wt, int nsamp, Out dst, hipStream_t st) {
+    static_assert(sample_block_rows(sizeof(T)) == 4 * 16 * (sizeof(T) == 4 ? 2 : 1), "rows per workgroup: 4 waves x 16 TM");
+    const dim3 grid((unsigned)sample_blocks(g.Np, sizeof(T)));          // Np (a multiple of 256) is covered exactly
     const int ldw = sample_w_cols(nsamp), Kq = (int)round_up(g.K, 16);
     for (int rem = (nsamp + 15) / 16, s0 = 0; rem > 0;) {
         const int p = sample_tiles<T>(rem);
         const auto args = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, Phi, Wt, ldw, s0, Kq, g.Kp, g.N, nsamp, out);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, Phi, Wt, ldw, s0, Kq, g.Kp, g.N, nsamp, dst);
         };
-        if (p == 8) args(sample_fw_kernel<T, sizeof(T) == 4 ? 4 : 8>);           // p == 8 in fp64 only
-        else if (p == 4) args(sample_fw_kernel<T, 4>);
-        else if (p == 2) args(sample_fw_kernel<T, 2>);
-        else args(sample_fw_kernel<T, 1>);
+        if (p == 8) args(sample_fw_kernel<T, sizeof(T) == 4 ? 4 : 8, Out>);      // p == 8 in fp64 only
+        else if (p == 4) args(sample_fw_kernel<T, 4, Out>);
+        else if (p == 2) args(sample_fw_kernel<T, 2, Out>);
+        else args(sample_fw_kernel<T, 1, Out>);
         s0 += 16 * p; rem -= p;
     }
+}
+
+template <typename T>
+void sample_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode, const double* ysp,
+                    const Scal* sc, double* out, hipStream_t st) {
+    sample_launches<T>(g, Phi, Wt, nsamp, out, st);
     if (noise || ymode >= 0)
         hipLaunchKernelGGL(sample_post_kernel, dim3(2048), dim3(256), 0, st, out, g.N * nsamp, nsamp, t0, seed, noise, ymode, ysp, sc);
+}
+
+template <typename T>
+void sample_argmax_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, const double* w, int minimize, int64_t t0, int first,
+                           const SampleArgmaxBufs& b, hipStream_t st) {
+    sample_launches<T>(g, Phi, Wt, nsamp, SampleArgmaxOut{w, b.pv, b.pt, b.flag, minimize}, st);
+    hipLaunchKernelGGL(sample_argmax_merge_kernel, dim3((unsigned)((nsamp + 255) / 256)), dim3(256), 0, st, b.pv, b.pt,
+                       (int)sample_blocks(g.Np, sizeof(T)), nsamp, t0, first, minimize, b.bestv, b.bestt);
+}
+// the y scaler's backward transform of the nsamp winning values, by the kernel that applies it to scfgp_sample's block: the same bits
+void sample_argmax_finalize(double* bestv, int nsamp, int ymode, const double* ysp, const Scal* sc, hipStream_t st) {
+    hipLaunchKernelGGL(sample_post_kernel, dim3(4), dim3(256), 0, st, bestv, (int64_t)nsamp, nsamp, (int64_t)0, (uint64_t)0, 0, ymode, ysp, sc);
 }
 
 template void sample_weights<double>(const Geom&, const double*, const double*, const Scal*, int, uint64_t, double*, double*, double*, hipStream_t);
@@ -229,3 +351,7 @@ template void sample_product<double>(const Geom&, const double*, const double*, 
                                      double*, hipStream_t);
 template void sample_product<float>(const Geom&, const float*, const float*, int, int64_t, uint64_t, int, int, const double*, const Scal*,
                                     double*, hipStream_t);
+template void sample_argmax_product<double>(const Geom&, const double*, const double*, int, const double*, int, int64_t, int,
+                                            const SampleArgmaxBufs&, hipStream_t);
+template void sample_argmax_product<float>(const Geom&, const float*, const float*, int, const double*, int, int64_t, int,
+                                           const SampleArgmaxBufs&, hipStream_t);

@@ -805,6 +805,14 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_sample_argmax: the same product, reduced per sample column in its epilogue and merged into the call's running best
+    static int sample_argmax_chunk(scfgp_ctx* c, const Geom& g, const void* Wt, int nsamp, const double* w, int minimize, int64_t t0,
+                                   const SampleArgmaxBufs& b) {
+        features(c, g);
+        sample_argmax_product<T>(g, (const T*)c->p_Phi, (const T*)Wt, nsamp, w, minimize, t0, t0 == 0, b, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
 };
 
 #define DISPATCH(c, fn, ...) ((c)->dtype == SCFGP_F32 ? Impl<float>::fn(__VA_ARGS__) : Impl<double>::fn(__VA_ARGS__))
@@ -1191,8 +1199,8 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 }
 
 // ----------------------------------------------------------------------------------------------
-// the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_predict_cov, scfgp_condition, scfgp_loo
-// and scfgp_select
+// the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
+// scfgp_condition, scfgp_loo and scfgp_select
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -1511,6 +1519,70 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     HIPCHK(c, hipGetLastError());
+    return SCFGP_OK;
+}
+
+// scfgp_sample's pipeline without the OutRing: the weights w travel as the feed's targets and reach the product's epilogue through
+// pack_data's zero-padded copy; per chunk the workgroups' records (two slots, alternating) are merged into nsamp running (value, row)
+// pairs on the device, which are all that the host fetches, once, with the non-finite flag.  w is checked on the host before any device
+// work, as scfgp_select does.
+extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
+                                   uint64_t seed, int mode, int minimize, int64_t* idx, double* val) {
+    if (!c) return SCFGP_EARG;
+    int rc;
+    if ((rc = sample_check(c, Xs && alpha && Li && idx && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_argmax"))) return rc;
+    if (mode >= 1 && !c->d_xscale) { c->err = "sample_argmax: no X scaler set"; return SCFGP_EARG; }
+    if (mode == 2 && !c->d_yscale) { c->err = "sample_argmax: no y scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "sample_argmax: parameters not set"; return SCFGP_EARG; }
+    if (w) {
+        bool nonfinite = false, positive = false;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "sample_argmax: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) positive = true;
+        }
+        if (nonfinite) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+        if (!positive) { c->err = "sample_argmax: no row has a positive weight"; return SCFGP_EARG; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    SampleW sw;
+    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const int64_t nrec = sample_blocks(round_up(std::min<int64_t>(T, PRED_ROWS), 256), c->tsize()) * nsamp;      // records of a chunk
+    RowFeed feed; DevTmp wchunk, rec;                             // two chunks of [Xs | w] | w of the chunk, padded | records, running best, flag
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0))))) return rc;
+    if (w && (rc = dmalloc(c, &wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
+    if ((rc = dmalloc(c, &rec.p, sizeof(double) * (4 * nrec + 2 * nsamp + 1)))) return rc;
+    double* d_bestv = rec + 4 * nrec;
+    long long* d_bestt = (long long*)(d_bestv + nsamp);
+    int* d_flag = (int*)(d_bestv + 2 * nsamp);
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *wraw;
+        if ((rc = feed.acquire(i, &x, &wraw))) return rc;
+        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, wchunk.p, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        const SampleArgmaxBufs b = {rec + (i & 1) * nrec, (long long*)(rec + (2 + (i & 1)) * nrec), d_bestv, d_bestt, d_flag};
+        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, sw.wt.p, nsamp, wchunk.p, minimize, i * PRED_ROWS, b))) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    if (mode == 2 && val) sample_argmax_finalize(d_bestv, nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> h(2 * nsamp + 1);                         // the outputs are written on success only
+    HIPCHK(c, hipMemcpyAsync(h.data(), d_bestv, sizeof(double) * (2 * nsamp + 1), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    int flag;
+    memcpy(&flag, &h[2 * nsamp], sizeof(int));
+    if (flag) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    memcpy(idx, &h[nsamp], sizeof(int64_t) * nsamp);
+    if (val) memcpy(val, h.data(), sizeof(double) * nsamp);
     return SCFGP_OK;
 }
 

@@ -318,6 +318,41 @@ class HipEngine(object):
                                           int(bool(noise)), dptr(out)), 'sample')
         return out
 
+    def sample_argmax(self, Xs, alpha, Li, nsamp, seed=0, w=None, mode='scaled', minimize=False):
+        """Per-sample maximisers over the pool Xs (include/scfgp_hip.h: scfgp_sample_argmax): (idx (nsamp,) int64, val (nsamp,)) with
+        idx[s] the lowest eligible row at which sample function s of `sample` (same seed, no noise) is largest (minimize: smallest)
+        and val[s] its value there, bit for bit what `sample` returns.  w (T,): row t is eligible iff w[t] > 0 (None: every row).
+        mode as in `sample`; with 'y' the row is chosen in scaled units and val is in raw y units."""
+        if mode not in self.SAMPLE_MODES:
+            raise ValueError('sample_argmax: mode must be one of %s' % sorted(self.SAMPLE_MODES))
+        m = self.SAMPLE_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('sample_argmax: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        T = Xs.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        alpha, Li = self._factors(alpha, Li)
+        nsamp = int(nsamp)
+        n = nsamp if 0 < nsamp <= 1024 else 0                   # out of range: the library refuses before it writes
+        idx = np.empty(n, dtype=np.int64); val = np.empty(n)
+        rc = self.lib.scfgp_sample_argmax(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), nsamp, int(seed) & (2 ** 64 - 1), m,
+                                          int(bool(minimize)), idx.ctypes.data_as(_lib._c_i64_p), dptr(val))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('sample_argmax: %s' % self.last_error())
+        self._check(rc, 'sample_argmax')
+        return idx, val
+
     PREDICT_COV_MODES = {'scaled': 0, 'raw': 1}
 
     def predict_cov(self, Xa, Li, Xb=None, mode='scaled', noise=False):

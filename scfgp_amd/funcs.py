@@ -289,6 +289,13 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return self.engine.sample(Xs_raw, alpha, Li, nsamp, seed=seed, mode='y', noise=noise)
 
+    def sample_argmax_y(self, Xs_raw, x_scaler, y_scaler, alpha, Li, nsamp, seed=0, weights=None, minimize=False):
+        """Per-sample maximisers (idx, val) of sample_y's functions over the raw pool rows Xs_raw, val in raw y units
+        (engine.sample_argmax)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, y_scaler)
+        return self.engine.sample_argmax(Xs_raw, alpha, Li, nsamp, seed=seed, w=weights, mode='y', minimize=minimize)
+
     def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
         """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
         self._sync_params()

@@ -276,6 +276,45 @@ class SCFGP(object):
             raise TypeError('sample needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
         return owner.sample_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, noise=noise)
 
+    def sample_argmax(self, X_pool, nsamples, seed=0, weights=None, minimize=False):
+        """For each of nsamples posterior sample functions, the row of the raw pool X_pool (T,D) that maximises it (minimize: minimises
+        it) and its value there: (idx (nsamples,) indices into the pool, val (nsamples,) in raw y units).  The functions are those of
+        sample(X_pool, nsamples, seed): val[s] is sample(...)[idx[s], s] bit for bit, and no T x nsamples block is formed anywhere
+        (include/scfgp_hip.h: scfgp_sample_argmax).  weights (T,): row t is eligible iff weights[t] > 0.  The row is chosen in scaled
+        y units; ties go to the lowest index.  val is a draw of the maximum f* (max-value entropy search), and the share of samples
+        that name a row estimates its probability of being the best."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('sample_argmax needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        return owner.sample_argmax_y(X_pool, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, weights=weights,
+                                     minimize=minimize)
+
+    def thompson(self, X_pool, m, seed=0, weights=None, minimize=False):
+        """Thompson sampling of a batch: m distinct rows of the raw pool X_pool (T,D), row j the maximiser (minimize: minimiser) of
+        posterior sample function j.  It runs in rounds of sample_argmax with nsamples = m fixed, so sample j stays the same function:
+        round 1 is the plain call; among samples that name the same row the lowest-numbered keeps it; every further round masks the
+        rows held so far, calls again and resolves the samples still without a row by the same rule, until all m hold distinct rows.
+        weights (T,): row t is eligible iff weights[t] > 0.  ValueError if m exceeds the number of eligible rows.  Returns idx (m,)
+        int64, the row held by sample 0 .. m-1; observe them and absorb the results with condition(), as with select()."""
+        m = int(m)
+        T = np.asarray(X_pool).shape[0]
+        w = np.ones(T) if weights is None else np.array(weights, dtype=np.float64).reshape(-1)
+        if w.size != T:
+            raise ValueError('thompson: weights has %d entries for %d rows' % (w.size, T))
+        eligible = int(np.count_nonzero(w > 0))
+        if m > eligible:
+            raise ValueError('thompson: m = %d but only %d rows are eligible' % (m, eligible))
+        held = np.full(max(m, 0), -1, dtype=np.int64)
+        first = True
+        while first or (held < 0).any():
+            idx, _ = self.sample_argmax(X_pool, m, seed=seed, weights=None if first and weights is None else w, minimize=minimize)
+            for s in np.flatnonzero(held < 0):                   # ascending: the lowest-numbered sample keeps a contested row
+                if not (held == idx[s]).any():
+                    held[s] = idx[s]
+            w[held[held >= 0]] = 0.0
+            first = False
+        return held
+
     def predict_cov(self, Xs, Xs2=None, noise=False):
         """Joint posterior covariance of the fitted model's function values between the raw rows Xs and Xs2 (None: among the rows of
         Xs, a bit-for-bit symmetric matrix): (T, T2) = kappa phi(x)^T A^-1 phi(x').  Inputs are in raw X units; the covariance is that
