@@ -192,10 +192,38 @@ int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alph
  * a non-finite w, and for a non-finite value of an eligible row in any sample (a non-finite row with w = 0 is not an error): the outputs
  * are untouched in both cases.  Row-sharded use needs no communicator: each rank calls it on its rows and the caller merges the
  * (val, idx + offset) pairs by the rule above (for mode 2, merge mode-1 values and transform afterwards, or rely on the transform being
- * monotone).  Out of scope: top-k per sample, continuous optimisation of the maximiser, and weights or factors kept on the device
- * between calls. */
+ * monotone).  Continuous refinement of a maximiser off the pool: scfgp_sample_grad gives the value and input gradient of a sample
+ * function at any point.  Out of scope: top-k per sample, and weights or factors kept on the device between calls. */
 int scfgp_sample_argmax(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
                         uint64_t seed, int mode, int minimize, int64_t* idx, double* val);
+/* scfgp_sample_grad: values and input gradients of sample functions, one sample per row -- what a gradient method needs to move each
+ * sample's best pool row off the grid (Thompson sampling or max-value entropy search in a continuous domain).
+ *     val[t] = f_s(x_t) = phi(x_t)^T w_s,   grad[t][:] = d f_s / d x at x_t,   s = sidx[t]   (sidx == NULL: s = t % nsamp)
+ * W (K x nsamp, row-major, fp64) is what scfgp_sample_weights returns: column s is w_s in alpha's layout (J cosine features, then J
+ * sine features).  Any K-vectors are allowed: W = alpha with nsamp = 1 gives the mean.  The call takes W, not (alpha, Li, seed): an
+ * optimiser calls it tens of times with the same functions and pays K nsamp doubles of upload per call, never the K x K factor or the
+ * weight kernel.  val (T) may be NULL; grad (T x D, row-major) may not.  This is the paired form (row t belongs to one sample: one
+ * current point per sample, or a few starts per sample); the cross form, every row under every sample, is obtained by repeating rows.
+ * Modes as scfgp_predict_grad: 0 scaled rows; 1 column-selected raw rows through the registered X scaler, grad chained through the
+ * derivative of its forward transform column by column; 2 mode 1, and val = bw(f) by the device function scfgp_sample mode 2 applies,
+ * grad = bw'(f) grad f (bw: the y scaler's backward transform).
+ * Numerics: Phi* in the context's type.  With Zbar_j = phi_c_j w[J + j] - phi_s_j w[j] formed in fp64 from the fp64 weights and rounded
+ * once to the context's type, grad = Zbar F_all^T by fp64 MFMA (fp64 contexts) or exact-fp32 MFMA (SCFGP_F32 and SCFGP_F16X3, which agree
+ * bit for bit): scfgp_predict_grad's loop for dmu with the row's own weights in alpha's place, same feature order and MFMA pairing.
+ * val = sum_j phi_c_j w[j] + phi_s_j w[J + j] is summed in fp64 in one fixed order that depends on J alone; it does not claim
+ * scfgp_sample's bits (in fp32 contexts it is the more accurate of the two: scfgp_sample sums in fp32 MFMA).
+ * Bounds: 1 <= nsamp <= 1024; T >= 1 without limit: the rows go through in chunks and device memory does not grow with T.
+ * Guarantees: a row's val and grad depend on the row, its weight vector and the parameters only, bit for bit -- not on T, the row's
+ * position, the chunk, nsamp or the other samples present.  With nsamp = 1 and W = alpha, mode-0 grad equals scfgp_predict_grad's dmu
+ * bit for bit.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xs, W or grad, T < 1, nsamp out of range, a bad mode, a
+ * missing X scaler (modes 1, 2) or y scaler (mode 2), parameters not set, or an sidx entry outside [0, nsamp) (the text names the first
+ * such row); SCFGP_ENONFINITE for a non-finite W: the outputs are untouched in both cases.  Non-finite rows give non-finite outputs and
+ * no error, as scfgp_sample.
+ * Out of scope: the T x nsamp x D cross form, gradients of noisy draws, Hessians, a device-resident optimiser, weights kept on the
+ * device between calls, a row-sharded form (per-row work: each rank calls it on its own rows). */
+int scfgp_sample_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* W, int nsamp, const int64_t* sidx, int mode,
+                      double* val, double* grad);
 
 /* ---- joint posterior covariance between test points (no reference counterpart: the reference reports the marginals only) -------
  * Under the weight posterior w ~ N(alpha, kappa A^-1) above, two function values have covariance kappa phi(x)^T A^-1 phi(x'); with
@@ -338,8 +366,9 @@ int scfgp_select(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, c
  * the host between picks.  The training state of the context survives.
  * SCFGP_EARG (with a scfgp_last_error text, before any device work) as scfgp_select, and for a negative wr, an all-zero wr, R < 1 with
  * Xr given, or K above the bound; SCFGP_ENONFINITE for non-finite rows, weights or factors: the outputs are untouched in both cases.
- * Out of scope: a row-sharded pool or reference, raw-y units, factors or Q kept on the device between calls, continuous optimisation of
- * the candidate, K above the LDS bound. */
+ * Out of scope: a row-sharded pool or reference, raw-y units, factors or Q kept on the device between calls, K above the LDS bound.
+ * Continuous optimisation: the criterion itself has no gradient entry; candidates found by following sample functions off the pool
+ * (scfgp_sample_grad) can be appended to Xc. */
 int scfgp_select_iv(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* wr,
                     const double* Li, int m, int mode, int64_t* idx, double* red, double* var, double* ivar, double* std_after);
 

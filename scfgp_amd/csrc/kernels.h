@@ -269,6 +269,18 @@ void sample_argmax_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, 
 // bestv (nsamp) <- the y scaler's backward transform of mode ymode, by the kernel sample_product applies it with
 void sample_argmax_finalize(double* bestv, int nsamp, int ymode, const double* ysp, const Scal* sc, hipStream_t st);
 
+// ---- samplegrad.hip, values and input gradients of sample functions, one sample per row (scfgp_sample_grad) ----------------------------
+// leading dimension of WT: a weight row is contiguous, 16-byte aligned and zero past K
+int samplegrad_w_ld(int K);
+// WT (nsamp x samplegrad_w_ld(K), fp64) <- the transpose of W (K x nsamp row-major: a device copy of the host array)
+void samplegrad_weights(const double* W, int K, int nsamp, double* WT, hipStream_t st);
+// chunk row n < N under sample s = sidx[n] (sidx: Np doubles holding integers in [0, nsamp); NULL: s = (t0 + n) % nsamp):
+// val[n] = sum_j phi_c_nj w_s[j] + phi_s_nj w_s[J + j] (fp64) and grad[n][d] = sum_j Fall[d][j] (phi_c w_s[J + j] - phi_s w_s[j])_nj,
+// d < D (ld D), by predgrad's arithmetic and launch plan; FT as predgrad_operand leaves it
+template <typename T>
+void samplegrad(const Geom& g, const T* Phi, const double* WT, const double* sidx, int64_t t0, int nsamp, const T* FT, double* val,
+                double* grad, hipStream_t st);
+
 // ---- predcov.hip, joint posterior covariance between test points (scfgp_predict_cov) ---------------------------------------------------
 // out[n][j] (n < nrows, j < Tb; row-major, leading dimension Tb, fp64) = kappa sum_k Ca[n][k] Cb[j][k] over the K features, + kappa
 // where row_base + n == j with `noise`.  Ca, Cb: C = Phi Li^T as apply_c leaves it (leading dimension Kp, columns K.. zero), with

@@ -813,6 +813,14 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_sample_grad: f and d f / d x~ of the chunk's rows, each under its own sample's weights (samplegrad.hip; FT: grad_operand)
+    static int sample_grad_chunk(scfgp_ctx* c, const Geom& g, const double* WT, const double* sidx, int64_t t0, int nsamp, double* val,
+                                 double* grad) {
+        features(c, g);
+        samplegrad<T>(g, (const T*)c->p_Phi, WT, sidx, t0, nsamp, (const T*)c->p_FT, val, grad, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
 };
 
 #define DISPATCH(c, fn, ...) ((c)->dtype == SCFGP_F32 ? Impl<float>::fn(__VA_ARGS__) : Impl<double>::fn(__VA_ARGS__))
@@ -1583,6 +1591,88 @@ extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, co
     if (flag) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
     memcpy(idx, &h[nsamp], sizeof(int64_t) * nsamp);
     if (val) memcpy(val, h.data(), sizeof(double) * nsamp);
+    return SCFGP_OK;
+}
+
+// scfgp_sample's pipeline (RowFeed, OutRing) with the weights given: W is uploaded and transposed once, the rows' sample indices travel
+// as the feed's targets (doubles: exact below 1024) and reach the kernel through pack_data's zero-padded copy, and each chunk leaves
+// [grad (rows x D) | val (rows)] in one of two staging slots.  W and sidx are checked on the host before any device work.
+extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, const double* W, int nsamp, const int64_t* sidx, int mode,
+                                 double* val, double* grad) {
+    if (!c) return SCFGP_EARG;
+    int rc;
+    if ((rc = sample_check(c, Xs && W && grad && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_grad"))) return rc;
+    if (mode >= 1 && !c->d_xscale) { c->err = "sample_grad: no X scaler set"; return SCFGP_EARG; }
+    if (mode == 2 && !c->d_yscale) { c->err = "sample_grad: no y scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "sample_grad: parameters not set"; return SCFGP_EARG; }
+    const Geom& g0 = c->g;
+    std::vector<double> hs;                                       // sidx as the feed's targets
+    if (sidx) {
+        hs.resize(T);
+        for (int64_t t = 0; t < T; ++t) {
+            if (sidx[t] < 0 || sidx[t] >= nsamp) {
+                c->err = "sample_grad: sample index " + std::to_string(sidx[t]) + " at row " + std::to_string(t) + " is outside [0, nsamp)";
+                return SCFGP_EARG;
+            }
+            hs[t] = (double)sidx[t];
+        }
+    }
+    for (int64_t e = 0, n = (int64_t)g0.K * nsamp; e < n; ++e)
+        if (!std::isfinite(W[e])) { c->err = "sample_grad: non-finite weights"; return SCFGP_ENONFINITE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_grad(c, false))) return rc;
+    DevTmp wraw, wt, schunk, stage;                               // W as uploaded | its transpose | sidx of the chunk, padded | two slots
+    const int ldw = samplegrad_w_ld(g0.K);
+    if ((rc = dmalloc(c, &wraw.p, sizeof(double) * g0.K * nsamp))) return rc;
+    if ((rc = dmalloc(c, &wt.p, sizeof(double) * (int64_t)nsamp * ldw))) return rc;
+    if (sidx && (rc = dmalloc(c, &schunk.p, sizeof(double) * PRED_ROWS))) return rc;
+    HIPCHK(c, hipMemcpyAsync(wraw, W, sizeof(double) * g0.K * nsamp, hipMemcpyHostToDevice, c->st));
+    samplegrad_weights(wraw, g0.K, nsamp, wt, c->st);
+    DISPATCH(c, grad_operand, c);
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, slot_len = rows * (g0.D + 1);
+    RowFeed feed; OutRing ring;
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (sidx ? 1 : 0))))) return rc;
+    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
+    if ((rc = ring.open(c))) return rc;
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto slot_grad = [&](int64_t i) { return stage + (i & 1) * slot_len; };
+    auto slot_val = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * g0.D; };
+    auto upload = [&](int64_t i) {
+        return feed.upload(i, Xs + i * PRED_ROWS * g0.D, sidx ? hs.data() + i * PRED_ROWS : nullptr, rows_of(i));
+    };
+    auto download = [&](int64_t i) {
+        return ring.drain(i, [&]() -> int {
+            HIPCHK(c, hipMemcpyAsync(grad + i * PRED_ROWS * g0.D, slot_grad(i), sizeof(double) * rows_of(i) * g0.D, hipMemcpyDeviceToHost, c->copy_st));
+            if (val) HIPCHK(c, hipMemcpyAsync(val + i * PRED_ROWS, slot_val(i), sizeof(double) * rows_of(i), hipMemcpyDeviceToHost, c->copy_st));
+            return SCFGP_OK;
+        });
+    };
+    const int xmode = mode >= 1 ? c->xs_mode : 0;
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *sraw;
+        if ((rc = feed.acquire(i, &x, &sraw))) return rc;
+        pack_data(g, x, sidx ? sraw : nullptr, nullptr, c->p_Xt, schunk.p, c->st, xmode, c->d_xscale);
+        if ((rc = ring.acquire(i))) return rc;
+        if ((rc = DISPATCH(c, sample_grad_chunk, c, g, wt.p, schunk.p, i * PRED_ROWS, nsamp, slot_val(i), slot_grad(i)))) return rc;
+        // the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is released after them), the y
+        // scaler's at the scaled value, which its backward transform then replaces
+        if (xmode) xgrad_chunk(x, g.N, g0.D, xmode, c->d_xscale, slot_grad(i), nullptr, c->st);
+        if ((rc = feed.release(i))) return rc;
+        if (mode == 2) {
+            ygrad_chunk(slot_val(i), nullptr, g.N, g0.D, c->ys_mode, c->d_yscale, slot_grad(i), nullptr, c->st);
+            sample_argmax_finalize(slot_val(i), (int)g.N, c->ys_mode, c->d_yscale, c->d_sc, c->st);
+        }
+        if ((rc = ring.computed(i))) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i >= 1 && (rc = download(i - 1))) return rc;
+    }
+    if ((rc = download(nchunks - 1))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
     return SCFGP_OK;
 }
 

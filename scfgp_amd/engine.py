@@ -353,6 +353,47 @@ class HipEngine(object):
         self._check(rc, 'sample_argmax')
         return idx, val
 
+    def sample_grad(self, Xs, W, sidx=None, mode='scaled', want_val=True):
+        """Values and input gradients of sample functions, one sample per row (include/scfgp_hip.h: scfgp_sample_grad): (val (T,),
+        grad (T, D)) with val[t] = phi(x_t)^T W[:, sidx[t]] and grad[t] its gradient in x_t.  W (K, nsamp) as sample_weights returns
+        it (any K-vectors: W = alpha[:, None] gives the mean); sidx (T,) ints in [0, nsamp), None: t % nsamp.  mode as in
+        predict_grad: 'raw' chains grad through the X scaler and returns (T, D_raw) with zero columns where the scaler dropped a
+        constant column; 'y' also maps val through the y scaler's backward transform and grad through its derivative.  val is None
+        without want_val."""
+        if mode not in self.SAMPLE_MODES:
+            raise ValueError('sample_grad: mode must be one of %s' % sorted(self.SAMPLE_MODES))
+        m = self.SAMPLE_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('sample_grad: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        D_in = Xs.shape[1]
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[0] != self.K:
+            raise ValueError('W must be (K, nsamp) with K=%d' % self.K)
+        T, nsamp = Xs.shape[0], W.shape[1]
+        if sidx is not None:
+            sidx = np.ascontiguousarray(sidx, dtype=np.int64).reshape(-1)
+            if sidx.size != T:
+                raise ValueError('sidx has %d entries for %d rows' % (sidx.size, T))
+        val = np.empty(T) if want_val else None
+        grad = np.empty((T, self.D))
+        rc = self.lib.scfgp_sample_grad(self.ctx, dptr(Xs), T, dptr(W), nsamp, None if sidx is None else sidx.ctypes.data_as(_lib._c_i64_p),
+                                        m, dptr(val), dptr(grad))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('sample_grad: %s' % self.last_error())
+        self._check(rc, 'sample_grad')
+        if cols is not None:
+            grad = _scatter(grad, cols, D_in)
+        return val, grad
+
     PREDICT_COV_MODES = {'scaled': 0, 'raw': 1}
 
     def predict_cov(self, Xa, Li, Xb=None, mode='scaled', noise=False):

@@ -296,6 +296,18 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return self.engine.sample_argmax(Xs_raw, alpha, Li, nsamp, seed=seed, w=weights, mode='y', minimize=minimize)
 
+    def sample_weights(self, alpha, Li, nsamp, seed=0):
+        """W (K, nsamp): the weights of sample_y's functions at the shared parameter vector (engine.sample_weights)."""
+        self._sync_params()
+        return self.engine.sample_weights(alpha, Li, nsamp, seed=seed)
+
+    def sample_grad_raw(self, Xs_raw, x_scaler, y_scaler, W, sidx=None, y_units=False, want_val=True):
+        """Values and gradients (val (T,), grad (T, D_raw)) of the sample functions with weights W at the raw rows Xs_raw, row t under
+        function sidx[t]: in scaled y units, or with y_units in raw y units through the y scaler (engine.sample_grad)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, y_scaler if y_units else None)
+        return self.engine.sample_grad(Xs_raw, W, sidx=sidx, mode='y' if y_units else 'raw', want_val=want_val)
+
     def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
         """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
         self._sync_params()

@@ -315,6 +315,31 @@ class SCFGP(object):
             first = False
         return held
 
+    def sample_maximize(self, X_pool, nsamples, seed=0, weights=None, bounds=None, minimize=False, max_iter=60, gtol=1e-6):
+        """Continuous maximisers (minimize: minimisers) of nsamples posterior sample functions: each function's best row of the raw
+        pool X_pool (T,D), as sample_argmax names it, refined off the grid by projected-gradient ascent in raw X (scfgp_amd.ascent on
+        include/scfgp_hip.h: scfgp_sample_grad; one device call per step for all samples).  The functions are those of
+        sample(., nsamples, seed): their weights come from one sample_weights call.  The ascent runs on the scaled y value: the y
+        scaler's backward transform is monotone, so the maximiser is the same.  bounds = (lo, hi), scalars or (D,), default the
+        pool's per-column minimum and maximum; weights (T,): pool row t may start a sample iff weights[t] > 0.
+        Returns X_best (nsamples, D) raw points inside the bounds, val_y (nsamples,) the functions' values there in raw y units,
+        idx_start (nsamples,) the pool rows the ascents started from, converged (nsamples,) bool (projected-gradient norm <=
+        gtol max(1, |value|) within max_iter iterations).  In scaled units no value is worse than at its start row.  Nothing of the
+        model is touched."""
+        from .ascent import ascend
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('sample_maximize needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        X_pool = np.asarray(X_pool, dtype=np.float64)
+        nsamples = int(nsamples)
+        idx, _ = self.sample_argmax(X_pool, nsamples, seed=seed, weights=weights, minimize=minimize)
+        W = owner.sample_weights(self.alpha, self.Li, nsamples, seed=seed)
+        lo, hi = (X_pool.min(0), X_pool.max(0)) if bounds is None else bounds
+        fg = lambda X, s: owner.sample_grad_raw(X, self.X_scaler, self.y_scaler, W, sidx=s)
+        X_best, _, converged, _ = ascend(fg, X_pool[idx], np.arange(nsamples), lo, hi, minimize=minimize, max_iter=max_iter, gtol=gtol)
+        val_y, _ = owner.sample_grad_raw(X_best, self.X_scaler, self.y_scaler, W, sidx=np.arange(nsamples), y_units=True)
+        return X_best, val_y, idx, converged
+
     def predict_cov(self, Xs, Xs2=None, noise=False):
         """Joint posterior covariance of the fitted model's function values between the raw rows Xs and Xs2 (None: among the rows of
         Xs, a bit-for-bit symmetric matrix): (T, T2) = kappa phi(x)^T A^-1 phi(x').  Inputs are in raw X units; the covariance is that
