@@ -266,9 +266,45 @@ int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double
  * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL pointers, n < 1, a bad mode, a missing X scaler in mode 1 or
  * parameters not set; SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if the Cholesky of S fails: the outputs are
  * untouched in all three cases.  Out of scope: a communicator / row-sharded form (the update is replicated work on n rows: every rank
- * calls it with the same rows), removing observations, and keeping the factors resident on the device between calls. */
+ * calls it with the same rows) and keeping the factors resident on the device between calls.  Removing observations: scfgp_forget. */
 int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                     double* alpha_out, double* Li_out);
+
+/* ---- removing observations from a fitted posterior (no reference counterpart: the reference refits on the remaining rows) ------------
+ * The mirror image of scfgp_condition: n rows (Xo, yo) that ARE in the fit leave it through a K x K downdate that needs only alpha, Li,
+ * the parameters and the rows being removed.  Notation as there; Phi_o the features of the removed rows at the SAME hyper-parameters:
+ *     C = Phi_o Li^T (n x K)         r = yo - Phi_o alpha              S = I - C^T C = M M^T  (M lower; eigenvalues in (0, 1])
+ *     Li' = M^-1 Li                  gamma = S^-1 C^T r                alpha' = alpha - Li^T gamma
+ * A' = A - Phi_o^T Phi_o = L S L^T = (L M)(L M)^T, so (alpha', Li') are what scfgp_eval returns on the remaining rows (A' alpha' = A alpha -
+ * Phi_o^T yo gives the sign).  S is positive definite exactly when the rows were in the fit; otherwise it may have no Cholesky factor
+ * and the call returns SCFGP_ENOTPD.  The held-out predictions of the removed rows under the downdated fit -- the next step of
+ * cross-validation with arbitrary folds -- are formed on the device from factors that never leave it: mu_i = phi_i^T alpha',
+ * std_i = sqrt(kappa (1 + |Li' phi_i|^2)), and the joint log density of the block given the other rows needs no n x n matrix
+ * (det(I - C C^T) = det S, (I - C C^T)^-1 = I + C S^-1 C^T):
+ *     log p(yo | rest) = -1/2 [ (r^T r + |M^-1 C^T r|^2) / kappa + n log(2 pi kappa) - 2 sum_i log M_ii ]
+ * which is scfgp_loo's block formula for any n.
+ * mode 0: scaled rows; 1: column-selected raw rows through the registered X scaler.  yo is always the SCALED target.  alpha (K) and Li
+ * (K x K, entries above the diagonal are not read) as scfgp_eval returns them.  Three output groups, of which at least one is asked for:
+ *   alpha_out (K), Li_out (K x K, exactly zero above the diagonal): both or neither; they may alias alpha and Li;
+ *   mu, std (n each): both or neither; bit for bit what scfgp_predict (mode 0) or scfgp_predict_raw (mode 1) returns for the same rows
+ *     when given the returned (alpha', Li'): a second pass over Xo after the K x K stage, on the typed transpose of the device's Li';
+ *   stats (8 doubles, may be NULL, needs mu / std), with e = yo - mu: [0] n, [1] sum e^2, [2] sum |e|, [3] sum_i log N(yo_i; mu_i,
+ *     std_i^2), [4] the joint log density above, [5] min_i M_ii^2 (how close to singular the downdate was: M_ii^2 <= 1, and a value
+ *     near 0 says that what remains barely determines some direction of the weights), [6] 1, [7] 0.  [0] to [3] are formed from the
+ *     rounded outputs in row order by one thread: the same bits on every run.
+ * With the factor outputs omitted a cross-validation fold uploads Li once and downloads 2 n + 8 doubles.  All outputs are written only
+ * on success.  n >= 1 without limit: the rows go through in chunks of 32768 in both passes, so device memory does not grow with n.  The
+ * first pass (features, C, C^T C, C^T r) and the K x K stage are fp64 in every context: where scfgp_condition adds the rounding error of
+ * C^T C to eigenvalues >= 1, here it is divided by lam_min(S), so SCFGP_F32 and SCFGP_F16X3 contexts run the fp64 kernels of precision
+ * level 1 for it (on fp64 chunk buffers of the call's own, allocated by the first call) and agree bit for bit; the second pass is
+ * scfgp_predict's, in the context's precision.  Removing nearly everything a direction of the weights was determined by costs accuracy
+ * in any precision, and stats[5] shows it.  The training state of the context survives.  SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL inputs, n < 1, a
+ * bad mode, half an output group, stats without mu / std, no output group at all, a missing X scaler in mode 1 or parameters not set;
+ * SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if S has no Cholesky factor (the rows were not in this fit):
+ * the outputs are untouched in all three cases.  Out of scope: a communicator / row-sharded form, raw-y units, factors kept resident
+ * on the device between calls, and gradients of these numbers in the hyper-parameters. */
+int scfgp_forget(scfgp_ctx* ctx, const double* Xo, const double* yo, int64_t n, const double* alpha, const double* Li, int mode,
+                 double* alpha_out, double* Li_out, double* mu, double* std, double* stats);
 
 /* ---- exact leave-one-out / leave-block-out predictions of rows that are IN the fit (no reference counterpart: the reference refits) --
  * How well does the fitted model predict rows it has not seen -- without a refit.  With A = Phi^T Phi + lam I = L L^T, Li = L^-1,
@@ -296,7 +332,7 @@ int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t 
  * Cholesky factor (the rows were not in the fit): the message names the first such block.  On these two stats is untouched and mu, std,
  * lev hold nothing of use.  Row-sharded use needs no communicator: each rank calls it on its own rows with the common (alpha, Li) and
  * the caller adds the stats ([5]: the maximum).  Out of scope: folds of more than 64 rows or of rows that are not consecutive (they want
- * the K x K downdate), gradients of these numbers in the hyper-parameters, raw-y units, and factors kept on the device between calls. */
+ * the K x K downdate: scfgp_forget), gradients of these numbers in the hyper-parameters, raw-y units, and factors kept on the device between calls. */
 int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode, int block,
               double* mu, double* std, double* lev, double* stats);
 

@@ -327,6 +327,15 @@ struct KUpdate {
     int* flag;              // flag[0] = 1: S not positive definite (or NaN)
 };
 void kstage_update(const KUpdate& k, hipStream_t st);
+// scfgp_forget: the same stage with S = I - C^T C and alpha' = alpha - Li^T gamma (flag[0] = 1: the rows were not in the fit), then
+// out[0] = log p(y_o | the other rows) from rr[0] = r^T r, |M^-1 C^T r|^2 and M's diagonal, out[1] = min_i M_ii^2.  k.part holds
+// M^-1 C^T r on return.
+void kstage_downdate(const KUpdate& k, const double* rr, double n, const Scal* sc, double* out, hipStream_t st);
+// acc[0] += sum of r[0..n)^2 (one workgroup, fixed order)
+void update_sumsq(const double* r, int64_t n, double* acc, hipStream_t st);
+// acc[0..2] += sum e^2, sum |e|, sum log N(y_i; mu_i, sd_i^2) of n rows, e = y - mu: terms from the rounded mu / sd into rec (3 x ldr),
+// added in row order by one lane per sum
+void forget_stats(const double* mu, const double* sd, const double* y, int64_t n, int64_t ldr, double* rec, double* acc, hipStream_t st);
 // host-layout K x K factor on the device (ld K, entries above the diagonal not read) <-> Kp x Kp lower triangular, identity padding
 void update_load_factor(const double* Li_host_layout, int K, int Kp, double* Li, hipStream_t st);
 void update_store_factor(const double* Li, int K, int Kp, double* Li_host_layout, hipStream_t st);

@@ -686,7 +686,8 @@ void kstage_adjoint(const KStage& k, const double* BWB, double* Abar, const Scal
 // ---------------------------------------------------------------------------
 // posterior update (scfgp_condition; derivation in include/scfgp_hip.h): with C = Phi_n Li^T of the new rows,
 //   S = I + C^T C = M M^T,  Li' = M^-1 Li,  gamma = S^-1 C^T r,  alpha' = alpha + Li^T gamma
-// on its own buffers (KUpdate): nothing of the evaluation's K x K stage is touched.
+// on its own buffers (KUpdate): nothing of the evaluation's K x K stage is touched.  The downdate that takes rows OUT of a fit
+// (scfgp_forget) is the same stage with S = I - C^T C and alpha' = alpha - Li^T gamma (the DOWN instantiations).
 // ---------------------------------------------------------------------------
 // host-layout K x K factor (ld K; entries above the diagonal are not read) -> Kp x Kp lower triangular, identity padding
 __global__ __launch_bounds__(256) void update_pad_lower_kernel(const double* __restrict__ src, int K, int Kp, double* __restrict__ dst) {
@@ -716,7 +717,8 @@ __global__ __launch_bounds__(256) void update_accumulate_kernel(double* __restri
 }
 // packed lower 128 x 128 tiles of C^T C -> working matrix of the factorisation as kstage_unpack_kernel lays it out: lower 64 x 64
 // blocks of S = I + C^T C (the padding rows and columns of C^T C are zero, so the padding block is the identity by itself), the
-// strictly upper blocks := 0; padding blocks of Mi and of S^-1: identity
+// strictly upper blocks := 0; padding blocks of Mi and of S^-1: identity.  DOWN: S = I - C^T C (scfgp_forget)
+template <bool DOWN>
 __global__ __launch_bounds__(256) void update_unpack_kernel(const double* __restrict__ packed, int B, double* __restrict__ A, double* __restrict__ Mi,
                                                             double* __restrict__ Si, int64_t ld, int nbk) {
     const int t = blockIdx.x;
@@ -727,7 +729,8 @@ __global__ __launch_bounds__(256) void update_unpack_kernel(const double* __rest
     for (int e = blockIdx.y * 256 + threadIdx.x; e < B * B; e += gridDim.y * 256) {
         const double v = packed[(int64_t)t * B * B + e];
         const int i = ti * B + e / B, j = tj * B + e % B;
-        A[(int64_t)i * ld + j] = j / 64 > i / 64 ? 0.0 : (i == j ? v + 1.0 : v);
+        if (DOWN) A[(int64_t)i * ld + j] = j / 64 > i / 64 ? 0.0 : (i == j ? 1.0 - v : -v);
+        else A[(int64_t)i * ld + j] = j / 64 > i / 64 ? 0.0 : (i == j ? v + 1.0 : v);
         if (ti != tj) A[(int64_t)j * ld + i] = 0.0;
         if (i / 64 >= nbk || j / 64 >= nbk) {
             const double id = i == j ? 1.0 : 0.0;
@@ -774,14 +777,84 @@ __global__ __launch_bounds__(KCfg::THREADS) void tri_ll_kernel(const double* __r
             }
         }
 }
-// out[i] = base[i] + sum of the nparts partial sums of gemv_cols_part_kernel
+// out[i] = base[i] + (DOWN: -) sum of the nparts partial sums of gemv_cols_part_kernel
+template <bool DOWN>
 __global__ __launch_bounds__(256) void update_alpha_kernel(const double* __restrict__ base, const double* __restrict__ part, int nparts,
                                                            double* __restrict__ out, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     double s = 0;
     for (int p = 0; p < nparts; ++p) s += part[(int64_t)p * n + i];
-    out[i] = base[i] + s;
+    out[i] = DOWN ? base[i] - s : base[i] + s;
+}
+// acc[0] += sum of r[0..n)^2, one workgroup, fixed order: r^T r of one more chunk of rows (scfgp_forget)
+__global__ __launch_bounds__(256) void update_sumsq_kernel(const double* __restrict__ r, int64_t n, double* __restrict__ acc) {
+    __shared__ double r1[256];
+    double s = 0;
+    for (int64_t e = threadIdx.x; e < n; e += 256) s += r[e] * r[e];
+    r1[threadIdx.x] = s;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if (threadIdx.x < m) r1[threadIdx.x] += r1[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) acc[0] += r1[0];
+}
+// the downdate's scalars from M's diagonal (Lm), w = M^-1 C^T r and rr[0] = r^T r of the n removed rows:
+// out[0] = log p(y_o | the other rows) = -1/2 [ (r^T r + |w|^2) / kappa + n log(2 pi kappa) - 2 sum_i log M_ii ],  out[1] = min_i M_ii^2
+__global__ __launch_bounds__(256) void downdate_scalars_kernel(const double* __restrict__ Lm, int64_t ld, int K, const double* __restrict__ w,
+                                                               const double* __restrict__ rr, double n, const Scal* __restrict__ sc,
+                                                               double* __restrict__ out) {
+    __shared__ double r1[256], r2[256], r3[256];
+    double s1 = 0, s2 = 0, lmin = 1.0 / 0.0;
+    for (int i = threadIdx.x; i < K; i += 256) {
+        const double l = Lm[(int64_t)i * ld + i];
+        s1 += log(l); s2 += w[i] * w[i];
+        lmin = fmin(lmin, l * l);
+    }
+    r1[threadIdx.x] = s1; r2[threadIdx.x] = s2; r3[threadIdx.x] = lmin;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if (threadIdx.x < m) {
+            r1[threadIdx.x] += r1[threadIdx.x + m]; r2[threadIdx.x] += r2[threadIdx.x + m];
+            r3[threadIdx.x] = fmin(r3[threadIdx.x], r3[threadIdx.x + m]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double kappa = sc->kappa, TWO_PI = 6.283185307179586476925286766559;
+        out[0] = -0.5 * ((rr[0] + r2[0]) / kappa + n * log(TWO_PI * kappa) - 2.0 * r1[0]);
+        out[1] = r3[0];
+    }
+}
+// the terms of scfgp_forget's stats from the ROUNDED outputs, as a host recomputes them: rec[0..2][i] = e^2, |e|, log N(y_i; mu_i, sd_i^2)
+__global__ __launch_bounds__(256) void forget_terms_kernel(const double* __restrict__ mu, const double* __restrict__ sd, const double* __restrict__ y,
+                                                           int64_t n, int64_t ldr, double* __restrict__ rec) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+#pragma clang fp contract(off)
+        const double TWO_PI = 6.283185307179586476925286766559;
+        const double er = y[i] - mu[i], var = sd[i] * sd[i];
+        const double e2 = er * er;
+        rec[i] = e2; rec[ldr + i] = fabs(er); rec[2 * ldr + i] = -0.5 * (e2 / var + log(TWO_PI * var));
+    }
+}
+// acc[s] += rec[s][0..n) in row order, s = 0..2: one lane per sum, one row after the other (the same bits on every run)
+__global__ __launch_bounds__(64) void forget_reduce_kernel(const double* __restrict__ rec, int64_t n, int64_t ldr, double* __restrict__ acc) {
+    const int s = threadIdx.x;
+    if (s >= 3) return;
+    const double* v = rec + s * ldr;
+    double a = acc[s];
+    int64_t j = 0;
+    for (; j + 8 <= n; j += 8) {
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = v[j + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a += t[u];
+    }
+    for (; j < n; ++j) a += v[j];
+    acc[s] = a;
 }
 
 void update_load_factor(const double* Li_host_layout, int K, int Kp, double* Li, hipStream_t st) {
@@ -796,17 +869,33 @@ void update_check_finite(const double* x, int64_t n, int* flag, hipStream_t st) 
 void update_accumulate(double* acc, const double* part, int64_t n, hipStream_t st) {
     hipLaunchKernelGGL(update_accumulate_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, acc, part, n);
 }
-void kstage_update(const KUpdate& k, hipStream_t st) {
+void update_sumsq(const double* r, int64_t n, double* acc, hipStream_t st) {
+    hipLaunchKernelGGL(update_sumsq_kernel, dim3(1), dim3(256), 0, st, r, n, acc);
+}
+void forget_stats(const double* mu, const double* sd, const double* y, int64_t n, int64_t ldr, double* rec, double* acc, hipStream_t st) {
+    hipLaunchKernelGGL(forget_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mu, sd, y, n, ldr, rec);
+    hipLaunchKernelGGL(forget_reduce_kernel, dim3(1), dim3(64), 0, st, rec, n, ldr, acc);
+}
+// DOWN = false: scfgp_condition's update; true: scfgp_forget's downdate, S = I - C^T C and alpha' = alpha - Li^T gamma
+template <bool DOWN>
+static void update_stage(const KUpdate& k, hipStream_t st) {
     const int Kp = k.Kp, nts = Kp / 128, nbk = (k.K + 63) / 64, nb = Kp / 64;
     const int64_t ld = Kp;
-    hipLaunchKernelGGL(update_unpack_kernel, dim3(nts * (nts + 1) / 2, 16), dim3(256), 0, st, k.packed, 128, k.S, k.Mi, k.Si, ld, nbk);
+    hipLaunchKernelGGL(update_unpack_kernel<DOWN>, dim3(nts * (nts + 1) / 2, 16), dim3(256), 0, st, k.packed, 128, k.S, k.Mi, k.Si, ld, nbk);
     KStage f{}; f.K = k.K; f.Kp = Kp; f.A = k.S; f.T2 = k.Lm; f.Li = k.Mi; f.B = k.Si; f.flag = k.flag;
     cholesky_inverse_gram(f, st);                                      // M in Lm's diagonal blocks, Mi = M^-1, Si = S^-1 = Mi^T Mi
-    // gamma = S^-1 (C^T r); alpha' = alpha + Li^T gamma (the OLD factor); Li' = Mi Li over S, which the factorisation is done with
+    // gamma = S^-1 (C^T r); alpha' = alpha +- Li^T gamma (the OLD factor); Li' = Mi Li over S, which the factorisation is done with
     hipLaunchKernelGGL(gemv_rows_kernel, dim3((Kp + 3) / 4), dim3(256), 0, st, k.Si, ld, k.packed + k.n_pk, k.gamma, Kp);
     constexpr int PARTS = 32;
     hipLaunchKernelGGL(gemv_cols_part_kernel, dim3((Kp + 255) / 256, PARTS), dim3(256), 0, st, k.Li, ld, k.gamma, k.part, Kp);
-    hipLaunchKernelGGL(update_alpha_kernel, dim3((Kp + 255) / 256), dim3(256), 0, st, k.alpha, k.part, PARTS, k.alpha_out, Kp);
+    hipLaunchKernelGGL(update_alpha_kernel<DOWN>, dim3((Kp + 255) / 256), dim3(256), 0, st, k.alpha, k.part, PARTS, k.alpha_out, Kp);
     allow_big_lds(tri_ll_kernel, KCfg::LDS_BYTES);
     hipLaunchKernelGGL(tri_ll_kernel, dim3(nb * (nb + 1) / 2), dim3(KCfg::THREADS), KCfg::LDS_BYTES, st, k.Mi, k.Li, k.S, ld, nb);
+}
+void kstage_update(const KUpdate& k, hipStream_t st) { update_stage<false>(k, st); }
+// ... and w = M^-1 C^T r into k.part (the partial sums are done with), then the scalars: out[0] the joint log density, out[1] min M_ii^2
+void kstage_downdate(const KUpdate& k, const double* rr, double n, const Scal* sc, double* out, hipStream_t st) {
+    update_stage<true>(k, st);
+    hipLaunchKernelGGL(gemv_rows_kernel, dim3((k.Kp + 3) / 4), dim3(256), 0, st, k.Mi, (int64_t)k.Kp, k.packed + k.n_pk, k.part, k.Kp);
+    hipLaunchKernelGGL(downdate_scalars_kernel, dim3(1), dim3(256), 0, st, k.Lm, (int64_t)k.Kp, k.K, k.part, rr, n, sc, out);
 }

@@ -194,6 +194,11 @@ struct scfgp_ctx {
     // chunk, two staging halves of [mu | std | lev], the running stats ([0..3] sums, [4] max h) and the flags ([0] non-finite, [1] first
     // block without a Cholesky factor)
     double *l_y = nullptr, *l_r = nullptr, *l_rec = nullptr, *l_out = nullptr, *l_acc = nullptr; unsigned long long* l_bad = nullptr;
+    // ... and those of scfgp_forget beyond scfgp_condition's, allocated by its first call (ensure_forget): two staging halves of
+    // [mu | std], the stats' terms of a chunk (3 x PRED_ROWS) and the scalars ([0..2] running sums, [3] r^T r, [4] joint, [5] min M_ii^2)
+    // In fp32 contexts its first pass runs in fp64 (the fp64 features, C and Gram of precision level 1) on f_w: [Phi | C] (PRED_ROWS x Kp
+    // each) and [Li^T | Li] (Kp x Kp each), all fp64
+    double *f_out = nullptr, *f_w = nullptr;
     // on-device optimiser + captured training iteration
     int opt_algo = -1; OptHyper opt_h{}; double *d_opt = nullptr, *d_tctr = nullptr, *d_hist = nullptr; int hist_cap = 0;
     hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; int64_t graph_N = -1; bool in_train = false, warm = false;
@@ -468,6 +473,7 @@ extern "C" void scfgp_destroy(scfgp_ctx* c) {
     dfree(c->u_Li); dfree(c->u_S); dfree(c->u_Lm); dfree(c->u_Mi); dfree(c->u_Si); dfree(c->u_vec); dfree(c->u_acc); dfree(c->u_part);
     dfree(c->u_y); dfree(c->u_r); dfree(c->u_slabs); dfree(c->u_LiT); dfree(c->u_ws2); dfree(c->u_flag);
     dfree(c->l_y); dfree(c->l_r); dfree(c->l_rec); dfree(c->l_out); dfree(c->l_acc); dfree(c->l_bad);
+    dfree(c->f_out); dfree(c->f_w);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->graph) hipGraphDestroy(c->graph);
     dfree(c->d_opt); dfree(c->d_tctr); dfree(c->d_hist);
@@ -540,6 +546,9 @@ static void unpack_exchange(scfgp_ctx* c, const double* xp, double* x) {
     hipMemcpyAsync(x + (int64_t)g.Kp * g.Kp, xp + c->n_pk, sizeof(double) * (g.Kp + 8), hipMemcpyDeviceToDevice, c->st);
 }
 
+// typed operands of the first pass of scfgp_condition / scfgp_forget (Impl::update_chunk): Phi and C of a chunk (PRED_ROWS x Kp, padding
+// columns zero), the factor's transpose and the factor (Kp x Kp)
+struct UpdateOperands { void *Phi, *C, *LiT, *Li; };
 template <typename T> struct Impl {
     typedef SweepKernels<T> SK;
     // out = [packed lower tiles of M^T diag(w) M | M^T side (Kp)],  M = Phi (pass 1) or V = Phi B (pass 2)
@@ -768,17 +777,18 @@ template <typename T> struct Impl {
     }
     // workgroups per row split of the Gram launch on the context's geometry (update_splits)
     static int gram_jobs(const scfgp_ctx* c) { return SK::gram_jobs(c->g); }
-    // scfgp_condition: C = Phi_n Li^T with the update's own factor and alpha (u_LiT, u_vec), the residual r = y - Phi_n alpha, then
-    // [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the chunk's geometry with the
-    // update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows (never the fp16 split: an
-    // f16x3 context runs fp32 mode's kernels here)
-    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, double* out) {
-        features(c, g);
-        factor_c(c, g, (const T*)c->u_LiT, c->u_vec, (T*)c->p_C);
+    // scfgp_condition, scfgp_forget: C = Phi_n Li^T with the update's own factor and alpha (o.LiT / o.Li, u_vec), the residual
+    // r = y - Phi_n alpha, then [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the
+    // chunk's geometry with the update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows
+    // (never the fp16 split: an f16x3 context runs fp32 mode's kernels here).  The typed operands come with the call (UpdateOperands):
+    // scfgp_forget runs the fp64 arm on buffers of its own in an fp32 context.
+    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const UpdateOperands& o, double* out) {
+        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.Phi, c->st);
+        SK::apply_c(g, (const T*)o.Phi, (const T*)o.LiT, (const T*)o.Li, (T*)o.C, c->p_vpart, c->u_vec, c->u_vec, c->p_mupart, c->st, 0);
         SK::rowresidual(g, c->p_mupart, c->u_y, c->u_r, c->st);
         const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
         double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
-        SK::gram(g, (const T*)c->p_C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
+        SK::gram(g, (const T*)o.C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
         reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
         reduce_side(sidepart, rs.nsplit, g.Kp, g.gfull * g.tile + g.gstrip * 64, out + c->n_pk, c->st);
         HIPCHK(c, hipGetLastError());
@@ -1208,7 +1218,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_loo and scfgp_select
+// scfgp_condition, scfgp_forget, scfgp_loo and scfgp_select
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -1765,7 +1775,8 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
 // absorbing new observations into a fitted posterior (kernels_kstage.hip: kstage_update; derivation in include/scfgp_hip.h)
 // ----------------------------------------------------------------------------------------------
 // row splits of the update's Gram product over a chunk of Np rows, and the slabs they need
-static RowSplits update_splits(const scfgp_ctx* c, int64_t Np) {
+static RowSplits update_splits(const scfgp_ctx* c, int64_t Np, bool wide = false) {
+    if (wide) return gram_row_splits(Impl<double>::gram_jobs(c), Np, false, 0, 1);     // the fp64 job list in an fp32 context
     return gram_row_splits(DISPATCH(c, gram_jobs, c), Np, c->dtype == SCFGP_F32, 0, 1);
 }
 // the update stage's own buffers (first call only; the slabs grow to what the call's chunks need)
@@ -1793,9 +1804,66 @@ static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
     return SCFGP_OK;
 }
 
-// The chunk pipeline (RowFeed) with the targets behind the rows of their chunk and the X scaler in mode 1.  Each chunk adds its C^T C
-// and C^T r to a running fp64 sum, and one K x K stage turns the sum into the new factors, which leave through the feed's buffer.  The
-// outputs are fetched only when the stage succeeded.
+// The first pass of scfgp_condition and scfgp_forget: the chunk pipeline (RowFeed) with the targets behind the rows of their chunk and
+// the X scaler in mode 1.  The factors are loaded into the update's buffers (u_Li, u_LiT, alpha at u_vec), then each chunk adds its
+// C^T C and C^T r to a running fp64 sum in u_acc and, rr != NULL, its r^T r to rr[0].  u_flag[0..3] are cleared first; u_flag[1] tells
+// of non-finite rows, targets or factors.  `feed` is opened here and stays open for the caller.  wide != NULL (fp32 contexts only): the
+// pass runs the fp64 kernels on these operands.
+static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const double* y, int64_t n, const double* alpha, const double* Li,
+                         int mode, double* rr, const UpdateOperands* wide = nullptr) {
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp;
+    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    {   // slabs of the widest split among the call's chunk shapes (full chunks and the ragged last one)
+        const int nts = Kp / g0.tile, ntiles = nts * (nts + 1) / 2;
+        size_t need = 0;
+        for (int64_t np : {round_up(std::min<int64_t>(n, PRED_ROWS), 256), round_up(n - (nchunks - 1) * PRED_ROWS, 256)})
+            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np, wide).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
+        if ((rc = ensure_update(c, need))) return rc;
+    }
+    const UpdateOperands own = {c->p_Phi, c->p_C, c->u_LiT, c->p_Li};
+    const UpdateOperands& ops = wide ? *wide : own;
+    // Li in host layout (in, then out) / two chunks of [X | y]
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
+    HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
+    if (rr) HIPCHK(c, hipMemsetAsync(rr, 0, sizeof(double), c->st));
+    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->u_Li, wide ? nullptr : ops.LiT, wide ? nullptr : ops.Li, alpha, c->u_vec,
+                          c->u_flag))) return rc;
+    if (wide) Impl<double>::type_factor(c, c->u_Li, ops.LiT, ops.Li);
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return feed.upload(i, X + i * PRED_ROWS * g0.D, y + i * PRED_ROWS, rows_of(i)); };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *yi;
+        if ((rc = feed.acquire(i, &x, &yi))) return rc;
+        pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        double* out = i == 0 ? c->u_acc : c->u_part;
+        if ((rc = wide ? Impl<double>::update_chunk(c, g, update_splits(c, g.Np, true), ops, out)
+                       : DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), ops, out))) return rc;
+        if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
+        if (rr) update_sumsq(c->u_r, g.N, rr, c->st);
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    // non-finite rows or targets have reached C^T C or C^T r by now
+    update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
+    return SCFGP_OK;
+}
+static KUpdate update_buffers(scfgp_ctx* c) {
+    const int64_t Kp = c->g.Kp;
+    KUpdate k;
+    k.K = c->g.K; k.Kp = c->g.Kp; k.packed = c->u_acc; k.n_pk = c->n_pk; k.Li = c->u_Li; k.alpha = c->u_vec; k.S = c->u_S; k.Lm = c->u_Lm;
+    k.Mi = c->u_Mi; k.Si = c->u_Si; k.gamma = c->u_vec + Kp; k.alpha_out = c->u_vec + 2 * Kp; k.part = c->u_vec + 3 * Kp; k.flag = c->u_flag;
+    return k;
+}
+
+// One K x K stage turns the first pass's sum into the new factors, which leave through the feed's buffer.  The outputs are fetched only
+// when the stage succeeded.
 extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                                double* alpha_out, double* Li_out) {
     if (!c) return SCFGP_EARG;
@@ -1806,44 +1874,13 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
     int rc;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    {   // slabs of the widest split among the call's chunk shapes (full chunks and the ragged last one)
-        const int nts = Kp / g0.tile, ntiles = nts * (nts + 1) / 2;
-        size_t need = 0;
-        for (int64_t np : {round_up(std::min<int64_t>(n, PRED_ROWS), 256), round_up(n - (nchunks - 1) * PRED_ROWS, 256)})
-            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
-        if ((rc = ensure_update(c, need))) return rc;
-    }
-    RowFeed feed;                                                 // Li in host layout (in, then out) / two chunks of [X | y]
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
-    double* d_alpha = c->u_vec; double* d_gamma = c->u_vec + Kp; double* d_alpha_out = c->u_vec + 2 * Kp; double* d_parts = c->u_vec + 3 * Kp;
-    HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
-    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->u_Li, c->u_LiT, c->p_Li, alpha, d_alpha, c->u_flag))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xn + i * PRED_ROWS * g0.D, yn + i * PRED_ROWS, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
-        const double *x, *y;
-        if ((rc = feed.acquire(i, &x, &y))) return rc;
-        pack_data(g, x, y, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), i == 0 ? c->u_acc : c->u_part))) return rc;
-        if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
-    }
-    // non-finite rows or targets have reached C^T C or C^T r by now
-    update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
-    KUpdate k;
-    k.K = g0.K; k.Kp = g0.Kp; k.packed = c->u_acc; k.n_pk = c->n_pk; k.Li = c->u_Li; k.alpha = d_alpha; k.S = c->u_S; k.Lm = c->u_Lm;
-    k.Mi = c->u_Mi; k.Si = c->u_Si; k.gamma = d_gamma; k.alpha_out = d_alpha_out; k.part = d_parts; k.flag = c->u_flag;
+    RowFeed feed;
+    if ((rc = update_gather(c, feed, Xn, yn, n, alpha, Li, mode, nullptr))) return rc;
+    const KUpdate k = update_buffers(c);
     kstage_update(k, c->st);
     update_check_finite(c->u_S, K2, c->u_flag, c->st);
-    update_check_finite(d_alpha_out, Kp, c->u_flag, c->st);
+    update_check_finite(k.alpha_out, Kp, c->u_flag, c->st);
     update_store_factor(c->u_S, g0.K, g0.Kp, feed.raw, c->st);
     HIPCHK(c, hipGetLastError());
     int flags[2] = {0, 0};
@@ -1852,8 +1889,115 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
     if (flags[1]) { c->err = "condition: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
     if (flags[0]) { c->err = "condition: I + C^T C is not positive definite"; return SCFGP_ENOTPD; }
     HIPCHK(c, hipMemcpyAsync(Li_out, feed.raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(alpha_out, d_alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// removing observations from a fitted posterior (kernels_kstage.hip: kstage_downdate; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static int ensure_forget(scfgp_ctx* c) {
+    if (c->f_out) return SCFGP_OK;
+    const int64_t Kp = c->g.Kp;
+    int rc;
+    if (c->dtype == SCFGP_F32) {
+        const size_t bytes = sizeof(double) * 2 * (PRED_ROWS * Kp + Kp * Kp);
+        if ((rc = dmalloc(c, &c->f_w, bytes))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->f_w, 0, bytes, c->st));               // the padding columns of Phi and C stay zero
+    }
+    return dmalloc(c, &c->f_out, sizeof(double) * (7 * PRED_ROWS + 8));
+}
+// scfgp_condition's first pass over the rows (plus r^T r), the K x K stage in its downdate form, then -- mu != NULL -- a second pass of
+// the same feed over the rows: predict_chunk on the typed transpose of the device's Li', mu | std leaving through two staging halves
+// (OutRing), the stats' sums formed on the device.  The host learns whether the stage succeeded before anything is written.
+extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, int64_t n, const double* alpha, const double* Li, int mode,
+                            double* alpha_out, double* Li_out, double* mu, double* sd, double* stats) {
+    if (!c) return SCFGP_EARG;
+    if (!Xo || !yo || !alpha || !Li || mode < 0 || mode > 1) { c->err = "forget: bad arguments"; return SCFGP_EARG; }
+    if ((!alpha_out) != (!Li_out)) { c->err = "forget: alpha_out and Li_out go together"; return SCFGP_EARG; }
+    if ((!mu) != (!sd)) { c->err = "forget: mu and std go together"; return SCFGP_EARG; }
+    if (stats && !mu) { c->err = "forget: stats need mu and std"; return SCFGP_EARG; }
+    if (!alpha_out && !mu) { c->err = "forget: no output asked for"; return SCFGP_EARG; }
+    if (n < 1) { c->err = "forget: n must be at least 1"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "forget: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "forget: parameters not set"; return SCFGP_EARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
+    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
+    int rc;
+    if ((rc = ensure_forget(c))) return rc;
+    double* rec = c->f_out + 4 * PRED_ROWS; double* acc = c->f_out + 7 * PRED_ROWS;
+    // In fp32 contexts the first pass is the fp64 one: the error of C^T C is divided by lam_min(S) here, and what the fp32 chains of the
+    // Gram launch add to it (~1e-6 of its entries) is felt in the predictions once most of a fit is removed.
+    const UpdateOperands wide = {c->f_w, c->f_w + PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp + K2};
+    RowFeed feed;
+    if ((rc = update_gather(c, feed, Xo, yo, n, alpha, Li, mode, acc + 3, c->dtype == SCFGP_F32 ? &wide : nullptr))) return rc;
+    const KUpdate k = update_buffers(c);
+    kstage_downdate(k, acc + 3, (double)n, c->d_sc, acc + 4, c->st);
+    // u_flag[1]: what went in; u_flag[2]: what came out (a factorisation that failed leaves NaN behind, which is u_flag[0]'s to tell)
+    update_check_finite(c->u_S, K2, c->u_flag + 1, c->st);
+    update_check_finite(k.alpha_out, Kp, c->u_flag + 1, c->st);
+    HIPCHK(c, hipGetLastError());
+    int flags[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (flags[1]) { c->err = "forget: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
+    if (flags[0]) { c->err = "forget: I - C^T C is not positive definite: these rows were not in this fit"; return SCFGP_ENOTPD; }
+    if (flags[2]) { c->err = "forget: the downdated factors are not finite"; return SCFGP_ENONFINITE; }
+    if (mu) {
+        // the operands predict would build from the returned factors: the typed Li'^T (over the old one) and alpha', zero-padded
+        DISPATCH(c, type_factor, c, c->u_S, c->u_LiT, nullptr);
+        HIPCHK(c, hipMemsetAsync(c->alpha_pred(), 0, sizeof(double) * Kp, c->st));
+        HIPCHK(c, hipMemcpyAsync(c->alpha_pred(), k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToDevice, c->st));
+        HIPCHK(c, hipMemsetAsync(acc, 0, sizeof(double) * 3, c->st));
+        OutRing ring;
+        if ((rc = ring.open(c))) return rc;
+        auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
+        // the feed's jobs go on counting behind the first pass's, so its halves and events keep their order
+        auto upload = [&](int64_t i) { return feed.upload(nchunks + i, Xo + i * PRED_ROWS * g0.D, yo + i * PRED_ROWS, rows_of(i)); };
+        auto slot = [&](int64_t i) { return c->f_out + (i & 1) * 2 * PRED_ROWS; };
+        auto download = [&](int64_t i) {
+            return ring.drain(i, [&]() -> int {
+                const int64_t t0 = i * PRED_ROWS, m = rows_of(i);
+                const double* o = slot(i);
+                HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+                HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
+                return SCFGP_OK;
+            });
+        };
+        if ((rc = upload(0))) return rc;
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const Geom g = chunk_geom(g0, rows_of(i));
+            const double *x, *yi;
+            if ((rc = feed.acquire(nchunks + i, &x, &yi))) return rc;
+            pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+            if ((rc = feed.release(nchunks + i))) return rc;
+            if ((rc = ring.acquire(i))) return rc;
+            double* o = slot(i);
+            if ((rc = DISPATCH(c, predict_chunk, c, g, c->u_LiT, o, o + PRED_ROWS))) return rc;
+            if (stats) forget_stats(o, o + PRED_ROWS, c->u_y, g.N, PRED_ROWS, rec, acc, c->st);
+            if ((rc = ring.computed(i))) return rc;
+            if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+            if (i >= 1 && (rc = download(i - 1))) return rc;
+        }
+        if ((rc = download(nchunks - 1))) return rc;
+    }
+    double h_acc[6];
+    if (stats) HIPCHK(c, hipMemcpyAsync(h_acc, acc, sizeof(h_acc), hipMemcpyDeviceToHost, c->st));
+    if (alpha_out) {
+        update_store_factor(c->u_S, g0.K, g0.Kp, c->u_Si, c->st);          // S^-1 is done with: Li' in host layout
+        HIPCHK(c, hipMemcpyAsync(Li_out, c->u_Si, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (stats) {
+        stats[0] = (double)n; stats[1] = h_acc[0]; stats[2] = h_acc[1]; stats[3] = h_acc[2]; stats[4] = h_acc[4]; stats[5] = h_acc[5];
+        stats[6] = 1.0; stats[7] = 0.0;
+    }
     return SCFGP_OK;
 }
 

@@ -602,6 +602,54 @@ class HipEngine(object):
         self._check(rc, 'condition')
         return alpha_out, Li_out
 
+    FORGET_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'log_joint', 'min_pivot2', 'blocks')
+
+    def forget(self, X, y, alpha, Li, factors=True, predict=False, mode='scaled'):
+        """Remove the observations (X, y), rows that ARE in the fit (alpha, Li), from the posterior (include/scfgp_hip.h: scfgp_forget).
+        factors: return (alpha' (K,1), Li' (K,K)), the factors of the fit on the remaining rows.  predict: return (mu (n,1), std (n,),
+        stats dict), the held-out predictions of the removed rows under that fit -- bit for bit predict(X, alpha', Li') -- and
+        FORGET_STATS with e = y - mu; with factors=False Li' never leaves the device.  Both: (alpha', Li', mu, std, stats).  mode
+        'scaled': X as predict takes it; 'raw': unscaled X through the registered X scaler.  y (n,) or (n,1) is the SCALED target."""
+        if mode not in self.CONDITION_MODES:
+            raise ValueError('forget: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        if X is None or y is None or alpha is None or Li is None:
+            raise ValueError('forget: X, y, alpha and Li are all needed')
+        if not factors and not predict:
+            raise ValueError('forget: nothing asked for (factors and predict are both False)')
+        m = self.CONDITION_MODES[mode]
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('forget: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise TypeError('X must be a 2-d float64 array')
+        if cols is not None:
+            X = X[:, cols]
+        X = np.ascontiguousarray(X)
+        if X.shape[1] != self.D:
+            raise ValueError('X has %d columns, expected %d' % (X.shape[1], self.D))
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if y.size != X.shape[0]:
+            raise ValueError('y has %d entries for %d rows' % (y.size, X.shape[0]))
+        n = X.shape[0]
+        alpha, Li = self._factors(alpha, Li)
+        alpha_out = np.empty((self.K, 1)) if factors else None
+        Li_out = np.empty((self.K, self.K)) if factors else None
+        mu = np.empty((n, 1)) if predict else None
+        sd = np.empty(n) if predict else None
+        stats = np.zeros(8) if predict else None
+        rc = self.lib.scfgp_forget(self.ctx, dptr(X), dptr(y), n, dptr(alpha), dptr(Li), m, dptr(alpha_out), dptr(Li_out), dptr(mu), dptr(sd),
+                                   dptr(stats))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('forget: %s' % self.last_error())
+        self._check(rc, 'forget')
+        out = (alpha_out, Li_out) if factors else ()
+        if predict:
+            st = dict(zip(self.FORGET_STATS, stats.tolist()))
+            st['n'] = int(st['n']); st['blocks'] = int(st['blocks'])
+            out = out + (mu, sd, st)
+        return out
+
     LOO_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'sum_log_joint', 'max_leverage', 'blocks')
 
     def loo(self, X=None, y=None, alpha=None, Li=None, block=1, mode='scaled'):

@@ -321,6 +321,18 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.condition(X_raw, y_scaled, alpha, Li, mode='raw')
 
+    def forget_raw(self, X_raw, y_scaled, x_scaler, alpha, Li, factors=True, predict=False):
+        """engine.forget of the rows (X_raw, y_scaled), which must be rows of the fit (alpha, Li), at the shared parameter vector: raw
+        rows through the X scaler on the device, targets already scaled."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.forget(X_raw, y_scaled, alpha, Li, factors=factors, predict=predict, mode='raw')
+
+    def forget_func(self, X, y, alpha, Li, factors=True, predict=False):
+        """forget_raw for SCALED rows (X, y), as train_func takes them."""
+        self._sync_params()
+        return self.engine.forget(X, y, alpha, Li, factors=factors, predict=predict, mode='scaled')
+
     def loo_raw(self, X_raw, y_scaled, x_scaler, alpha, Li, block=1):
         """Leave-block-out predictions (mu, std, lev, stats) of the rows (X_raw, y_scaled), which must be rows of the fit (alpha, Li), at
         the shared parameter vector: raw rows through the X scaler on the device, targets already scaled (engine.loo)."""

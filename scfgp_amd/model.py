@@ -365,6 +365,79 @@ class SCFGP(object):
         self.alpha, self.Li = owner.condition_raw(X, ys, self.X_scaler, self.alpha, self.Li)
         return self
 
+    def forget(self, X, y):
+        """Remove the observations (X, y), raw inputs (n,D) and raw targets (n,1) that ARE rows of the fit, from the fitted posterior:
+        self.alpha and self.Li become those of the fit on the remaining rows, at the current hyper-parameters, through a K x K
+        downdate that needs no other rows (include/scfgp_hip.h: scfgp_forget): the inverse of condition(X, y), a sliding window when
+        the two alternate.  Units, scalers and what is left alone are as in condition: the scalers are not refitted and self.X /
+        self.y are NOT touched.  Rows that were not in the fit raise the library's 'not positive definite' error (or, if few, go
+        unnoticed: the library cannot check membership).  Returns self."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('forget needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        ys = np.asarray(self.y_scaler.forward_transform(np.asarray(y, dtype=np.float64).reshape(-1, 1)), dtype=np.float64)
+        self.alpha, self.Li = owner.forget_raw(X, ys, self.X_scaler, self.alpha, self.Li)
+        return self
+
+    def cv(self, X=None, y=None, folds=5, seed=0):
+        """K-fold cross-validation of the fitted model with arbitrary folds, without a refit: (mu_y (n,1), std_y (n,1), metrics,
+        fold_stats).  Every row is predicted from the fit on all rows but those of its fold, at the current hyper-parameters and with
+        the fitted scalers: one scfgp_forget call per fold, which downdates the factors on the device and predicts the fold's rows
+        there (no K x K matrix comes back).  folds: an integer k >= 2 -- a random partition into k folds of nearly equal size drawn
+        from numpy's default_rng(seed) -- or an array (n,) of fold ids.  Without X, y the rows are the model's own training set; raw
+        (X, y) -- ALL rows of the fit, or the held-out predictions condition on more than 'the other rows' -- may be passed instead,
+        the only way for a model restored by load().  mu_y / std_y and the six metrics are in raw y units as loo returns them;
+        metrics['CV_LPD'] is the mean log predictive density of the scaled targets and 'CV_LOG_JOINT' the sum of the folds' joint log
+        densities; fold_stats is the list of the folds' stats (engine.FORGET_STATS, scaled units) with 'fold' (its id) added, in
+        ascending id order.  Neither self.evals nor self.alpha / self.Li are touched."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('cv needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        if (X is None) != (y is None):
+            raise ValueError('cv: X and y go together (both None: the training set)')
+        if X is None:
+            if getattr(self, "X", None) is None or getattr(self, "y", None) is None:
+                raise ValueError('cv: the model holds no training rows (restored by load()?): pass the raw (X, y) of the fit')
+            Xr = np.asarray(self.X, dtype=np.float64)
+            fy = np.asarray(self.y, dtype=np.float64).reshape(-1, 1)
+            ys = self.y_scaler.backward_transform(fy)
+            call = lambda rows: owner.forget_func(Xr[rows], fy[rows], self.alpha, self.Li, factors=False, predict=True)
+        else:
+            Xr = np.asarray(X, dtype=np.float64)
+            ys = np.asarray(y, dtype=np.float64).reshape(-1, 1)
+            fy = np.asarray(self.y_scaler.forward_transform(ys), dtype=np.float64)
+            call = lambda rows: owner.forget_raw(Xr[rows], fy[rows], self.X_scaler, self.alpha, self.Li, factors=False, predict=True)
+        n = Xr.shape[0]
+        if np.ndim(folds) == 0:
+            k = int(folds)
+            if k < 2 or k > n:
+                raise ValueError('cv: folds must lie in 2..n')
+            ids = np.empty(n, dtype=np.int64)
+            ids[np.random.default_rng(seed).permutation(n)] = np.arange(n) % k
+        else:
+            ids = np.asarray(folds).reshape(-1)
+            if ids.size != n:
+                raise ValueError('cv: folds has %d entries for %d rows' % (ids.size, n))
+        mu_f = np.empty((n, 1)); std_f = np.empty(n); fold_stats = []
+        for f in np.unique(ids):
+            rows = np.flatnonzero(ids == f)
+            m, s, st = call(rows)
+            mu_f[rows] = m; std_f[rows] = s
+            st['fold'] = f.item()
+            fold_stats.append(st)
+        mu_y = self.y_scaler.backward_transform(mu_f)
+        up_bnd_y = self.y_scaler.backward_transform(mu_f + std_f[:, None])
+        dn_bnd_y = self.y_scaler.backward_transform(mu_f - std_f[:, None])
+        std_y = 0.5 * (up_bnd_y - dn_bnd_y)
+        err = mu_y - ys
+        mae, mse = np.mean(np.abs(err)), np.mean(err ** 2.)
+        mnlp = 0.5 * np.mean((err / std_y) ** 2 + np.log(2 * np.pi * std_y ** 2))
+        nmse = mse / np.var(ys)
+        metrics = {'MAE': mae, 'NMAE': mae / np.std(ys), 'MSE': mse, 'NMSE': nmse, 'MNLP': mnlp, 'SCORE': nmse / (1 + np.exp(-mnlp)),
+                   'CV_LPD': sum(st['sum_log_marginal'] for st in fold_stats) / n,
+                   'CV_LOG_JOINT': sum(st['log_joint'] for st in fold_stats)}
+        return mu_y, std_y, metrics, fold_stats
+
     def loo(self, X=None, y=None, block=1):
         """Exact leave-block-out predictions of training rows, without a refit: (mu_y (n,1), std_y (n,1), metrics).  Row i is predicted
         from the fit on all training rows except the `block` consecutive rows of its block (block=1: leave-one-out; 1..64; permute the
