@@ -225,6 +225,51 @@ int scfgp_sample_argmax(scfgp_ctx* ctx, const double* Xs, int64_t T, const doubl
 int scfgp_sample_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* W, int nsamp, const int64_t* sidx, int mode,
                       double* val, double* grad);
 
+/* ---- acquisition functions over a pool (no reference counterpart) -------------------------------------------------------------------------
+ * scfgp_acquire: UCB, probability of improvement, expected improvement, log-EI and max-value entropy search at every row of a pool, the
+ * best eligible row, and the input gradient of the acquisition value -- the criteria of a Bayesian-optimisation loop as a by-product of
+ * scfgp_predict's chunk.  Everything is in scaled-y units (scfgp_predict's).  With sgn = +1, or -1 when `minimize` is set, u = sgn mu*(x),
+ * sigma = sigma_f = sqrt(kappa v) for noise == 0 (the spread of scfgp_sample's noise-free functions; v = ||Li phi(x)||^2) or
+ * sigma = sigma* = sqrt(kappa (1 + v)) for noise != 0 (pred_func's std), Phi / phi the standard normal CDF / PDF, lam = phi / Phi and
+ * h(g) = g Phi(g) + phi(g):
+ *     kind 0  UCB    u + beta sigma                                             par = [beta], beta >= 0
+ *     kind 1  PI     Phi(g),   g = (u - sgn best - xi) / sigma                  par = [best, xi], xi >= 0
+ *     kind 2  EI     sigma h(g)                                                 par = [best, xi]
+ *     kind 3  LOGEI  log sigma + log h(g): EI's logarithm, finite where EI underflows
+ *     kind 4  MES    (1 / n*) sum_s [ g_s lam(g_s) / 2 - log Phi(g_s) ],  g_s = (sgn f*_s - u) / sigma    no par; fstar (nstar = n*), 1 <= n* <= 1024
+ * fstar is what scfgp_sample_argmax(..., mode <= 1, the same minimize) returns in val; every MES term is >= 0.  The acquisition is always
+ * maximised, whatever minimize is.  sigma_f is formed from the fp64 v itself, never as sqrt(sigma*^2 - kappa).  All acquisition arithmetic
+ * is fp64 in every compute mode; only mu and v come from the context's precision (SCFGP_F16X3 contexts run fp32 mode's kernels and agree
+ * with it bit for bit).  The tail forms (scfgp_amd/csrc/acquire.hip) keep log Phi, lam and log h accurate for very negative g; a MES term
+ * loses absolute eps g^2 there, where two g^2 / 2 cancel.
+ * Outputs, each may be NULL, but not acq, idx and grad all together:
+ *     acq (T)        the value of every row
+ *     idx, val (1)   row t is eligible iff w == NULL or w[t] > 0 (scfgp_sample_argmax's meaning and host-side checks); idx[0] = the lowest
+ *                    eligible t at which acq is largest, val[0] = acq[idx[0]] bit for bit; scfgp_sample_argmax's merge rule at every level,
+ *                    the running best stays on the device across chunks; val needs idx
+ *     mu, sd (T)     mu* with scfgp_predict's bits (the same partial sums in the same order) and the sigma used (with noise != 0:
+ *                    scfgp_predict's std bit for bit)
+ *     grad (T x D)   d acq / d x = sgn a_u d mu* / d x + a_sigma d sigma / d x with scfgp_predict_grad's kernels (a_u, a_sigma: the partials
+ *                    of the value in u and sigma); in mode 1 chained through the X scaler's derivative
+ * mode 0: scaled rows; 1: column-selected raw rows through the registered X scaler.  There is no raw-y mode: the y scaler's backward
+ * transform is not affine, so EI in raw y units has no closed form (as scfgp_predict_cov).
+ * Bounds: T >= 1 without limit: the rows go through in chunks; device memory beside the chunk buffers is 3 T doubles (mu, sd, acq) plus
+ * T x D for grad.
+ * Guarantees: a row's acq, mu, sd and grad depend only on the row, the factors, the parameters and the call's scalars and fstar -- not on T,
+ * the row's position, the chunk or w.  idx and val do not change when the pool is appended to itself.  The MES sum over the samples runs in
+ * one fixed order that depends on n* alone.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xs, alpha or Li, T < 1, a bad kind or mode, npar not matching
+ * the kind, NULL par where the kind needs one, beta < 0 or xi < 0, kind 4 with NULL fstar or nstar outside [1, 1024], fstar given for
+ * another kind, a missing X scaler in mode 1, parameters not set, a negative w, no positive w, no output requested, val without idx.
+ * SCFGP_ENONFINITE for a non-finite par, fstar or w (on the host, before any device work) and for an eligible row whose mu, sigma or value
+ * is non-finite or whose sigma is 0 (found on the device); a non-finite row with w = 0 is not an error and its acq is whatever comes out.
+ * The outputs are untouched in every error case.  Row-sharded use: each rank calls it on its rows and the caller merges (val, idx + offset)
+ * by the merge rule.  Out of scope: top-k and batch (q-) acquisitions, raw-y acquisitions, knowledge gradient, factors or f* kept on the
+ * device between calls. */
+int scfgp_acquire(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
+                  int kind, const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize,
+                  double* acq, int64_t* idx, double* val, double* mu, double* sd, double* grad);
+
 /* ---- joint posterior covariance between test points (no reference counterpart: the reference reports the marginals only) -------
  * Under the weight posterior w ~ N(alpha, kappa A^-1) above, two function values have covariance kappa phi(x)^T A^-1 phi(x'); with
  * A^-1 = Li^T Li that is

@@ -45,6 +45,9 @@ SIGNATURES = {
     'scfgp_sample_argmax': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_uint64, C.c_int,
                                       C.c_int, _c_i64_p, _c_double_p]),
     'scfgp_sample_grad': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int, _c_i64_p, C.c_int, _c_double_p, _c_double_p]),
+    'scfgp_acquire': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.c_int, _c_double_p, C.c_int,
+                                _c_double_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_double_p, _c_i64_p, _c_double_p, _c_double_p, _c_double_p,
+                                _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_forget': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p,

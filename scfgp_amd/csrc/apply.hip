@@ -553,6 +553,7 @@ void ApplyKernels<T>::rowpredict(const Geom& g, const double* mupart, const doub
     hipLaunchKernelGGL((rowstats_kernel<1>), dim3(nblocks), dim3(256), 0, st, mupart, vpart, apply_njt<T>(g),
                        (const double*)nullptr, sc, mu, sd, (double*)nullptr, g.N, g.Np);
 }
+template <typename T> int ApplyKernels<T>::partials(const Geom& g) { return apply_njt<T>(g); }
 // r = y - mu on the live rows, 0 on the padding rows (the side vector of the update's Gram product: scfgp_condition)
 __global__ __launch_bounds__(256) void rowresidual_kernel(const double* __restrict__ mupart, int njt, const double* __restrict__ y,
                                                           double* __restrict__ r, int64_t N, int64_t Np) {

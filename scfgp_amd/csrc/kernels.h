@@ -134,6 +134,8 @@ struct ApplyKernels {
                            hipStream_t st);
     // residual of new rows under the old mean (scfgp_condition): r[n] = y[n] - sum_jt mupart[jt][n] for n < N, 0 on the padding rows
     static void rowresidual(const Geom& g, const double* mupart, const double* y, double* r, hipStream_t st);
+    // slices per row of vpart / mupart: the column tiles of the launch plan (depends on K alone)
+    static int partials(const Geom& g);
 };
 
 // ---- apply_f16.hip, gram_f16.hip: compute mode SCFGP_F16X3 -- the big products as a three-term fp16 split (a labelled secondary mode) ----
@@ -268,6 +270,25 @@ void sample_argmax_product(const Geom& g, const T* Phi, const T* Wt, int nsamp, 
                            const SampleArgmaxBufs& b, hipStream_t st);
 // bestv (nsamp) <- the y scaler's backward transform of mode ymode, by the kernel sample_product applies it with
 void sample_argmax_finalize(double* bestv, int nsamp, int ymode, const double* ysp, const Scal* sc, hipStream_t st);
+
+// ---- acquire.hip, acquisition functions over a pool (scfgp_acquire) ------------------------------------------------------------------------
+// the call's scalars: kind 0 UCB (par = [beta]), 1 PI, 2 EI, 3 LOGEI (par = [best, xi]), 4 MES (fstar: nstar sampled maxima on the device)
+struct AcquireSpec { int kind; double par[2]; const double* fstar; int nstar; int noise; int minimize; };
+// workgroup records of the argmax over a chunk of Np rows
+inline int64_t acquire_blocks(int64_t Np) { return Np / 256; }
+// mu, sd, acq: the chunk's rows of the call's T-sized arrays; au, as (Np): the partials d acq / d u, d acq / d sigma of the chunk's rows;
+// pv, pt: the records of the chunk's workgroups (value, chunk-local row or -1); bestv, bestt (1 each): the running best over the chunks so
+// far; flag: set where an eligible row has a non-finite mu, sigma or value, or sigma = 0
+struct AcquireBufs { double* mu; double* sd; double* acq; double* au; double* as; double* pv; long long* pt; double* bestv; long long* bestt; int* flag; };
+// rows n < N from the chunk's partials (njt slices each, summed in rowpredict's order): mu, sd = sqrt(kappa v) or (noise) sqrt(kappa (1 + v)),
+// the acquisition value and its partials
+void acquire_rows(const Geom& g, int njt, const double* mupart, const double* vpart, const Scal* sc, const AcquireSpec& a, const AcquireBufs& b,
+                  hipStream_t st);
+// the chunk's best eligible row (w == NULL: all; else w[n] > 0; w: Np entries) merged into bestv / bestt with rows counted from t0
+// (`first`: the running best starts empty); the largest value wins, ties go to the lowest row
+void acquire_argmax(const Geom& g, const double* w, int64_t t0, int first, const AcquireBufs& b, hipStream_t st);
+// grad (N x D, holding d mu / d x) <- sgn au grad + as dsd
+void acquire_grad(const Geom& g, const AcquireBufs& b, int minimize, const double* dsd, double* grad, hipStream_t st);
 
 // ---- samplegrad.hip, values and input gradients of sample functions, one sample per row (scfgp_sample_grad) ----------------------------
 // leading dimension of WT: a weight row is contiguous, 16-byte aligned and zero past K

@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "tile_engine.h"
 #include "yscale.h"
+#include "argmax.h"
 
 // Philox4x64-10 of counter (c0, c1, 0, 0) and key (k0, k1)
 __device__ __forceinline__ void philox4x64_10(uint64_t c0, uint64_t c1, uint64_t k0, uint64_t k1, uint64_t (&o)[4]) {
@@ -131,16 +132,6 @@ __device__ __forceinline__ void load_row4(const double* __restrict__ p, double (
 // same text for both, so the value of an element is the same bits in both.
 constexpr int SAMPLE_FLUSH = 128;
 
-// One merge rule for every level of scfgp_sample_argmax (lanes, waves, workgroups, column-tile launches, chunks; ranks on the caller's
-// side): record a = (v, t) beats b iff key(a) > key(b), or the keys are equal and a.t < b.t; key = v, or -v when minimising (exact).
-// t < 0 marks the empty record, which loses to everything.  On records with finite values the rule is a total order, so the winner
-// does not depend on how the records are grouped.
-__device__ __forceinline__ bool argmax_beats(double va, long long ta, double vb, long long tb, bool minimize) {
-    if (ta < 0) return false;
-    if (tb < 0) return true;
-    const double ka = minimize ? -va : va, kb = minimize ? -vb : vb;
-    return ka > kb || (ka == kb && ta < tb);
-}
 // the argmax epilogue's destination: w the chunk's weights (NULL: every row is eligible; row n is eligible iff w[n] > 0), pv / pt the
 // workgroups' records ([gridDim.x][nsamp]: value, chunk-local row or -1), flag set where an eligible row's value is not finite
 struct SampleArgmaxOut {

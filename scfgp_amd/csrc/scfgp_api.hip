@@ -823,6 +823,16 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_acquire: predict_chunk with acquire.hip's row kernels in rowpredict's place (the same partials in the same order, so mu has
+    // scfgp_predict's bits), then the chunk's best eligible row into the call's running best
+    static int acquire_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const AcquireSpec& a, const double* w, int64_t t0, const AcquireBufs& b) {
+        features(c, g);
+        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
+        acquire_rows(g, ApplyKernels<T>::partials(g), c->p_mupart, c->p_vpart, c->d_sc, a, b, c->st);
+        acquire_argmax(g, w, t0, t0 == 0, b, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
     // scfgp_sample_grad: f and d f / d x~ of the chunk's rows, each under its own sample's weights (samplegrad.hip; FT: grad_operand)
     static int sample_grad_chunk(scfgp_ctx* c, const Geom& g, const double* WT, const double* sidx, int64_t t0, int nsamp, double* val,
                                  double* grad) {
@@ -1601,6 +1611,118 @@ extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, co
     if (flag) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
     memcpy(idx, &h[nsamp], sizeof(int64_t) * nsamp);
     if (val) memcpy(val, h.data(), sizeof(double) * nsamp);
+    return SCFGP_OK;
+}
+
+// predict_impl's pipeline (the factor pass, the feed of [Xs | w], mu / sd / acq of all T rows on the device until the end) with
+// acquire.hip's kernels in rowpredict's place and scfgp_sample_argmax's running best and non-finite flag.  With grad, predict_grad_chunk
+// gets the sigma in use as its sd, so its d sigma / d x is that sigma's; the combine runs before the X scaler's chain rule, which is
+// linear per column.  par, fstar and w are checked on the host before any device work; the outputs are written on success only.
+static constexpr int ACQUIRE_MAX_STAR = 1024;
+extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int kind,
+                             const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize, double* acq,
+                             int64_t* idx, double* val, double* mu, double* sd, double* grad) {
+    if (!c) return SCFGP_EARG;
+    auto bad = [&](const char* what) { c->err = std::string("acquire: ") + what; return SCFGP_EARG; };
+    if (!Xs || !alpha || !Li) return bad("NULL Xs, alpha or Li");
+    if (T < 1) return bad("T must be at least 1");
+    if (kind < 0 || kind > 4) return bad("kind must lie in 0..4");
+    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
+    const int need = kind == 0 ? 1 : (kind == 4 ? 0 : 2);
+    if (npar != need) return bad("npar does not match the kind");
+    if (need && !par) return bad("NULL par");
+    if (kind == 4 && (!fstar || nstar < 1 || nstar > ACQUIRE_MAX_STAR)) return bad("MES needs fstar with 1 <= nstar <= 1024");
+    if (kind != 4 && (fstar || nstar)) return bad("fstar given for a kind other than MES");
+    if (!acq && !idx && !grad) return bad("no output requested (acq, idx and grad are all NULL)");
+    if (val && !idx) return bad("val without idx");
+    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
+    if (!c->have_params) return bad("parameters not set");
+    AcquireSpec spec = {kind, {0.0, 0.0}, nullptr, kind == 4 ? nstar : 0, noise ? 1 : 0, minimize ? 1 : 0};
+    bool nonfinite = false;
+    for (int i = 0; i < need; ++i) { spec.par[i] = par[i]; if (!std::isfinite(par[i])) nonfinite = true; }
+    for (int i = 0; i < spec.nstar; ++i) if (!std::isfinite(fstar[i])) nonfinite = true;
+    if (!nonfinite && kind == 0 && par[0] < 0.0) return bad("beta must not be negative");
+    if (!nonfinite && (kind >= 1 && kind <= 3) && par[1] < 0.0) return bad("xi must not be negative");
+    if (w) {
+        bool positive = false;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "acquire: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) positive = true;
+        }
+        if (!nonfinite && !positive) return bad("no row has a positive weight");
+    }
+    if (nonfinite) { c->err = "acquire: non-finite par, fstar or weights"; return SCFGP_ENONFINITE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if (grad && (rc = ensure_pred_grad(c, true))) return rc;
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const int64_t nrec = acquire_blocks(PRED_ROWS);
+    RowFeed feed; DevTmp d_out, d_grad, work;     // Li / two chunks of [Xs | w] | mu, sd, acq of all T rows | grad of all T rows | chunk scratch
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0)), (int64_t)g0.K * g0.K))) return rc;
+    if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 3 * T))) return rc;
+    // work: w of the chunk, padded | a_u | a_sigma | d sigma / d x of the chunk | records of two chunks | running best, flag | fstar
+    const int64_t n_dsd = grad ? PRED_ROWS * g0.D : 0;
+    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + n_dsd + 4 * nrec + 3 + ACQUIRE_MAX_STAR)))) return rc;
+    double* d_mu = d_out; double* d_sd = d_out + T; double* d_acq = d_out + 2 * T;
+    double* d_w = work; double* d_au = work + PRED_ROWS; double* d_as = work + 2 * PRED_ROWS; double* d_dsd = work + 3 * PRED_ROWS;
+    double* d_rec = d_dsd + n_dsd;
+    double* d_bestv = d_rec + 4 * nrec;
+    long long* d_bestt = (long long*)(d_bestv + 1);
+    int* d_flag = (int*)(d_bestv + 2);
+    double* d_fstar = d_bestv + 3;
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
+    if (kind == 4) {
+        HIPCHK(c, hipMemcpyAsync(d_fstar, fstar, sizeof(double) * nstar, hipMemcpyHostToDevice, c->st));
+        spec.fstar = d_fstar;
+    }
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, nullptr, alpha, c->alpha_pred()))) return rc;
+    if (grad) {
+        if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D))) return rc;
+        DISPATCH(c, grad_operand, c);
+        DISPATCH(c, type_factor, c, c->d_T1, nullptr, c->p_Li);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const int64_t t0 = i * PRED_ROWS;
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *wraw;
+        if ((rc = feed.acquire(i, &x, &wraw))) return rc;
+        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if (!grad && (rc = feed.release(i))) return rc;
+        const AcquireBufs b = {d_mu + t0, d_sd + t0, d_acq + t0, d_au, d_as, d_rec + (i & 1) * nrec, (long long*)(d_rec + (2 + (i & 1)) * nrec),
+                               d_bestv, d_bestt, d_flag};
+        if ((rc = DISPATCH(c, acquire_chunk, c, g, LiT, spec, w ? d_w : nullptr, t0, b))) return rc;
+        if (grad) {
+            double* gm = d_grad + t0 * g0.D;
+            if ((rc = DISPATCH(c, predict_grad_chunk, c, g, LiT, d_sd + t0, gm, d_dsd))) return rc;
+            acquire_grad(g, b, spec.minimize, d_dsd, gm, c->st);
+            if (mode == 1 && c->xs_mode) xgrad_chunk(x, g.N, g0.D, c->xs_mode, c->d_xscale, gm, nullptr, c->st);
+            if ((rc = feed.release(i))) return rc;
+        }
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    HIPCHK(c, hipGetLastError());
+    double h[3];                                                  // the running best and the flag first: the outputs are written on success only
+    HIPCHK(c, hipMemcpyAsync(h, d_bestv, sizeof(h), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    int flag;
+    memcpy(&flag, &h[2], sizeof(int));
+    if (flag) { c->err = "acquire: an eligible row has a non-finite mu, sigma or value, or sigma = 0"; return SCFGP_ENONFINITE; }
+    if (acq) HIPCHK(c, hipMemcpyAsync(acq, d_acq, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (mu) HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (sd) HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (grad) HIPCHK(c, hipMemcpyAsync(grad, d_grad, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (idx) memcpy(idx, &h[1], sizeof(int64_t));
+    if (val) val[0] = h[0];
     return SCFGP_OK;
 }
 

@@ -353,6 +353,82 @@ class HipEngine(object):
         self._check(rc, 'sample_argmax')
         return idx, val
 
+    ACQUIRE_KINDS = {'ucb': 0, 'pi': 1, 'ei': 2, 'logei': 3, 'mes': 4}
+    ACQUIRE_MODES = {'scaled': 0, 'raw': 1}
+    ACQUIRE_WANT = ('acq', 'argmax', 'mu', 'sd', 'grad')
+
+    def acquire(self, Xs, alpha, Li, kind, best=None, xi=0.0, beta=None, fstar=None, w=None, mode='scaled', noise=False, minimize=False,
+                want=('acq', 'argmax')):
+        """Acquisition functions over the pool Xs (include/scfgp_hip.h: scfgp_acquire), in scaled y units.  kind 'ucb' (beta), 'pi',
+        'ei', 'logei' (best, xi) or 'mes' (fstar: sampled maxima, what sample_argmax returns in val with mode 'scaled' / 'raw' and the
+        same minimize).  noise: the predictive std sigma* instead of the latent sigma_f.  w (T,): row t is eligible iff w[t] > 0.  mode
+        'scaled' or 'raw' (through the registered X scaler).  want: any of 'acq' (T,), 'argmax' (idx, val: the lowest eligible row with
+        the largest value, and that value), 'mu' (T,), 'sd' (T,), 'grad' (T, D; (T, D_raw) in mode 'raw' with zero columns where the
+        scaler dropped a constant column).  Returns a dict with the keys asked for ('argmax' gives 'idx' and 'val')."""
+        if kind not in self.ACQUIRE_KINDS:
+            raise ValueError('acquire: kind must be one of %s' % sorted(self.ACQUIRE_KINDS))
+        if mode not in self.ACQUIRE_MODES:
+            raise ValueError('acquire: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for k in want:
+            if k not in self.ACQUIRE_WANT:
+                raise ValueError('acquire: want holds %r; allowed: %s' % (k, self.ACQUIRE_WANT))
+        k, m = self.ACQUIRE_KINDS[kind], self.ACQUIRE_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('acquire: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        D_in = Xs.shape[1]
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        T = Xs.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        alpha, Li = self._factors(alpha, Li)
+        if k == 0:
+            if beta is None:
+                raise ValueError("acquire: kind 'ucb' needs beta")
+            par = np.array([beta], dtype=np.float64)
+        elif k == 4:
+            par = None
+        else:
+            if best is None:
+                raise ValueError('acquire: kind %r needs best' % kind)
+            par = np.array([best, xi], dtype=np.float64)
+        if fstar is not None:
+            fstar = np.ascontiguousarray(fstar, dtype=np.float64).reshape(-1)
+        out = {}
+        acq = np.empty(T) if 'acq' in want else None
+        idx = np.empty(1, dtype=np.int64) if 'argmax' in want else None
+        val = np.empty(1) if 'argmax' in want else None
+        mu = np.empty(T) if 'mu' in want else None
+        sd = np.empty(T) if 'sd' in want else None
+        grad = np.empty((T, self.D)) if 'grad' in want else None
+        rc = self.lib.scfgp_acquire(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), k, dptr(par), 0 if par is None else par.size,
+                                    dptr(fstar), 0 if fstar is None else fstar.size, m, int(bool(noise)), int(bool(minimize)), dptr(acq),
+                                    None if idx is None else idx.ctypes.data_as(_lib._c_i64_p), dptr(val), dptr(mu), dptr(sd), dptr(grad))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('acquire: %s' % self.last_error())
+        self._check(rc, 'acquire')
+        if acq is not None:
+            out['acq'] = acq
+        if idx is not None:
+            out['idx'] = int(idx[0]); out['val'] = float(val[0])
+        if mu is not None:
+            out['mu'] = mu
+        if sd is not None:
+            out['sd'] = sd
+        if grad is not None:
+            out['grad'] = _scatter(grad, cols, D_in) if cols is not None else grad
+        return out
+
     def sample_grad(self, Xs, W, sidx=None, mode='scaled', want_val=True):
         """Values and input gradients of sample functions, one sample per row (include/scfgp_hip.h: scfgp_sample_grad): (val (T,),
         grad (T, D)) with val[t] = phi(x_t)^T W[:, sidx[t]] and grad[t] its gradient in x_t.  W (K, nsamp) as sample_weights returns

@@ -296,6 +296,19 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler)
         return self.engine.sample_argmax(Xs_raw, alpha, Li, nsamp, seed=seed, w=weights, mode='y', minimize=minimize)
 
+    def acquire_raw(self, Xs_raw, x_scaler, alpha, Li, kind, **kw):
+        """Acquisition functions over the raw pool rows Xs_raw, in scaled y units (engine.acquire with mode 'raw'; kw: its best, xi,
+        beta, fstar, w, noise, minimize, want)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.acquire(Xs_raw, alpha, Li, kind, mode='raw', **kw)
+
+    def sample_argmax_raw(self, Xs_raw, x_scaler, alpha, Li, nsamp, seed=0, weights=None, minimize=False):
+        """Per-sample maximisers (idx, val) over the raw pool rows Xs_raw with val in SCALED y units: the f* of acquire_raw's 'mes'."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.sample_argmax(Xs_raw, alpha, Li, nsamp, seed=seed, w=weights, mode='raw', minimize=minimize)
+
     def sample_weights(self, alpha, Li, nsamp, seed=0):
         """W (K, nsamp): the weights of sample_y's functions at the shared parameter vector (engine.sample_weights)."""
         self._sync_params()

@@ -340,6 +340,93 @@ class SCFGP(object):
         val_y, _ = owner.sample_grad_raw(X_best, self.X_scaler, self.y_scaler, W, sidx=np.arange(nsamples), y_units=True)
         return X_best, val_y, idx, converged
 
+    def _acquire_best(self, best, minimize):
+        """the incumbent in scaled y units: `best` (raw y) through the y scaler, or the best observed training target"""
+        if best is None:
+            y = np.asarray(self.y, dtype=np.float64)
+            return float(y.min() if minimize else y.max())
+        return float(np.asarray(self.y_scaler.forward_transform(np.array([[float(best)]]))).reshape(-1)[0])
+
+    @staticmethod
+    def _acquire_starts(X_pool, acq, weights, starts):
+        """the `starts` best distinct eligible pool rows by acq: descending value, ties to the lowest index, a row that repeats an
+        earlier start's coordinates skipped"""
+        acq = np.asarray(acq, dtype=np.float64).reshape(-1)
+        ok = np.ones(acq.size, dtype=bool) if weights is None else np.asarray(weights).reshape(-1) > 0
+        order = np.flatnonzero(ok)
+        order = order[np.argsort(-acq[order], kind='stable')]
+        picked, seen = [], set()
+        for t in order:
+            key = np.ascontiguousarray(X_pool[t], dtype=np.float64).tobytes()
+            if key not in seen:
+                seen.add(key); picked.append(int(t))
+                if len(picked) == int(starts):
+                    break
+        return np.array(picked, dtype=np.int64)
+
+    def _acquire_owner(self, who):
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('%s needs the library\'s pred_func (build_hip_models / fit); got %r' % (who, self.pred_func))
+        return owner
+
+    def acquire(self, X_pool, kind, best=None, xi=0.0, beta=None, fstar=None, weights=None, noise=False, minimize=False,
+                want=('acq', 'argmax')):
+        """Acquisition function `kind` ('ucb', 'pi', 'ei', 'logei', 'mes') at every row of the raw pool X_pool (T,D), and the best
+        eligible row (include/scfgp_hip.h: scfgp_acquire).  best: the incumbent in RAW y units (it goes through the y scaler's forward
+        transform); None: the best observed training target in the direction of minimize.  xi >= 0: the improvement margin and beta >= 0
+        UCB's weight, both in SCALED y units; fstar ('mes'): sampled maxima in scaled y units (see mes()).  The returned acq, val,
+        mu and sd are in SCALED y units, the space the model is Gaussian in: the y scaler's backward transform is not affine, so EI
+        in raw y has no closed form.  grad is d acq / d x with x in raw X units.  The acquisition is always maximised;
+        minimize says that small targets are good.  noise: use the predictive std sigma* instead of the latent sigma_f.  Returns the
+        dict of engine.acquire (want: 'acq', 'argmax' -> 'idx', 'val', 'mu', 'sd', 'grad')."""
+        owner = self._acquire_owner('acquire')
+        kw = dict(w=weights, noise=noise, minimize=minimize, want=want)
+        if kind == 'ucb':
+            kw['beta'] = beta
+        elif kind == 'mes':
+            kw['fstar'] = fstar
+        else:
+            kw['best'] = self._acquire_best(best, minimize); kw['xi'] = xi
+        return owner.acquire_raw(X_pool, self.X_scaler, self.alpha, self.Li, kind, **kw)
+
+    def mes(self, X_pool, nsamples, seed=0, weights=None, minimize=False):
+        """Max-value entropy search over the raw pool: one sample_argmax call for nsamples draws of the maximum f* in scaled y units,
+        then acquire('mes') on the same pool.  Returns acquire's dict with 'fstar' added."""
+        owner = self._acquire_owner('mes')
+        _, fstar = owner.sample_argmax_raw(X_pool, self.X_scaler, self.alpha, self.Li, int(nsamples), seed=seed, weights=weights,
+                                           minimize=minimize)
+        out = self.acquire(X_pool, 'mes', fstar=fstar, weights=weights, minimize=minimize)
+        out['fstar'] = fstar
+        return out
+
+    def acquire_maximize(self, X_pool, kind, best=None, xi=0.0, beta=None, fstar=None, weights=None, noise=False, minimize=False,
+                         bounds=None, starts=8, max_iter=60, gtol=1e-6):
+        """Continuous maximisers of an acquisition function: the `starts` best distinct eligible rows of the raw pool by acquire(),
+        refined off the grid by projected-gradient ascent in raw X (scfgp_amd.ascent; one acquire call with grad per step for all
+        starts).  bounds = (lo, hi), scalars or (D,), default the pool's per-column minimum and maximum.  Returns X_best (n, D) raw
+        points inside the bounds, val (n,) the acquisition values there (scaled units), idx_start (n,) the pool rows the ascents started
+        from (descending value), converged (n,) bool; n = min(starts, distinct eligible rows).  No value is below its start row's."""
+        from .ascent import ascend
+        owner = self._acquire_owner('acquire_maximize')
+        X_pool = np.asarray(X_pool, dtype=np.float64)
+        kw = dict(noise=noise, minimize=minimize)
+        if kind == 'ucb':
+            kw['beta'] = beta
+        elif kind == 'mes':
+            kw['fstar'] = fstar
+        else:
+            kw['best'] = self._acquire_best(best, minimize); kw['xi'] = xi
+        acq = owner.acquire_raw(X_pool, self.X_scaler, self.alpha, self.Li, kind, w=weights, want=('acq',), **kw)['acq']
+        idx = self._acquire_starts(X_pool, acq, weights, starts)
+        lo, hi = (X_pool.min(0), X_pool.max(0)) if bounds is None else bounds
+
+        def fg(X, sidx):                                        # one function for every row: sidx is ignored
+            r = owner.acquire_raw(X, self.X_scaler, self.alpha, self.Li, kind, want=('acq', 'grad'), **kw)
+            return r['acq'], r['grad']
+        X_best, val, converged, _ = ascend(fg, X_pool[idx], np.zeros(idx.size, dtype=np.int64), lo, hi, max_iter=max_iter, gtol=gtol)
+        return X_best, val, idx, converged
+
     def predict_cov(self, Xs, Xs2=None, noise=False):
         """Joint posterior covariance of the fitted model's function values between the raw rows Xs and Xs2 (None: among the rows of
         Xs, a bit-for-bit symmetric matrix): (T, T2) = kappa phi(x)^T A^-1 phi(x').  Inputs are in raw X units; the covariance is that

@@ -30,5 +30,25 @@ if ctx:
                  (xp, 1, None, 0, xp, 2, 0, xp), (xp, 1, None, 0, xp, 0, 0, xp)]:     # the last: parameters not set
         assert lib.scfgp_predict_cov(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'predict_cov')
         n += 1
+# scfgp_acquire: the same -- every argument check precedes the first device call
+ip = C.cast((C.c_int64 * 1)(0), C.POINTER(C.c_int64))
+assert lib.scfgp_acquire(None, xp, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None) == -1
+n += 1
+if ctx:
+    for args in [(None, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None),      # NULL Xs
+                 (xp, 0, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None),        # T < 1
+                 (xp, 1, None, xp, xp, 5, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None),        # kind
+                 (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 2, 0, 0, xp, ip, xp, None, None, None),        # mode
+                 (xp, 1, None, xp, xp, 2, xp, 1, None, 0, 0, 0, 0, xp, ip, xp, None, None, None),        # npar
+                 (xp, 1, None, xp, xp, 2, None, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None),      # NULL par
+                 (xp, 1, None, xp, xp, 4, None, 0, None, 3, 0, 0, 0, xp, ip, xp, None, None, None),      # MES without fstar
+                 (xp, 1, None, xp, xp, 4, None, 0, xp, 1025, 0, 0, 0, xp, ip, xp, None, None, None),     # nstar
+                 (xp, 1, None, xp, xp, 2, xp, 2, xp, 1, 0, 0, 0, xp, ip, xp, None, None, None),          # fstar for EI
+                 (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, None, None, None, xp, xp, None),      # no output
+                 (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, None, xp, None, None, None),      # val without idx
+                 (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 1, 0, 0, xp, ip, xp, None, None, None),        # no X scaler
+                 (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None)]:       # parameters not set
+        assert lib.scfgp_acquire(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'acquire')
+        n += 1
 if ctx: lib.scfgp_destroy(ctx)
 print('host-side calls under ASan/UBSan:', n + 4, 'ok')
