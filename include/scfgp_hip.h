@@ -193,7 +193,8 @@ int scfgp_sample(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alph
  * are untouched in both cases.  Row-sharded use needs no communicator: each rank calls it on its rows and the caller merges the
  * (val, idx + offset) pairs by the rule above (for mode 2, merge mode-1 values and transform afterwards, or rely on the transform being
  * monotone).  Continuous refinement of a maximiser off the pool: scfgp_sample_grad gives the value and input gradient of a sample
- * function at any point.  Out of scope: top-k per sample, and weights or factors kept on the device between calls. */
+ * function at any point.  A batch chosen for improvement from the same sample functions: scfgp_select_qei.  Out of scope: top-k per
+ * sample, and weights or factors kept on the device between calls. */
 int scfgp_sample_argmax(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
                         uint64_t seed, int mode, int minimize, int64_t* idx, double* val);
 /* scfgp_sample_grad: values and input gradients of sample functions, one sample per row -- what a gradient method needs to move each
@@ -264,8 +265,8 @@ int scfgp_sample_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double*
  * SCFGP_ENONFINITE for a non-finite par, fstar or w (on the host, before any device work) and for an eligible row whose mu, sigma or value
  * is non-finite or whose sigma is 0 (found on the device); a non-finite row with w = 0 is not an error and its acq is whatever comes out.
  * The outputs are untouched in every error case.  Row-sharded use: each rank calls it on its rows and the caller merges (val, idx + offset)
- * by the merge rule.  Out of scope: top-k and batch (q-) acquisitions, raw-y acquisitions, knowledge gradient, factors or f* kept on the
- * device between calls. */
+ * by the merge rule.  Batch (q-) expected improvement: scfgp_select_qei.  Out of scope: top-k, raw-y acquisitions, knowledge gradient,
+ * factors or f* kept on the device between calls. */
 int scfgp_acquire(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
                   int kind, const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize,
                   double* acq, int64_t* idx, double* val, double* mu, double* sd, double* grad);
@@ -452,6 +453,52 @@ int scfgp_select(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, c
  * (scfgp_sample_grad) can be appended to Xc. */
 int scfgp_select_iv(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* wr,
                     const double* Li, int m, int mode, int64_t* idx, double* red, double* var, double* ivar, double* std_after);
+
+/* ---- greedy Monte-Carlo batch expected improvement over a pool (q-EI; no reference counterpart) ------------------------------------------
+ * scfgp_select_qei: which m pool rows should be tried together, for improvement over the incumbent?  A sample function of this model is a
+ * function (K weights; the same seed gives the same functions on any rows), so joint draws over the whole pool are exact and cost one
+ * product Phi* W: no T x T covariance is formed.  With F[t][s] = f_s(x_t) what scfgp_sample(Xc, .., nsamp, seed, mode, noise = 0) returns,
+ * bit for bit, sgn = +1, or -1 when `minimize` is set, u_ts = sgn F[t][s] and b = sgn best + xi (scaled-y units, as scfgp_acquire), the
+ * Monte-Carlo q-EI of a batch B is
+ *     qEI(B) = (1 / nsamp) sum_s max( max_{t in B} u_ts - b, 0 )
+ * It is monotone and submodular in B (each term is a max over a set), so the greedy batch is a (1 - 1/e) maximiser, the argument
+ * scfgp_select rests on.  Row t is eligible iff w == NULL or w[t] > 0 (scfgp_sample_argmax's meaning and host-side checks).
+ *     start      m_s = b; with pending rows Xp (np x D, same mode; np = 0: none, Xp may then be NULL): m_s = max(b, max_r sgn f_s(xp_r)), the
+ *                maximum being what scfgp_sample_argmax on Xp returns in val (its product and merge kernels: scfgp_sample's bits)
+ *     step j     score_t = (1 / nsamp) sum_s max(u_ts - m_s, 0)   for every row t
+ *                p_j = the lowest eligible, not yet taken t at which score_t is largest (scfgp_sample_argmax's merge rule)
+ *                gain[j] = score_{p_j}        m_s <- max(m_s, u_{p_j, s})
+ * Pending rows (chosen, not yet observed) enter through their sampled values: the fantasy treatment of asynchronous optimisation.  When
+ * every remaining score is 0 (no sample can still improve), the picks go to the lowest eligible untaken indices and their gain is 0;
+ * that is not an error.
+ * Outputs: idx (m): the picks in order, indices into the pool; gain (m, may be NULL); score0 (T, may be NULL): the scores of step 0 of
+ * every row, eligible or not -- the Monte-Carlo one-point EI given the pending rows; mstate (nsamp, may be NULL): m after the last pick;
+ * qei (2 doubles, may be NULL): [0] = (1 / nsamp) sum_s (m_s - b) at the start, the q-EI of the pending rows alone (0 without them), [1]
+ * the same after the last pick, the q-EI of pending rows plus picks; each is added by one thread in sample order.
+ * mode 0: scaled rows; 1: column-selected raw rows through the registered X scaler.  There is no raw-y mode (as scfgp_acquire) and no
+ * noise argument (as scfgp_sample_argmax).
+ * Bounds: 1 <= nsamp <= 1024, 1 <= m <= min(4096, number of eligible rows), 1 <= T <= 2^20, np >= 0 without limit (the pending rows go
+ * through the chunk pipeline).  The call owns T x nsamp doubles of F for its duration (a failed allocation is SCFGP_EHIP with the size in
+ * the message) and 2 T doubles of per-row state; nothing stays resident between calls.  Storing F costs 8 T nsamp bytes and makes a
+ * pick one read of it; recomputing Phi* W instead would cost 2 T K nsamp flops per pick.
+ * Guarantees: F is written by scfgp_sample's kernel and stays fp64 in every compute mode (SCFGP_F16X3 contexts run fp32 mode's kernels
+ * and agree with it bit for bit).  A row's score depends on the row's F values, m and nsamp only -- not on T, the row's position, the
+ * grid or w: a group of lanes whose width depends on nsamp alone (16 for nsamp <= 64, else 64) adds s = g, g + G, .. in ascending order,
+ * a fixed xor butterfly follows, then one division by nsamp.  m is exact (max).  So the picks of m1 < m2 are a prefix, bit for bit, in
+ * idx and gain; gain never increases; appending rows of weight 0, or duplicating the pool behind itself, changes nothing; and a later
+ * call with the first picks passed as pending rows (and masked) continues the same sequence with the same bits.  No step returns to the
+ * host: a pick is two eager launches on the context's stream; the host waits once after F is built (for the non-finite flag) and once
+ * at the end.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xc, alpha, Li or idx, T, m, nsamp or mode out of range,
+ * np < 0, np > 0 with NULL Xp, xi < 0, a missing X scaler in mode 1, parameters not set, a negative w, or fewer than m rows with a
+ * positive w.  SCFGP_ENONFINITE for a non-finite best, xi or w (on the host, before any device work) and for a non-finite sampled value
+ * of an eligible or pending row (found on the device); a non-finite row with w = 0 is not an error: its terms count as 0 in score0.
+ * The outputs are untouched in every error case.
+ * Out of scope: lazy-greedy pruning of the sweep, q-PI / q-UCB, gradients of q-EI in the inputs (continuous refinement goes through
+ * scfgp_sample_grad), a row-sharded pool, raw-y units, and F, W or factors kept on the device between calls. */
+int scfgp_select_qei(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Xp, int64_t np,
+                     const double* alpha, const double* Li, int nsamp, uint64_t seed, double best, double xi, int m, int mode,
+                     int minimize, int64_t* idx, double* gain, double* score0, double* mstate, double* qei);
 
 /* ---- staged evaluation for row-sharded data parallelism ---------------------------------
  * The objective needs three row sweeps separated by two K x K stages; with rows sharded

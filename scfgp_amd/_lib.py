@@ -58,6 +58,9 @@ SIGNATURES = {
                                _c_double_p, _c_double_p]),
     'scfgp_select_iv': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int,
                                   C.c_int, _c_i64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    'scfgp_select_qei': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int,
+                                   C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _c_i64_p, _c_double_p, _c_double_p,
+                                   _c_double_p, _c_double_p]),
     'scfgp_pass1': (C.c_int, [C.c_void_p]),
     'scfgp_factor': (C.c_int, [C.c_void_p]),
     'scfgp_pass2': (C.c_int, [C.c_void_p, C.c_int]),

@@ -407,3 +407,22 @@ void select_iv_init(const SelectBufs& b, const SelectIvBufs& iv, const T* C, con
 // pick j: idx[j], var[j], u_j as select_step; red[j] = kappa u_j . Q u_j, ivar[1] -= red[j]; then the sweep that downdates a and d and
 // leaves the next partials
 template <typename T> void select_iv_step(const SelectBufs& b, const SelectIvBufs& iv, const T* C, int j, const Scal* sc, hipStream_t st);
+
+// ---- selectqei.hip: greedy Monte-Carlo batch expected improvement over a pool (scfgp_select_qei) ----------------------------------------
+// F (T x nsamp fp64, row pitch nsamp): scfgp_sample's values of the pool, sgn = +1 or -1 (minimize).  Device state of one call: w (T: a
+// row is eligible iff w > 0; a picked row's is set to 0), ms (nsamp: the running per-sample maximum m of b, the pending rows and the
+// picks, in units sgn f), score0 (T: the scores of pick 0), pval / pidx (selectqei_blocks(T) records of the last sweep), idx / gain (m
+// each), qei (2), flag (an eligible row holds a non-finite value).
+struct SelectQeiBufs {
+    const double* F; int64_t T; int nsamp; double sgn;
+    double *w, *ms, *score0, *pval; long long* pidx;
+    long long* idx; double *gain, *qei; int* flag;
+};
+int selectqei_blocks(int64_t T);
+// start != 0: ms[s] = max(base, sgn pend[s]) (pend NULL: base) and qei[0]; start == 0: qei[1] from ms as it stands.  qei[.] =
+// (1 / nsamp) sum_s (ms[s] - base), by one thread in sample order
+void selectqei_state(const SelectQeiBufs& b, const double* pend, double base, int start, hipStream_t st);
+// the scores of every row against ms and the workgroups' records; j == 0 also writes score0 and raises the flag
+void selectqei_sweep(const SelectQeiBufs& b, int j, hipStream_t st);
+// folds the records: idx[j], gain[j], w[idx[j]] = 0, ms raised to the picked row
+void selectqei_commit(const SelectQeiBufs& b, int j, hipStream_t st);

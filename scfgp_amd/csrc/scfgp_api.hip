@@ -1228,7 +1228,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_forget, scfgp_loo and scfgp_select
+// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_select and scfgp_select_qei
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -1552,8 +1552,44 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
 
 // scfgp_sample's pipeline without the OutRing: the weights w travel as the feed's targets and reach the product's epilogue through
 // pack_data's zero-padded copy; per chunk the workgroups' records (two slots, alternating) are merged into nsamp running (value, row)
-// pairs on the device, which are all that the host fetches, once, with the non-finite flag.  w is checked on the host before any device
-// work, as scfgp_select does.
+// pairs on the device.  The run owns its buffers: bestv | bestt | flag (nsamp, nsamp, 1: contiguous) are valid once the context's
+// stream has drained.  xraw: the rows go through the registered X scaler.
+struct SampleArgmaxRun {
+    RowFeed feed; DevTmp wchunk, rec;                             // two chunks of [Xs | w] | w of the chunk, padded | records, running best, flag
+    double* bestv = nullptr; long long* bestt = nullptr; int* flag = nullptr;
+};
+static int sample_argmax_run(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const void* Wt, int nsamp, bool xraw, int minimize,
+                             SampleArgmaxRun& r) {
+    const Geom& g0 = c->g;
+    int rc;
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const int64_t nrec = sample_blocks(round_up(std::min<int64_t>(T, PRED_ROWS), 256), c->tsize()) * nsamp;      // records of a chunk
+    if ((rc = r.feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0))))) return rc;
+    if (w && (rc = dmalloc(c, &r.wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
+    if ((rc = dmalloc(c, &r.rec.p, sizeof(double) * (4 * nrec + 2 * nsamp + 1)))) return rc;
+    double* rec = r.rec;
+    r.bestv = rec + 4 * nrec;
+    r.bestt = (long long*)(r.bestv + nsamp);
+    r.flag = (int*)(r.bestv + 2 * nsamp);
+    HIPCHK(c, hipMemsetAsync(r.flag, 0, sizeof(double), c->st));
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return r.feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *wraw;
+        if ((rc = r.feed.acquire(i, &x, &wraw))) return rc;
+        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, r.wchunk.p, c->st, xraw ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = r.feed.release(i))) return rc;
+        const SampleArgmaxBufs b = {rec + (i & 1) * nrec, (long long*)(rec + (2 + (i & 1)) * nrec), r.bestv, r.bestt, r.flag};
+        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, Wt, nsamp, r.wchunk.p, minimize, i * PRED_ROWS, b))) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    return SCFGP_OK;
+}
+
+// sample_argmax_run; the running best is all that the host fetches, once, with the non-finite flag.  w is checked on the host before
+// any device work, as scfgp_select does.
 extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
                                    uint64_t seed, int mode, int minimize, int64_t* idx, double* val) {
     if (!c) return SCFGP_EARG;
@@ -1573,37 +1609,15 @@ extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, co
         if (!positive) { c->err = "sample_argmax: no row has a positive weight"; return SCFGP_EARG; }
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
     if ((rc = ensure_pred_chunk(c))) return rc;
     SampleW sw;
     if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
-    const int64_t nrec = sample_blocks(round_up(std::min<int64_t>(T, PRED_ROWS), 256), c->tsize()) * nsamp;      // records of a chunk
-    RowFeed feed; DevTmp wchunk, rec;                             // two chunks of [Xs | w] | w of the chunk, padded | records, running best, flag
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0))))) return rc;
-    if (w && (rc = dmalloc(c, &wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
-    if ((rc = dmalloc(c, &rec.p, sizeof(double) * (4 * nrec + 2 * nsamp + 1)))) return rc;
-    double* d_bestv = rec + 4 * nrec;
-    long long* d_bestt = (long long*)(d_bestv + nsamp);
-    int* d_flag = (int*)(d_bestv + 2 * nsamp);
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
-        const double *x, *wraw;
-        if ((rc = feed.acquire(i, &x, &wraw))) return rc;
-        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, wchunk.p, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
-        const SampleArgmaxBufs b = {rec + (i & 1) * nrec, (long long*)(rec + (2 + (i & 1)) * nrec), d_bestv, d_bestt, d_flag};
-        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, sw.wt.p, nsamp, wchunk.p, minimize, i * PRED_ROWS, b))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
-    }
-    if (mode == 2 && val) sample_argmax_finalize(d_bestv, nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
+    SampleArgmaxRun run;
+    if ((rc = sample_argmax_run(c, Xs, T, w, sw.wt.p, nsamp, mode >= 1, minimize, run))) return rc;
+    if (mode == 2 && val) sample_argmax_finalize(run.bestv, nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
     HIPCHK(c, hipGetLastError());
     std::vector<double> h(2 * nsamp + 1);                         // the outputs are written on success only
-    HIPCHK(c, hipMemcpyAsync(h.data(), d_bestv, sizeof(double) * (2 * nsamp + 1), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(h.data(), run.bestv, sizeof(double) * (2 * nsamp + 1), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     int flag;
@@ -2485,6 +2499,105 @@ extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const 
     if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
     if (ivar) HIPCHK(c, hipMemcpyAsync(ivar, iv.ivar, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// greedy Monte-Carlo batch expected improvement over a pool (selectqei.hip; formulas in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+// The pending rows go through sample_argmax_run (their per-sample best values are the start of m); the pool goes through scfgp_sample's
+// chunk body with each chunk's block written to its place in a T x nsamp buffer that this call owns.  Then m picks of two eager launches
+// each on the context's stream (selectqei.hip); the host waits once after the first sweep (for the non-finite flags) and once at the end.
+extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xp, int64_t np, const double* alpha,
+                                const double* Li, int nsamp, uint64_t seed, double best, double xi, int m, int mode, int minimize,
+                                int64_t* idx, double* gain, double* score0, double* mstate, double* qei) {
+    if (!c) return SCFGP_EARG;
+    auto bad = [&](const char* what) { c->err = std::string("select_qei: ") + what; return SCFGP_EARG; };
+    if (!Xc || !alpha || !Li || !idx) return bad("NULL Xc, alpha, Li or idx");
+    if (T < 1 || T > SELECT_MAX_T) return bad("T must lie in 1..1048576");
+    if (m < 1 || m > SELECT_MAX_M) return bad("m must lie in 1..4096");
+    if (nsamp < 1 || nsamp > SAMPLE_MAX) return bad("nsamp must lie in 1..1024");
+    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
+    if (np < 0) return bad("np must not be negative");
+    if (np > 0 && !Xp) return bad("np > 0 with NULL Xp");
+    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
+    if (!c->have_params) return bad("parameters not set");
+    bool nonfinite = !std::isfinite(best) || !std::isfinite(xi);
+    if (!nonfinite && xi < 0.0) return bad("xi must not be negative");
+    int64_t eligible = T;
+    if (w) {
+        eligible = 0;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "select_qei: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) ++eligible;
+        }
+    }
+    if (nonfinite) { c->err = "select_qei: non-finite best, xi or weights"; return SCFGP_ENONFINITE; }
+    if (m > eligible) {
+        c->err = "select_qei: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
+        return SCFGP_EARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    SampleW sw;
+    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
+    RowFeed feed; DevTmp Fbuf, state;                             // two chunks of Xc | F | w, score0, m, records, idx, gain, qei, flag
+    if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
+    if (hipMalloc((void**)&Fbuf.p, sizeof(double) * T * nsamp) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = "select_qei: no device memory for the pool's samples (" + std::to_string(T) + " x " + std::to_string(nsamp) + " x 8 = " +
+                 std::to_string((unsigned long long)(sizeof(double) * T * nsamp)) + " bytes)";
+        return SCFGP_EHIP;
+    }
+    const int64_t nblk = selectqei_blocks(T), mp = round_up(m, 8);
+    if ((rc = dmalloc(c, &state.p, sizeof(double) * (2 * T + nsamp + 2 * nblk + 2 * mp + 3)))) return rc;
+    SelectQeiBufs b;
+    b.F = Fbuf; b.T = T; b.nsamp = nsamp; b.sgn = minimize ? -1.0 : 1.0;
+    b.w = state; b.score0 = b.w + T; b.ms = b.score0 + T; b.pval = b.ms + nsamp; b.pidx = (long long*)(b.pval + nblk);
+    b.idx = (long long*)(b.pval + 2 * nblk); b.gain = b.pval + 2 * nblk + mp; b.qei = b.gain + mp; b.flag = (int*)(b.qei + 2);
+    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
+    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
+    else select_ones(b.w, T, c->st);
+    SampleArgmaxRun pend;                                         // the pending rows: every one of them is eligible
+    if (np > 0 && (rc = sample_argmax_run(c, Xp, np, nullptr, sw.wt.p, nsamp, mode == 1, minimize, pend))) return rc;
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xc + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double* x;
+        if ((rc = feed.acquire(i, &x))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(i))) return rc;
+        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, i * PRED_ROWS, seed, 0, -1, Fbuf + i * PRED_ROWS * nsamp))) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+    }
+    const double base = b.sgn * best + xi;
+    selectqei_state(b, np > 0 ? pend.bestv : nullptr, base, 1, c->st);
+    selectqei_sweep(b, 0, c->st);
+    HIPCHK(c, hipGetLastError());
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(&flags[0], b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    if (np > 0) HIPCHK(c, hipMemcpyAsync(&flags[1], pend.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (flags[0] || flags[1]) { c->err = "select_qei: a non-finite sampled value at an eligible or pending row"; return SCFGP_ENONFINITE; }
+    for (int j = 0; j < m; ++j) {
+        if (j) selectqei_sweep(b, j, c->st);
+        selectqei_commit(b, j, c->st);
+    }
+    selectqei_state(b, nullptr, base, 0, c->st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
+    if (gain) HIPCHK(c, hipMemcpyAsync(gain, b.gain, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
+    if (score0) HIPCHK(c, hipMemcpyAsync(score0, b.score0, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (mstate) HIPCHK(c, hipMemcpyAsync(mstate, b.ms, sizeof(double) * nsamp, hipMemcpyDeviceToHost, c->st));
+    if (qei) HIPCHK(c, hipMemcpyAsync(qei, b.qei, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SCFGP_OK;
 }

@@ -857,6 +857,59 @@ class HipEngine(object):
         self._check(rc, 'select_iv')
         return (idx, red, var, ivar, sd) if return_std else (idx, red, var, ivar)
 
+    def select_qei(self, Xc, alpha, Li, m, nsamp, best, xi=0.0, seed=0, w=None, pending=None, mode='scaled', minimize=False,
+                   return_score0=False, return_state=False):
+        """Greedy Monte-Carlo batch expected improvement over the pool Xc (include/scfgp_hip.h: scfgp_select_qei): (idx (m,) int64,
+        gain (m,), qei (2,)), then score0 (T,) with return_score0 and mstate (nsamp,) with return_state.  The nsamp sample functions
+        are `sample`'s (same seed, no noise); best and xi are in scaled y units, as in `acquire`.  Pick j is the eligible row that adds
+        most to the mean over the samples of max(best of pending rows and picks so far - (best + xi), 0); gain[j] is what it adds.
+        pending (np, D): rows chosen earlier and not yet observed, in the pool's mode; w (T,): row t is eligible iff w[t] > 0.  qei =
+        (q-EI of the pending rows alone, q-EI of pending rows plus picks); score0: the one-point Monte-Carlo EI of every row given the
+        pending rows; mstate: the per-sample running maximum after the last pick.  mode 'scaled' or 'raw'."""
+        if mode not in self.ACQUIRE_MODES:
+            raise ValueError('select_qei: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
+        md = self.ACQUIRE_MODES[mode]
+        cols = getattr(self, '_xcols', None) if md else None
+        if md and cols is None:
+            raise ValueError('select_qei: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+
+        def rows_of(X, name):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim != 2:
+                raise TypeError('%s must be a 2-d float64 array' % name)
+            if cols is not None:
+                X = X[:, cols]
+            X = np.ascontiguousarray(X)
+            if X.shape[1] != self.D:
+                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
+            return X
+        Xc = rows_of(Xc, 'Xc')
+        T = Xc.shape[0]
+        Xp = None if pending is None or len(pending) == 0 else rows_of(pending, 'pending')
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        alpha, Li = self._factors(alpha, Li)
+        m, nsamp = int(m), int(nsamp)
+        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
+        ns = nsamp if 0 < nsamp <= 1024 else 0
+        idx = np.empty(n, dtype=np.int64); gain = np.empty(n); qei = np.empty(2)
+        score0 = np.empty(T) if return_score0 else None
+        mstate = np.empty(ns) if return_state else None
+        rc = self.lib.scfgp_select_qei(self.ctx, dptr(Xc), T, dptr(w), dptr(Xp), 0 if Xp is None else Xp.shape[0], dptr(alpha), dptr(Li),
+                                       nsamp, int(seed) & (2 ** 64 - 1), float(best), float(xi), m, md, int(bool(minimize)),
+                                       idx.ctypes.data_as(_lib._c_i64_p), dptr(gain), dptr(score0), dptr(mstate), dptr(qei))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('select_qei: %s' % self.last_error())
+        self._check(rc, 'select_qei')
+        out = (idx, gain, qei)
+        if return_score0:
+            out += (score0,)
+        if return_state:
+            out += (mstate,)
+        return out
+
     def last_error(self):
         """Message of the last failure -- or refusal (a precision level whose buffers could not be had) -- on this context."""
         return self.lib.scfgp_last_error(self.ctx).decode()

@@ -375,6 +375,14 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.select_iv(X_raw, Li, m, Xr=Xr_raw, w=weights, wr=ref_weights, raw=True, return_std=return_std)
 
+    def select_qei_raw(self, X_raw, x_scaler, alpha, Li, m, nsamp, best, **kw):
+        """Greedy Monte-Carlo batch expected improvement over the raw pool rows X_raw under the posterior (alpha, Li), at the shared
+        parameter vector: engine.select_qei with mode 'raw' (best and xi in scaled y units; kw: its xi, seed, w, pending (raw rows),
+        minimize, return_score0, return_state)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.select_qei(X_raw, alpha, Li, m, nsamp, best, mode='raw', **kw)
+
     def value_and_grad(self, X, y):
         """cost, grad, alpha, Li at the current parameters without touching them."""
         return self._evaluate(X, y, True)

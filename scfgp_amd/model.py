@@ -588,6 +588,32 @@ class SCFGP(object):
         idx, red, _, ivar = owner.select_iv_raw(X_pool, self.X_scaler, self.Li, m, Xr_raw=X_ref, weights=weights, ref_weights=ref_weights)
         return idx, red, ivar
 
+    def select_qei(self, X_pool, m, nsamples=256, best=None, xi=0.0, seed=0, weights=None, pending=None, minimize=False):
+        """Which m rows of the raw pool X_pool (T,D) to try together, for improvement over the incumbent: (idx (m,) indices into the pool
+        in the order they are picked, gain (m,)).  The greedy maximiser of the Monte-Carlo batch expected improvement (q-EI) under
+        nsamples joint posterior sample functions (include/scfgp_hip.h: scfgp_select_qei): pick j is the row that adds most to the
+        expected improvement of the batch so far, and gain[j] is what it adds, in SCALED y units; the gains never increase, and a gain
+        of 0 says that no sample can still improve.  best: the incumbent in RAW y units, None: the best observed training target in
+        the direction of minimize (as acquire); xi >= 0: the improvement margin in scaled y units.  weights (T,): row t is eligible
+        iff weights[t] > 0.  pending (np,D): raw rows chosen earlier whose results are not in yet; they count through their sampled
+        values, so the new picks go elsewhere.  The same seed gives the same functions in every call.  A loop with parallel,
+        unequally long experiments:
+
+            running, best = np.empty((0, D)), float(y_train.min())       # rows under way; the incumbent in raw y units
+            while budget:
+                idx, gain = model.select_qei(pool, free_slots, best=best, pending=running, minimize=True)
+                running = np.vstack([running, pool[idx]])                # start them
+                X_done, y_done = wait_for_some(running)                  # observe
+                model.condition(X_done, y_done)                          # absorb the results (condition leaves model.y alone,
+                best = min(best, float(y_done.min()))                    #  so the caller keeps the incumbent)
+                running = remove_rows(running, X_done)                   # the unfinished ones stay pending
+
+        Nothing of the model is touched."""
+        owner = self._acquire_owner('select_qei')
+        idx, gain, _ = owner.select_qei_raw(X_pool, self.X_scaler, self.alpha, self.Li, m, int(nsamples), self._acquire_best(best, minimize),
+                                            xi=xi, seed=seed, w=weights, pending=pending, minimize=minimize)
+        return idx, gain
+
     # -- persistence -----------------------------------------------------------------------------------
     def save(self, path):
         """Portable checkpoint (arrays only; never pickles code).  The reference pickles the compiled
