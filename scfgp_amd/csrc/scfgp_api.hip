@@ -2244,7 +2244,8 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
 // ----------------------------------------------------------------------------------------------
 static constexpr int SELECT_MAX_M = 4096;
 static constexpr int64_t SELECT_MAX_T = (int64_t)1 << 20;
-static constexpr int SELECT_MAX_KP = 8192;                        // u_j lives in LDS as fp64: 64 KB
+static constexpr int SELECT_MAX_KP = 8192;                        // u_j lives in LDS as fp64: 64 KB dynamic beside the sweep's 128 B static
+                                                                  // (65 664 B: gfx950 launches it without an opt-in, tests/test_gpu_select_bounds.py)
 // The chunk pipeline (RowFeed) with the X scaler in mode 1; the chunk body is C = Phi_c Li^T, each chunk's C written to its place in a
 // T x Kp buffer that this call owns.  Then d = rowsum(C^2) and m picks, every one of them a handful of eager launches on the context's
 // stream (select.hip); the host waits once before the picks (for the non-finite flag of d) and once after them.  idx / var / gain are

@@ -7,7 +7,8 @@ numpy fp64 form of the greedy maximum-information choice (include/scfgp_hip.h: s
     d_i <- max(d_i - (c_i . u_j)^2, 0)
 
 `replay` runs the same downdates along a GIVEN pick sequence and returns d before every step, so another implementation's picks can be
-judged one by one.
+judged one by one; `replay_chol` returns the same from one Cholesky factorisation of the picked rows' Gram matrix (BLAS-3: for
+thousands of picks).  `synthetic_problem` is the input of the shapes at the documented bounds of K and m, where no fit is affordable.
 """
 import numpy as np
 
@@ -28,6 +29,43 @@ def long_weights(T=LONG[4]):
     w = np.zeros(T)
     for b in range(32768, T, 32768):
         w[b - 25:b + 25] = 1.0
+    return w
+
+
+def rows_per_group(T):
+    """select.hip's select_rows_per_group: rows per workgroup of the sweeps, 64 doubled until there are at most 4096 groups"""
+    rpw = 64
+    while (T + rpw - 1) // rpw > 4096:
+        rpw *= 2
+    return rpw
+
+
+def edge_rows(T):
+    """about 64 rows at the places where the index arithmetic of the sweeps can go wrong: row 0 and row T - 1, the first and the last
+    row of several groups of rows_per_group(T) rows (the last, possibly ragged, group among them), the rows on both sides of three
+    32768-row chunk boundaries, and rows in between"""
+    rpw = rows_per_group(T)
+    ng = (T + rpw - 1) // rpw
+    rows = {0, T - 1}
+    for g in (0, 1, 7, ng // 3, ng // 2, ng - 3, ng - 2, ng - 1):
+        rows |= {g * rpw, min((g + 1) * rpw, T) - 1}
+    rows |= {min((ng - 1) * rpw + 1, T - 1), T - 2}              # two more of the last group (or its neighbour)
+    nb = (T - 1) // 32768
+    for b in (1, nb // 2, nb):
+        rows |= {b * 32768 - 1, b * 32768}
+    rng = np.random.default_rng(T)
+    rows |= set(rng.integers(0, T, 64 - len(rows)).tolist())
+    return np.array(sorted(rows), np.int64)
+
+
+def edge_weights(T):
+    """w > 0 on edge_rows(T) only: unequal weights in [1, 2), row T - 1 the heaviest (10) and its neighbour T - 2 next (6): tuned on the
+    reference, whose picks under both criteria then take the two rows in the middle of the sequence (d varies 15-fold over the rows)"""
+    rows = edge_rows(T)
+    w = np.zeros(T)
+    w[rows] = 1.0 + np.random.default_rng(T + 1).random(len(rows))
+    w[T - 2] = 6.0
+    w[T - 1] = 10.0
     return w
 
 
@@ -88,6 +126,52 @@ def replay(C, w, idx):
         taken[p] = True
         ds.append(d.copy())
     return np.array(ds), np.array(scores)
+
+
+def replay_chol(C, w, idx):
+    """`replay` without the loop over the picks, for sequences too long for it: with C_P the picked rows in order,
+    L = chol(I + C_P C_P^T) and V = L^-1 C_P C^T (m, T), d before step j is d0 - sum_{l<j} V[l]^2 and dp_j = L_jj^2 - 1 (row j of
+    L^-1 C_P is u_j: the Cholesky factor orthogonalises the picks in order, as the recurrence does).  Returns `replay`'s two arrays
+    and dp (m,).  No clamp at 0: d is a difference of exact sums here, not a recurrence."""
+    from scipy.linalg import solve_triangular
+    C = np.asarray(C, np.float64)
+    T = C.shape[0]
+    idx = np.asarray(idx, np.int64).ravel()
+    m = len(idx)
+    w = np.ones(T) if w is None else np.asarray(w, np.float64).ravel()
+    CP = C[idx]
+    L = np.linalg.cholesky(np.eye(m) + CP @ CP.T)
+    V = solve_triangular(L, CP @ C.T, lower=True, check_finite=False)
+    ds = np.empty((m + 1, T))
+    ds[0] = np.sum(C * C, axis=1)
+    np.cumsum(V * V, axis=0, out=ds[1:])
+    ds[1:] = ds[0] - ds[1:]
+    free = np.ones((m, T), bool)
+    free[:, w <= 0] = False
+    for j in range(1, m):
+        free[j:, idx[j - 1]] = False
+    scores = np.where(free, w * ds[:m], -np.inf)
+    return ds, scores, np.diag(L) ** 2 - 1.0
+
+
+def synthetic_factor(K, seed=0):
+    """a dense, well-conditioned lower-triangular Li for shapes at which no fit is affordable (the selection entry points read only Li
+    and the parameters): diagonal 1 + U(0, 1), strict lower part N(0, (0.5 / sqrt(K))^2)"""
+    rng = np.random.default_rng(seed)
+    Li = np.tril(rng.standard_normal((K, K)), -1)
+    Li *= 0.5 / np.sqrt(K)
+    Li[np.diag_indices(K)] = 1.0 + rng.random(K)
+    return Li
+
+
+def synthetic_problem(D, S, M, T, seed=0):
+    """(params with (a, b, c) = ABC, Li = synthetic_factor(K), pool rows (T, D))"""
+    from oracle import scfgp_oracle as O
+    from scfgp_amd import synth
+    rng = np.random.default_rng(seed + 1)
+    params = O.init_params(D, S, M, rng)
+    params[:3] = ABC
+    return params, synthetic_factor(2 * (S + M), seed), synth.make_X(0x5E1EC7 + seed, T, D)
 
 
 def problem(case):

@@ -38,9 +38,10 @@ def _check_against_block(out, idx, val, w, minimize):
 
 
 # A: K = 42, the padded feature loop (48) does not end on a 128 flush, ragged rows; B: the second chunk is a ragged tail.
-# nsamp: ragged 16-column tiles and every launch width (300: tile counts 8 + 8 + 2 + 1 in fp64, 4 + 4 + 4 + 4 + 2 + 1 in fp32)
+# nsamp: ragged 16-column tiles and every launch width (300: tile counts 8 + 8 + 2 + 1 in fp64, 4 + 4 + 4 + 4 + 2 + 1 in fp32), and the
+# documented bound 1024
 @pytest.mark.parametrize('dtype', ['f64', 'f32'])
-@pytest.mark.parametrize('D,S,M,T,counts', [(3, 1, 20, 700, (1, 7, 17, 300)), (5, 4, 60, 32768 + 500, (1, 7, 17))])
+@pytest.mark.parametrize('D,S,M,T,counts', [(3, 1, 20, 700, (1, 7, 17, 300, 1024)), (5, 4, 60, 32768 + 500, (1, 7, 17))])
 def test_equals_argmax_of_sample_bit_for_bit(D, S, M, T, counts, dtype):
     eng, params, alpha, Li = _synthetic(D, S, M, dtype)
     Xs = synth.make_X(101, T, D)

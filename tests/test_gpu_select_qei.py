@@ -57,10 +57,10 @@ def _call(eng, Xs, alpha, Li, m, ns, best, **kw):
 
 
 # A: K = 42, ragged rows, every launch width of the product; B: the second chunk is a ragged tail.  nsamp covers both lane-group widths
-# (16 lanes up to 64 samples, a wave above), odd row pitches and a single sample.  best = the median of the block's column maxima
+# (16 lanes up to 64 samples, a wave above), odd row pitches, a single sample and the documented bound 1024.  best = the median of the block's column maxima
 # (minima when minimising): some samples can still improve and some cannot.
 @pytest.mark.parametrize('dtype', ['f64', 'f32'])
-@pytest.mark.parametrize('D,S,M,T,counts', [(3, 1, 20, 700, (1, 7, 17, 100, 300)), (5, 4, 60, 32768 + 500, (7, 65))])
+@pytest.mark.parametrize('D,S,M,T,counts', [(3, 1, 20, 700, (1, 7, 17, 100, 300, 1024)), (5, 4, 60, 32768 + 500, (7, 65))])
 def test_parity_with_the_restatement_on_the_device_block(D, S, M, T, counts, dtype):
     eng, params, alpha, Li = _synthetic(D, S, M, dtype)
     Xs = synth.make_X(101, T, D)

@@ -83,6 +83,67 @@ def test_prefix_property_and_replay(case):
     assert ref['gap'].min() > 1e-8
 
 
+def _agree(ds, scores, ds0, scores0):
+    """replay_chol's arrays against replay's: d to 1e-12 of the row's start value (the two sum in different orders), the same rows
+    eligible at every step"""
+    if ds.shape != ds0.shape or scores.shape != scores0.shape or not np.array_equal(np.isfinite(scores), np.isfinite(scores0)):
+        return False
+    live = np.isfinite(scores0)
+    tol = 1e-12 * np.broadcast_to(ds0[0], scores0.shape)
+    return bool(np.all(np.abs(ds - ds0) <= 1e-12 * ds0[0])) and bool(np.all(np.abs(scores[live] - scores0[live]) <= tol[live]))
+
+
+@pytest.mark.parametrize('case', R.CASES)
+def test_cholesky_replay_equals_the_recurrence(case):
+    D, S, M, N0, T, m = case
+    if case in CASES:
+        params, X0, y0, Xp, alpha, Li, C, ref = _setup(case)
+        idx = ref['idx']
+    else:                                                       # the headline K: no fit (it takes seconds), a synthetic factor
+        params, Li, Xp = R.synthetic_problem(D, S, M, T)
+        C = pred_cov_ref.factor(Xp, Li, params, S, M)
+        idx = R.select(C, m)['idx']
+    ds0, scores0 = R.replay(C, None, idx)
+    ds, scores, dp = R.replay_chol(C, None, idx)
+    worst = float((np.abs(ds - ds0) / ds0[0]).max())
+    print('select ref %s: Cholesky replay against the recurrence, worst |d - d_rec| / d0 %.3g' % (case, worst))
+    assert _agree(ds, scores, ds0, scores0)
+    assert np.allclose(dp, ds0[np.arange(m), idx], rtol=1e-9, atol=0)
+    # weights, a row of weight 0 among them
+    w = 0.5 + np.random.default_rng(4).random(T); w[idx[1]] = 0.0
+    idw = R.select(C, min(m, 10), w=w)['idx']
+    assert _agree(*R.replay_chol(C, w, idw)[:2], *R.replay(C, w, idw))
+    # the mutation: one pick swapped for its runner-up among the rows outside the sequence (every row is picked: for its successor)
+    # must not pass as the same sequence
+    j = m // 2
+    swapped = idx.copy()
+    if m < T:
+        s = scores0[j].copy(); s[idx] = -np.inf
+        swapped[j] = int(np.argmax(s))
+    else:
+        swapped[[j, j + 1]] = idx[[j + 1, j]]
+    assert not _agree(*R.replay_chol(C, None, swapped)[:2], ds0, scores0)
+
+
+@pytest.mark.parametrize('T,rpw', [(262144, 64), (262145, 128), (262144 + 69, 128), (524288, 128), (524289, 256), (1 << 20, 256)])
+def test_edge_rows_sit_where_the_sweeps_index(T, rpw):
+    """the inputs of tests/test_gpu_select_bounds.py: select.hip's rows per workgroup, and weighted rows at every edge of that tiling"""
+    assert R.rows_per_group(T) == rpw and (T + rpw - 1) // rpw <= 4096
+    rows = R.edge_rows(T); w = R.edge_weights(T)
+    last = (T - 1) // rpw * rpw
+    assert len(rows) <= 64 and len(set(rows.tolist())) == len(rows) and rows.min() == 0 and rows.max() == T - 1
+    assert {last - 1, last, min(last + 1, T - 1), T - 2, rpw - 1, rpw, 32767, 32768} <= set(rows.tolist())
+    assert np.array_equal(np.flatnonzero(w), rows) and len(set(w[rows].tolist())) == len(rows) and np.argmax(w) == T - 1
+
+
+def test_synthetic_factor_is_dense_lower_triangular_and_well_conditioned():
+    Li = R.synthetic_factor(300)
+    assert np.array_equal(Li, np.tril(Li)) and np.count_nonzero(Li) == 300 * 301 // 2
+    assert np.linalg.cond(Li) < 10.0
+    params, L2, Xp = R.synthetic_problem(4, 2, 10, 50)
+    assert L2.shape == (24, 24) and Xp.shape == (50, 4) and tuple(params[:3]) == R.ABC
+
+
 def test_weights():
     case = CASES[0]
     D, S, M, N0, T, m = case
