@@ -475,7 +475,8 @@ def test_one_context_through_a_random_sequence_of_calls(D, S, M, dtype, ctol, gt
     predictions (1 .. 5000 rows), two device training iterations, and option changes between them (precision level, factor
     form, rank-S backward projection, LDS-DMA tiles, row splits) -- and every result is compared with the oracle on the
     inputs of that call.  Buffers that outlive a call (row buffers sized for an earlier, larger N; the factor-form and fp64
-    feature buffers; slabs; the captured training graph) must never leak into a later one."""
+    feature buffers; slabs; the captured training graph) must never leak into a later one.  The posterior entry points added since
+    (predict_grad .. select_qei) go through the same kind of sequence in tests/test_gpu_posterior_sequence.py."""
     from scfgp_amd.engine import HipEngine
     rng = np.random.default_rng(D * 1000 + S * 10 + M + (0 if dtype == 'f64' else 7))
     eng = HipEngine(D, S, M, dtype)
