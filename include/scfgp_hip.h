@@ -265,11 +265,62 @@ int scfgp_sample_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double*
  * SCFGP_ENONFINITE for a non-finite par, fstar or w (on the host, before any device work) and for an eligible row whose mu, sigma or value
  * is non-finite or whose sigma is 0 (found on the device); a non-finite row with w = 0 is not an error and its acq is whatever comes out.
  * The outputs are untouched in every error case.  Row-sharded use: each rank calls it on its rows and the caller merges (val, idx + offset)
- * by the merge rule.  Batch (q-) expected improvement: scfgp_select_qei.  Out of scope: top-k, raw-y acquisitions, knowledge gradient,
- * factors or f* kept on the device between calls. */
+ * by the merge rule.  Batch (q-) expected improvement: scfgp_select_qei.  Knowledge gradient: scfgp_acquire_kg.  Out of scope: top-k,
+ * raw-y acquisitions, factors or f* kept on the device between calls. */
 int scfgp_acquire(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
                   int kind, const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize,
                   double* acq, int64_t* idx, double* val, double* mu, double* sd, double* grad);
+
+/* ---- knowledge gradient over a pool (no reference counterpart) ---------------------------------------------------------------------------
+ * scfgp_acquire_kg: the acquisition for the case where the answer reported at the end is the best posterior MEAN over a reference set (the
+ * pool, a grid, the region of interest), not the best observed value -- the normal case with noisy observations.  Candidates Xc (T rows),
+ * reference rows Xr (R rows); sgn = +1, or -1 with `minimize`; u_r = sgn mu*(x_r) with scfgp_predict's bits, d_r = u_r - max_r u_r <= 0.
+ * Observing candidate i moves every u_r to u_r + b_ir Z, Z ~ N(0, 1), with
+ *     b_ir = kappa <Li phi(x_i), Li phi(x_r)> / sigma_i
+ * whose numerator is scfgp_predict_cov's element bit for bit and whose sigma_i is scfgp_acquire's with the same `noise` (sigma* =
+ * sqrt(kappa (1 + v_i)) for noise != 0, a noisy observation; sigma_f = sqrt(kappa v_i) for noise == 0).  The knowledge gradient is
+ *     KG_i = E[ max_r (d_r + b_ir Z) ] >= 0,
+ * the expectation of the upper envelope of R lines.  The T x R matrix b is never formed: the caller passes J nodes z_1 < ... < z_J (finite,
+ * exactly one of them 0.0) and the product's epilogue reduces every element into
+ *     m_ij = max_r (d_r + b_ir z_j)          the envelope's value at z_j; formed as t = b z, then d + t: two roundings, no fma
+ *     s_ij = b_ir at the maximiser           its slope there; ties go to the lowest r
+ *     bmin_i, bmax_i = min_r, max_r b_ir     its slopes at -inf, +inf
+ * With h(x) = x Phi(x) + phi(x) (scfgp_acquire's, with its tail forms), two closed-form numbers per candidate bracket KG_i:
+ *     kg (T)      the expected maximum of the J tangents (m_ij, s_ij): slopes that do not exceed the last kept one merge with it; the
+ *                 tangents kept at nodes j' < j meet at c = (icpt' - icpt_j) / (s_j - s'), icpt = m - s z, clamped into [z_{j-1}, z_j]
+ *                 (where it lies in exact arithmetic); kg_i = sum (s_j - s') h(-|c|).  This is the exact knowledge gradient over the
+ *                 reference rows that win at some node: never above KG_i.  The node 0.0 makes the tangent envelope 0 at 0 (max d = 0).
+ *     kg_hi (T)   the expectation of the chord interpolant through (z_j, m_ij), continued with the slopes bmin_i, bmax_i outside the nodes:
+ *                 kg_hi_i = sum_j max(q_j - q_{j-1}, 0) h(-|z_j|), q_j = (m_{i,j+1} - m_ij) / (z_{j+1} - z_j) clamped into [s_ij, s_{i,j+1}]
+ *                 (a convex function's chord lies between its end slopes; exact arithmetic needs no clamp), q_0 = bmin_i, q_J = bmax_i:
+ *                 never below KG_i.  The gap kg_hi - kg is the caller's certificate that the nodes were enough.
+ * Every term of both sums is >= 0.  With R = 1 both are 0 exactly.  All node arithmetic is fp64 in every compute mode (SCFGP_F16X3
+ * contexts run fp32 mode's kernels and agree with it bit for bit).
+ * Xr == NULL: the reference set is the candidates (R is ignored, T <= 32768); the result is bit-equal to the call with Xr = Xc.
+ * Outputs, each may be NULL, but not all of kg, kg_hi, idx, m and s together:
+ *     kg, kg_hi (T)       as above
+ *     idx, val (1)        row t is eligible iff w == NULL or w[t] > 0 (scfgp_acquire's meaning and host-side checks); idx[0] = the lowest
+ *                         eligible t at which kg is largest, val[0] = kg[idx[0]] bit for bit, by scfgp_acquire's merge rule; val needs idx
+ *     m, s (T x J each)   the node table, row-major
+ * mode 0: scaled rows; 1: column-selected raw rows through the registered X scaler (Xc and Xr alike).  There is no raw-y mode (as
+ * scfgp_acquire and scfgp_predict_cov).
+ * Bounds: 1 <= R <= 32768 (scfgp_predict_cov's Tb bound: the reference rows' factor stays resident for the call); T >= 1 without limit, in
+ * chunks; 3 <= J <= 32 (the node state of a 128-row strip shares the CU's LDS with the product's operand images).  Device memory beside
+ * the chunk buffers: 2 T doubles, 2 T J more with m or s, and a fixed 64 K x (2 J + 2) doubles of node state: nothing grows with T x R.
+ * Guarantees: a candidate's kg, kg_hi, m and s depend on its own row, the SET of reference rows, the factors, the parameters and z -- not
+ * on T, the row's position, the chunk, w or the column split of the launch.  Permuting the reference rows, or appending the reference set
+ * to itself, leaves every output bit-identical unless two reference rows with different b tie exactly at a node (max is exact and
+ * order-free).  idx and val do not change when the pool is appended to itself.  The training state of the context survives.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xc, alpha, Li or z, T < 1, R outside [1, 32768], T > 32768 in
+ * the symmetric form, J outside [3, 32], nodes that are not strictly increasing or do not hold exactly one 0.0, a bad mode, a missing X
+ * scaler in mode 1, parameters not set, a negative w, no positive w, no output requested, val without idx.  SCFGP_ENONFINITE for a
+ * non-finite z or w (on the host, before any device work), a non-finite u_r, and an eligible candidate whose sigma is 0 or whose sigma, kg
+ * or kg_hi is non-finite (found on the device); a non-finite candidate with w = 0 is not an error and its outputs are whatever comes out.
+ * The outputs are untouched in every error case.  Out of scope: the exact envelope on the device, the input gradient of KG, batch or
+ * pending-row KG, reference-row weights, more than 32 nodes, a raw-y form, factors kept on the device between calls. */
+int scfgp_acquire_kg(scfgp_ctx* ctx, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R,
+                     const double* alpha, const double* Li, const double* z, int J, int mode, int noise, int minimize,
+                     double* kg, double* kg_hi, int64_t* idx, double* val, double* m, double* s);
 
 /* ---- joint posterior covariance between test points (no reference counterpart: the reference reports the marginals only) -------
  * Under the weight posterior w ~ N(alpha, kappa A^-1) above, two function values have covariance kappa phi(x)^T A^-1 phi(x'); with

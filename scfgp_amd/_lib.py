@@ -48,6 +48,8 @@ SIGNATURES = {
     'scfgp_acquire': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.c_int, _c_double_p, C.c_int,
                                 _c_double_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_double_p, _c_i64_p, _c_double_p, _c_double_p, _c_double_p,
                                 _c_double_p]),
+    'scfgp_acquire_kg': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p, _c_i64_p, _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_forget': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p,

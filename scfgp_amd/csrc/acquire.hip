@@ -17,29 +17,9 @@
 // two g^2 / 2 of a MES term at very negative g (absolute eps g^2 on a value of order log |g|).
 #include "kernels.h"
 #include "argmax.h"
-
-// the value of a row must not depend on what the compiler chose to fuse: no contraction in this file
-#pragma clang fp contract(off)
+#include "acquire_math.h"                                         // phi, Phi, tail_r (shared with kg.hip); contraction off from here on
 
 namespace {
-
-constexpr double INV_SQRT2 = 0.70710678118654752440;
-constexpr double INV_SQRT_2PI = 0.39894228040143267794;
-constexpr double SQRT_2_OVER_PI = 0.79788456080286535588;
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-constexpr double SQRT_PI = 1.77245385090551602730;
-constexpr double SQRT_PI_OVER_2 = 1.25331413731550025121;
-
-__device__ __forceinline__ double norm_pdf(double g) { return INV_SQRT_2PI * exp(-0.5 * g * g); }
-__device__ __forceinline__ double norm_cdf(double g) { return 0.5 * erfc(-g * INV_SQRT2); }
-// r = h / phi for g <= -1; e = erfcx(-g / sqrt 2)
-__device__ __forceinline__ double tail_r(double g, double e) {
-    if (g < -50.0) {
-        const double w = 1.0 / g, w2 = w * w;
-        return w2 * (1.0 + w2 * (-3.0 + w2 * (15.0 + w2 * (-105.0 + w2 * 945.0))));
-    }
-    return 1.0 - SQRT_PI * (-g * INV_SQRT2) * e;
-}
 
 // the acquisition value of kinds 0 - 3 and its partials in u and sigma
 template <int KIND>

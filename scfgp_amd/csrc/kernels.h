@@ -290,6 +290,22 @@ void acquire_argmax(const Geom& g, const double* w, int64_t t0, int first, const
 // grad (N x D, holding d mu / d x) <- sgn au grad + as dsd
 void acquire_grad(const Geom& g, const AcquireBufs& b, int minimize, const double* dsd, double* grad, hipStream_t st);
 
+// ---- kg.hip, knowledge gradient over a pool (scfgp_acquire_kg) ------------------------------------------------------------------------------
+// d (round_up(R, 128)): d_r = u_r - max u of the reference rows; zf (64): the nodes and h(-|z_j|); sd (Np): sigma of the chunk's candidates;
+// st_m, st_s (kg_state_rows() x J), st_b (kg_state_rows() x 2): the node states per row and column split; kg, kg_hi: the chunk's rows of
+// the call's T-sized arrays; m, s: its rows of the T x J node tables, or NULL
+struct KgBufs { double *d, *zf, *sd, *st_m, *st_s, *st_b, *kg, *kg_hi, *m, *s; };
+int64_t kg_state_rows();
+// after apply_predict on the R reference rows (njt partials per row, leading dimension Np): d, zf; flag[1] = 1 where a u_r is not finite
+void kg_reference(int njt, const double* mupart, int64_t Np, int64_t R, int minimize, const double* z, int J, double* d, double* zf, int* flag,
+                  hipStream_t st);
+// sd[n < Np] = sqrt(kappa v) or (noise) sqrt(kappa (1 + v)) from the chunk's partials, by acquire_rows' arithmetic
+void kg_sigma(const Geom& g, int njt, const double* vpart, const Scal* sc, int noise, double* sd, hipStream_t st);
+// Ca (the chunk's g.N candidates), Cb (R reference rows): C = Phi Li^T as apply_c leaves it, as predcov takes them.  The node table of
+// every candidate without the g.N x R matrix, then kg, kg_hi (and m, s) of the chunk's rows
+template <typename T>
+void kg_nodes(const Geom& g, const T* Ca, const T* Cb, int64_t R, int J, const KgBufs& b, const Scal* sc, hipStream_t st);
+
 // ---- samplegrad.hip, values and input gradients of sample functions, one sample per row (scfgp_sample_grad) ----------------------------
 // leading dimension of WT: a weight row is contiguous, 16-byte aligned and zero past K
 int samplegrad_w_ld(int K);

@@ -833,6 +833,27 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_acquire_kg, the reference job: predict_chunk's product on the R reference rows, whose partials give u_r with scfgp_predict's
+    // bits (kg.hip: d_r and the per-call constants of the nodes), then Cb = Phi Li^T into p_V, where it stays for the call
+    static int kg_ref_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int minimize, const double* z, int J, const KgBufs& b, int* flag) {
+        features(c, g);
+        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
+        kg_reference(ApplyKernels<T>::partials(g), c->p_mupart, g.Np, g.N, minimize, z, J, b.d, b.zf, flag, c->st);
+        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_V);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // a chunk of candidates: sigma from predict_chunk's product (scfgp_acquire's bits), Ca = Phi Li^T into p_C, then the fused product
+    // with the node reduction and the two sums (kg.hip)
+    static int kg_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int64_t R, int J, int noise, const KgBufs& b) {
+        features(c, g);
+        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
+        kg_sigma(g, ApplyKernels<T>::partials(g), c->p_vpart, c->d_sc, noise, b.sd, c->st);
+        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
+        kg_nodes<T>(g, (const T*)c->p_C, (const T*)c->p_V, R, J, b, c->d_sc, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
     // scfgp_sample_grad: f and d f / d x~ of the chunk's rows, each under its own sample's weights (samplegrad.hip; FT: grad_operand)
     static int sample_grad_chunk(scfgp_ctx* c, const Geom& g, const double* WT, const double* sidx, int64_t t0, int nsamp, double* val,
                                  double* grad) {
@@ -1228,7 +1249,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_select and scfgp_select_qei
+// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -1734,6 +1755,121 @@ extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const do
     if (mu) HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (sd) HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (grad) HIPCHK(c, hipMemcpyAsync(grad, d_grad, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (idx) memcpy(idx, &h[1], sizeof(int64_t));
+    if (val) val[0] = h[0];
+    return SCFGP_OK;
+}
+
+// scfgp_acquire's pipeline with scfgp_predict_cov's first job: job 0 of the feed is the reference rows (Cb stays in p_V, d_r on the
+// device), the chunks of [Xc | w] follow; each chunk's kg / kg_hi (and node table) join the call's T-sized arrays, its best eligible row
+// the running best, through acquire.hip's argmax kernels (kg_hi in mu's place: an eligible row's kg, kg_hi and sigma must be finite,
+// sigma not 0).  The symmetric form is the call with Xr = Xc.  z and w are checked on the host before any device work; the outputs are
+// written on success only.
+static constexpr int KG_MAX_NODES = 32;
+extern "C" int scfgp_acquire_kg(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* alpha,
+                                const double* Li, const double* z, int J, int mode, int noise, int minimize, double* kg, double* kg_hi,
+                                int64_t* idx, double* val, double* m, double* s) {
+    if (!c) return SCFGP_EARG;
+    auto bad = [&](const char* what) { c->err = std::string("acquire_kg: ") + what; return SCFGP_EARG; };
+    if (!Xc || !alpha || !Li || !z) return bad("NULL Xc, alpha, Li or z");
+    if (T < 1) return bad("T must be at least 1");
+    if (!Xr) {
+        if (T > PRED_ROWS) return bad("the symmetric form (Xr == NULL) takes 1..32768 rows");
+        Xr = Xc; R = T;
+    } else if (R < 1 || R > PRED_ROWS) return bad("R must lie in 1..32768");
+    if (J < 3 || J > KG_MAX_NODES) return bad("J must lie in 3..32");
+    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
+    if (!kg && !kg_hi && !idx && !m && !s) return bad("no output requested (kg, kg_hi, idx, m and s are all NULL)");
+    if (val && !idx) return bad("val without idx");
+    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
+    if (!c->have_params) return bad("parameters not set");
+    bool nonfinite = false;
+    for (int j = 0; j < J; ++j) if (!std::isfinite(z[j])) nonfinite = true;
+    if (!nonfinite) {
+        int zeros = z[0] == 0.0 ? 1 : 0;
+        for (int j = 1; j < J; ++j) {
+            if (!(z[j] > z[j - 1])) return bad("the nodes must be strictly increasing");
+            if (z[j] == 0.0) ++zeros;
+        }
+        if (zeros != 1) return bad("exactly one node must be 0.0");
+    }
+    if (w) {
+        bool positive = false;
+        for (int64_t i = 0; i < T; ++i) {
+            if (w[i] < 0.0) { c->err = "acquire_kg: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
+            if (!std::isfinite(w[i])) nonfinite = true;
+            else if (w[i] > 0.0) positive = true;
+        }
+        if (!nonfinite && !positive) return bad("no row has a positive weight");
+    }
+    if (nonfinite) { c->err = "acquire_kg: non-finite nodes or weights"; return SCFGP_ENONFINITE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const Geom& g0 = c->g;
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, njobs = nchunks + 1;
+    const int64_t nrec = acquire_blocks(PRED_ROWS), SR = kg_state_rows();
+    const bool table = m || s;
+    RowFeed feed; DevTmp d_out, work;             // Li / two jobs of [X | w] | kg, kg_hi (and m, s) of all T rows | chunk scratch
+    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0)), (int64_t)g0.K * g0.K))) return rc;
+    if ((rc = dmalloc(c, &d_out.p, sizeof(double) * T * (2 + (table ? 2 * J : 0))))) return rc;
+    // work: w of the chunk, padded | sigma of the chunk | d_r | z as given | nodes and h(-|z|) | records of two chunks | running best, flags |
+    // bmin, bmax and the (m, s) states per row and column split
+    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + 96 + 4 * nrec + 3 + SR * (2 + 2 * J))))) return rc;
+    double* d_kg = d_out; double* d_hi = d_out + T; double* d_m = table ? d_out + 2 * T : nullptr; double* d_s = table ? d_m + T * J : nullptr;
+    double* d_w = work; double* d_sd = work + PRED_ROWS; double* d_d = work + 2 * PRED_ROWS; double* d_z = work + 3 * PRED_ROWS;
+    double* d_zf = d_z + 32;
+    double* d_rec = d_zf + 64;
+    double* d_bestv = d_rec + 4 * nrec;
+    long long* d_bestt = (long long*)(d_bestv + 1);
+    int* d_flag = (int*)(d_bestv + 2);                            // [0]: a candidate (acquire_argmax); [1]: a reference row
+    double* d_stb = d_bestv + 3; double* d_stm = d_stb + 2 * SR; double* d_sts = d_stm + SR * J;
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
+    HIPCHK(c, hipMemcpyAsync(d_z, z, sizeof(double) * J, hipMemcpyHostToDevice, c->st));
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    auto job_rows = [&](int64_t job) { return job == 0 ? R : std::min<int64_t>(PRED_ROWS, T - (job - 1) * PRED_ROWS); };
+    auto upload = [&](int64_t job) {
+        if (job == 0) return feed.upload(0, Xr, nullptr, R);
+        return feed.upload(job, Xc + (job - 1) * PRED_ROWS * g0.D, w ? w + (job - 1) * PRED_ROWS : nullptr, job_rows(job));
+    };
+    if ((rc = upload(0))) return rc;
+    for (int64_t job = 0; job < njobs; ++job) {
+        const Geom g = chunk_geom(g0, job_rows(job));
+        const double *x, *wraw;
+        if ((rc = feed.acquire(job, &x, &wraw))) return rc;
+        const bool cand = job > 0;
+        pack_data(g, x, cand && w ? wraw : nullptr, nullptr, c->p_Xt, cand && w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        if ((rc = feed.release(job))) return rc;
+        const int64_t i = job - 1, t0 = i * PRED_ROWS;
+        const KgBufs b = {d_d, d_zf, d_sd, d_stm, d_sts, d_stb, cand ? d_kg + t0 : nullptr, cand ? d_hi + t0 : nullptr,
+                          cand && table ? d_m + t0 * J : nullptr, cand && table ? d_s + t0 * J : nullptr};
+        if (!cand) {
+            if ((rc = DISPATCH(c, kg_ref_chunk, c, g, LiT, minimize ? 1 : 0, d_z, J, b, d_flag))) return rc;
+        } else {
+            if ((rc = DISPATCH(c, kg_chunk, c, g, LiT, R, J, noise ? 1 : 0, b))) return rc;
+            const AcquireBufs ab = {b.kg_hi, d_sd, b.kg, nullptr, nullptr, d_rec + (i & 1) * nrec, (long long*)(d_rec + (2 + (i & 1)) * nrec),
+                                    d_bestv, d_bestt, d_flag};
+            acquire_argmax(g, w ? d_w : nullptr, t0, i == 0, ab, c->st);
+        }
+        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
+    }
+    HIPCHK(c, hipGetLastError());
+    double h[3];                                                  // the running best and the flags first: the outputs are written on success only
+    HIPCHK(c, hipMemcpyAsync(h, d_bestv, sizeof(h), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    int flag[2];
+    memcpy(flag, &h[2], sizeof(flag));
+    if (flag[1]) { c->err = "acquire_kg: a reference row has a non-finite mean"; return SCFGP_ENONFINITE; }
+    if (flag[0]) { c->err = "acquire_kg: an eligible candidate has a non-finite value or sigma, or sigma = 0"; return SCFGP_ENONFINITE; }
+    if (kg) HIPCHK(c, hipMemcpyAsync(kg, d_kg, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (kg_hi) HIPCHK(c, hipMemcpyAsync(kg_hi, d_hi, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
+    if (m) HIPCHK(c, hipMemcpyAsync(m, d_m, sizeof(double) * T * J, hipMemcpyDeviceToHost, c->st));
+    if (s) HIPCHK(c, hipMemcpyAsync(s, d_s, sizeof(double) * T * J, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (idx) memcpy(idx, &h[1], sizeof(int64_t));
     if (val) val[0] = h[0];

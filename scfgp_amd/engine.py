@@ -429,6 +429,73 @@ class HipEngine(object):
             out['grad'] = _scatter(grad, cols, D_in) if cols is not None else grad
         return out
 
+    KG_WANT = ('kg', 'kg_hi', 'idx', 'val', 'm', 's')
+    KG_DEFAULT_NODES = np.linspace(-5.0, 5.0, 31)
+
+    def _kg_rows(self, X, cols, name):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise TypeError('%s must be a 2-d float64 array' % name)
+        if cols is not None:
+            X = X[:, cols]
+        X = np.ascontiguousarray(X)
+        if X.shape[1] != self.D:
+            raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
+        return X
+
+    def acquire_kg(self, Xc, alpha, Li, Xr=None, z=None, w=None, mode='scaled', noise=True, minimize=False, want=('kg', 'idx', 'val')):
+        """Knowledge gradient of the candidates Xc (T, D) over the reference rows Xr (R <= 32768 rows; None: the candidates themselves,
+        T <= 32768), in scaled y units (include/scfgp_hip.h: scfgp_acquire_kg).  z: the nodes, strictly increasing and holding exactly one
+        0.0, 3..32 of them (None: linspace(-5, 5, 31)).  noise: the candidate is observed with noise (sigma*), the normal case.  w (T,):
+        row t is eligible iff w[t] > 0.  mode 'scaled' or 'raw' (Xc and Xr through the registered X scaler).  want: any of 'kg' (T,: the
+        lower bound), 'kg_hi' (T,: the upper bound), 'idx' (the lowest eligible row with the largest kg), 'val' (its kg; needs 'idx'),
+        'm', 's' ((T, J) each: the node table).  Returns a dict with the keys asked for."""
+        if mode not in self.ACQUIRE_MODES:
+            raise ValueError('acquire_kg: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        for k in want:
+            if k not in self.KG_WANT:
+                raise ValueError('acquire_kg: want holds %r; allowed: %s' % (k, self.KG_WANT))
+        md = self.ACQUIRE_MODES[mode]
+        cols = getattr(self, '_xcols', None) if md else None
+        if md and cols is None:
+            raise ValueError('acquire_kg: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        Xc = self._kg_rows(Xc, cols, 'Xc')
+        T = Xc.shape[0]
+        R = 0
+        if Xr is not None:
+            Xr = self._kg_rows(Xr, cols, 'Xr')
+            R = Xr.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        z = np.ascontiguousarray(self.KG_DEFAULT_NODES if z is None else z, dtype=np.float64).reshape(-1)
+        J = z.size
+        alpha, Li = self._factors(alpha, Li)
+        nj = J if 3 <= J <= 32 else 0                           # out of range: the library refuses before it writes
+        kg = np.empty(T) if 'kg' in want else None
+        hi = np.empty(T) if 'kg_hi' in want else None
+        idx = np.empty(1, dtype=np.int64) if 'idx' in want else None
+        val = np.empty(1) if 'val' in want else None
+        m = np.empty((T, nj)) if 'm' in want else None
+        s = np.empty((T, nj)) if 's' in want else None
+        rc = self.lib.scfgp_acquire_kg(self.ctx, dptr(Xc), T, dptr(w), dptr(Xr), R, dptr(alpha), dptr(Li), dptr(z), J, md, int(bool(noise)),
+                                       int(bool(minimize)), dptr(kg), dptr(hi), None if idx is None else idx.ctypes.data_as(_lib._c_i64_p),
+                                       dptr(val), dptr(m), dptr(s))
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('acquire_kg: %s' % self.last_error())
+        self._check(rc, 'acquire_kg')
+        out = {}
+        for k, a in (('kg', kg), ('kg_hi', hi), ('m', m), ('s', s)):
+            if a is not None:
+                out[k] = a
+        if idx is not None:
+            out['idx'] = int(idx[0])
+        if val is not None:
+            out['val'] = float(val[0])
+        return out
+
     def sample_grad(self, Xs, W, sidx=None, mode='scaled', want_val=True):
         """Values and input gradients of sample functions, one sample per row (include/scfgp_hip.h: scfgp_sample_grad): (val (T,),
         grad (T, D)) with val[t] = phi(x_t)^T W[:, sidx[t]] and grad[t] its gradient in x_t.  W (K, nsamp) as sample_weights returns

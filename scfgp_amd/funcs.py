@@ -303,6 +303,13 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.acquire(Xs_raw, alpha, Li, kind, mode='raw', **kw)
 
+    def acquire_kg_raw(self, Xc_raw, x_scaler, alpha, Li, Xr_raw=None, **kw):
+        """Knowledge gradient of the raw candidate rows Xc_raw over the raw reference rows Xr_raw, in scaled y units (engine.acquire_kg
+        with mode 'raw'; kw: its z, w, noise, minimize, want)."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.acquire_kg(Xc_raw, alpha, Li, Xr=Xr_raw, mode='raw', **kw)
+
     def sample_argmax_raw(self, Xs_raw, x_scaler, alpha, Li, nsamp, seed=0, weights=None, minimize=False):
         """Per-sample maximisers (idx, val) over the raw pool rows Xs_raw with val in SCALED y units: the f* of acquire_raw's 'mes'."""
         self._sync_params()

@@ -390,6 +390,17 @@ class SCFGP(object):
             kw['best'] = self._acquire_best(best, minimize); kw['xi'] = xi
         return owner.acquire_raw(X_pool, self.X_scaler, self.alpha, self.Li, kind, **kw)
 
+    def kg(self, X_pool, X_ref=None, nodes=None, weights=None, noise=True, minimize=False):
+        """Knowledge gradient of every row of the raw pool X_pool (T,D) over the raw reference rows X_ref (R <= 32768; None: the pool
+        itself, T <= 32768): the expected gain in the best posterior MEAN over the reference rows from observing the candidate
+        (include/scfgp_hip.h: scfgp_acquire_kg), in SCALED y units.  nodes: 3..32 strictly increasing values with exactly one 0.0
+        (None: linspace(-5, 5, 31)).  noise: the observation is noisy (the normal case).  minimize: small targets are good.  Returns a
+        dict: 'kg' (T,) a lower and 'kg_hi' (T,) an upper bound of the exact value -- their gap certifies the nodes -- and 'idx',
+        'val': the lowest eligible row (weights > 0) with the largest kg, and that kg."""
+        owner = self._acquire_owner('kg')
+        return owner.acquire_kg_raw(X_pool, self.X_scaler, self.alpha, self.Li, Xr_raw=X_ref, z=nodes, w=weights, noise=noise,
+                                    minimize=minimize, want=('kg', 'kg_hi', 'idx', 'val'))
+
     def mes(self, X_pool, nsamples, seed=0, weights=None, minimize=False):
         """Max-value entropy search over the raw pool: one sample_argmax call for nsamples draws of the maximum f* in scaled y units,
         then acquire('mes') on the same pool.  Returns acquire's dict with 'fstar' added."""

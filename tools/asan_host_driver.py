@@ -50,5 +50,28 @@ if ctx:
                  (xp, 1, None, xp, xp, 2, xp, 2, None, 0, 0, 0, 0, xp, ip, xp, None, None, None)]:       # parameters not set
         assert lib.scfgp_acquire(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'acquire')
         n += 1
+# scfgp_acquire_kg: the same
+z3 = C.cast((C.c_double * 5)(-1.0, 0.0, 1.0, 2.0, 3.0), C.POINTER(C.c_double))
+assert lib.scfgp_acquire_kg(None, xp, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None) == -1
+n += 1
+if ctx:
+    for args in [(None, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None),           # NULL Xc
+                 (xp, 1, None, None, 0, xp, xp, None, 3, 0, 1, 0, xp, xp, ip, xp, None, None),           # NULL z
+                 (xp, 0, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None),             # T < 1
+                 (xp, 32769, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None),         # the symmetric form's bound
+                 (xp, 1, None, xp, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None),               # R < 1
+                 (xp, 1, None, xp, 32769, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None),           # R
+                 (xp, 1, None, None, 0, xp, xp, z3, 2, 0, 1, 0, xp, xp, ip, xp, None, None),             # J
+                 (xp, 1, None, None, 0, xp, xp, z3, 33, 0, 1, 0, xp, xp, ip, xp, None, None),            # J
+                 (xp, 1, None, None, 0, xp, xp, xp, 3, 0, 1, 0, xp, xp, ip, xp, None, None),             # nodes not increasing
+                 (xp, 1, None, None, 0, xp, xp, C.cast(C.byref(z3.contents, 16), C.POINTER(C.c_double)), 3, 0, 1, 0, xp, xp, ip, xp, None,
+                  None),                                                                                 # no 0.0 among the nodes (1, 2, 3)
+                 (xp, 1, None, None, 0, xp, xp, z3, 4, 2, 1, 0, xp, xp, ip, xp, None, None),             # mode
+                 (xp, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, None, None, None, None, None, None),     # no output
+                 (xp, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, None, xp, None, None),           # val without idx
+                 (xp, 1, None, None, 0, xp, xp, z3, 3, 1, 1, 0, xp, xp, ip, xp, None, None),             # no X scaler
+                 (xp, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None)]:            # parameters not set
+        assert lib.scfgp_acquire_kg(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'acquire_kg')
+        n += 1
 if ctx: lib.scfgp_destroy(ctx)
 print('host-side calls under ASan/UBSan:', n + 4, 'ok')
