@@ -22,6 +22,11 @@ pred_grad_ref.x_scaler_deriv) under the entry point's own bound -- the device's 
 1e-11 (tests/test_gpu_parity.py), far inside every such bound.  'y': the y scaler's backward transform is not Lipschitz (normal ppf), so
 a y-mode step follows a raw-mode step on the same rows and is checked, as the own tests do, against the host tail applied to the
 DEVICE's raw-mode outputs of that step with those tests' tolerances.
+
+The geometry sweep (SWEEP_GEOMETRIES, sweep_schedule; the helper of tests/test_posterior_geometry_ref.py and
+tests/test_gpu_posterior_geometry.py) uses the same runner, references and records on a lean schedule per geometry, scfgp_acquire_kg
+included (it joins that schedule only), with two further checks: (c) a call on row 0 alone against row 0 of the 257-row call, bit for
+bit, and (d) an f16x3 context against the f32 context, bit for bit.
 """
 import functools
 
@@ -31,6 +36,7 @@ from oracle import scfgp_oracle as O
 from scfgp_amd.scaler import Scaler
 from tests import acquire_ref as A
 from tests import condition_ref, forget_ref, loo_ref, parity, pred_cov_ref
+from tests import kg_ref as KG
 from tests import pred_grad_ref as G
 from tests import sample_argmax_ref as AM
 from tests import sample_grad_ref as SG
@@ -40,6 +46,7 @@ from tests import select_qei_ref as Q
 from tests import select_ref as R
 # tolerance constants of the entry points' own GPU tests (importing these modules needs no GPU)
 from tests import test_gpu_acquire as T_ACQ
+from tests import test_gpu_acquire_kg as T_KG
 from tests import test_gpu_predict_cov as T_COV
 from tests import test_gpu_predict_grad as T_PG
 from tests import test_gpu_round3 as T_R3
@@ -186,6 +193,7 @@ def _finite(*arrays):
 class RefEngine(object):
     """tests/*_ref.py and the oracle behind the methods of HipEngine that the sequences call"""
     METRICS = ('MAE', 'NMAE', 'MSE', 'NMSE', 'MNLP', 'SCORE')
+    ROW_BITS = False                          # numpy's products promise no bits of a row across row counts: (c) is checked to 1e-10 here
 
     def __init__(self, D, S, M, dtype='f64'):
         self.D, self.S, self.M = D, S, M
@@ -198,7 +206,7 @@ class RefEngine(object):
     def dims(self):
         ru = lambda v, m: (v + m - 1) // m * m
         k64 = ru(self.K, 64)
-        return dict(K=self.K, Kp=(k64 // 128 + k64 // 64 % 2) * 128, Dp=ru(self.D + 1, 16))
+        return dict(K=self.K, Kp=(k64 // 128 + k64 // 64 % 2) * 128, Jp=ru(self.K // 2, 128), Dp=ru(self.D + 1, 16), Sp=ru(self.S + 1, 16))
 
     # state
     def set_params(self, p):
@@ -345,6 +353,20 @@ class RefEngine(object):
             out['grad'] = self._chain((-1.0 if minimize else 1.0) * au[:, None] * dmu + as_[:, None] * dsig, J, cols, width)
         return out
 
+    def acquire_kg(self, Xc, alpha, Li, Xr=None, z=None, w=None, mode='scaled', noise=True, minimize=False, want=('kg', 'idx', 'val')):
+        """tests/kg_ref.py's restatement on the lines of this engine's own predict_cov, predict and sigma (the calls the records form the
+        device's lines from)"""
+        z = KG.check_nodes(KG.DEFAULT_NODES if z is None else z)
+        Xb = Xc if Xr is None else Xr
+        cov = self.predict_cov(Xc, Li, Xb=Xb, mode=mode)
+        mu_r = (self.predict if mode == 'scaled' else self.predict_raw)(Xb, alpha, Li)[0].ravel()
+        sd = self.acquire(Xc, alpha, Li, 'ucb', beta=0.0, mode=mode, noise=noise, want=('acq', 'sd'))['sd']
+        m, s, lo, hi = KG.node_table(KG.offsets(mu_r, minimize), KG.slopes(cov, sd), z)
+        kg, kg_hi = KG.bounds(m, s, lo, hi, z)
+        out = dict(kg=kg, kg_hi=kg_hi, m=m, s=s, idx=int(KG.argmax(kg, w)))
+        out['val'] = float(kg[out['idx']])
+        return {k: v for k, v in out.items() if k in want}
+
     def predict_cov(self, Xa, Li, Xb=None, mode='scaled', noise=False):
         Xa = self._rows(Xa, mode)[0]
         Xb = None if Xb is None else self._rows(Xb, mode)[0]
@@ -382,6 +404,8 @@ class RefEngine(object):
             raise FloatingPointError('loo: non-finite input')
         r = loo_ref.loo(X, y, alpha, Li, self.params, self.S, self.M, block)
         st = dict(zip(self.LOO_STATS, r['stats'].tolist())); st['n'] = int(st['n']); st['blocks'] = int(st['blocks'])
+        if block == 1:
+            st['sum_log_joint'] = st['sum_log_marginal']            # the header: block 1, the same number bit for bit
         return r['mu'].reshape(-1, 1), r['std'], r['lev'], st
 
     # selection
@@ -588,6 +612,353 @@ def check_all_schedules():
     return scheds
 
 
+# ---- the geometry sweep -------------------------------------------------------------------------------------------------------------------
+# What a posterior call launches depends on a few integer classes of (D, S, M); this set visits the classes the sequences above never
+# reach (tests/test_posterior_geometry_ref.py asserts that it covers them, tests/test_gpu_posterior_geometry.py runs it).  M = 1 is left
+# out on purpose: at (1, 1, 1) the oracle's penalty takes the log of a zero variance and the cost is infinite.
+SWEEP_GEOMETRIES = [
+    (1, 2, 2),        # K = 8:   D = 1; the smallest K of the training tests; one 64-tile, strip only
+    (7, 12, 3),       # K = 30:  M < S
+    (70, 5, 60),      # K = 130: 3 tiles, 2 live columns in the last, 4 partial slots; Dp = 80 > 64; rank-S projection live
+    (15, 15, 60),     # K = 150: D + 1 = Dp = 16 and S + 1 = Sp = 16 exactly
+    (16, 16, 70),     # K = 172: one past both (Dp = Sp = 32)
+    (6, 5, 91),       # K = 192: 3 full 64-tiles, the fourth block all padding
+    (9, 8, 120),      # K = 256: the last small plan; K = Kp; J = Jp = 128
+    (40, 6, 123),     # K = 258: the first 128-wide plan; remainder tile with 2 live columns; J = 129 -> Jp = 256; rank-S live
+    (33, 3, 158),     # K = 322: remainder of two 64-tiles, the second with 2 live columns
+    (5, 4, 188),      # K = 384: 128-wide plan with no remainder launch; K = Kp
+]
+SWEEP_ENTRY_POINTS = ('predict',) + POSTERIOR + ('acquire_kg',)          # all seventeen
+SWEEP_T = (257, 1)                                                       # one row past the 256-row padding, and its row 0 alone
+SWEEP_N = 300                                                            # rows in the fit
+SWEEP_MOVED = (1, 37)                                                    # rows condition and forget move; R of acquire_kg; pending / Xb rows
+
+
+# The seed of a group of steps of a geometry's schedule is drawn from (D, S, M, the group's number, its salt).  An output bounded relative to its own norm is a fair check only
+# where that norm is not a cancellation: row 0 alone may hold one number (one sample, D = 1) that happens to lie near 0 while the error
+# of its sum does not shrink with it.  A group's salt is the first for which conditioned_row0 holds for every such record of its steps,
+# a correct fp32 predict stands inside half its bound, and acquire's gradient terms do not cancel (acquire_grad_cancellation);
+# and the lines of an acquire_kg step on 257 rows are not near-parallel (kg_conditioning <= 1; at D = 1, K = 8 no draw of the step with
+# 37 reference rows meets it, and that step is exempt); tests/test_posterior_geometry_ref.py asserts all of it on the CPU references.  These are conditions on the choice of inputs, computed from the fp64 references alone, not tolerances.
+# (D, S, M) -> {group number: salt}; every other group: 0
+_SALT = {
+    (1, 2, 2): {0: 1, 5: 1, 6: 1, 15: 1, 16: 1, 18: 13, 19: 1, 21: 13, 24: 237, 34: 1, 35: 2},
+    (7, 12, 3): {12: 1, 14: 2, 18: 2, 21: 6, 22: 9},
+    (70, 5, 60): {6: 3, 13: 1, 14: 1, 16: 2, 21: 2, 22: 1},
+    (15, 15, 60): {18: 1, 19: 1, 21: 10, 22: 1},
+    (16, 16, 70): {12: 1, 14: 2, 16: 2, 19: 2, 21: 14, 22: 6, 24: 1},
+    (6, 5, 91): {4: 2, 6: 6, 14: 1, 15: 3, 16: 8, 17: 1, 20: 2, 21: 4},
+    (9, 8, 120): {14: 1, 15: 3, 16: 2, 21: 1, 35: 1},
+    (40, 6, 123): {10: 1, 12: 1, 13: 1, 14: 2, 18: 2, 21: 11, 22: 8, 35: 1},
+    (33, 3, 158): {4: 2, 5: 1, 6: 3, 10: 1, 14: 2, 15: 3, 16: 5, 18: 5, 19: 2, 20: 3, 21: 8, 22: 2},
+    (5, 4, 188): {4: 4, 6: 2, 16: 4, 17: 2, 20: 3, 21: 2},
+}
+SWEEP_SALT = {g + (n,): v for g, d in _SALT.items() for n, v in d.items()}
+ROW0_NORM = 0.5
+
+
+def conditioned_row0(ref_row0, ref_big):
+    """the reference of a norm-relative record of a step on row 0 alone holds at least ROW0_NORM of the rms row norm of the same record of
+    the 257-row step: the smaller check is then at most 1 / ROW0_NORM times as tight as the larger one (None: the two are not
+    row-aligned, as the symmetric covariance, whose 1 x 1 form is a variance)"""
+    r = np.asarray(ref_row0, np.float64); b = np.asarray(ref_big, np.float64)
+    if r.ndim == 0 or b.ndim == 0 or r.size == 0 or r.shape[1:] != b.shape[1:] or b.shape[0] <= r.shape[0]:
+        return None
+    fin = np.isfinite(b).reshape(len(b), -1).all(axis=1)
+    if not fin.any() or not np.isfinite(r).all():
+        return None
+    rms = float(np.linalg.norm(b[fin])) / np.sqrt(fin.sum() / len(r))
+    return bool(float(np.linalg.norm(r)) >= ROW0_NORM * rms)
+
+
+GRAD_CANCEL = 2.0
+
+
+def acquire_grad_cancellation(a, fit):
+    """(|a_u d mu| + |a_sigma d sigma|) / |a_u d mu + a_sigma d sigma| in norm over the step's rows, from the fp64 references: acquire's
+    gradient is a sum of two products, and tests/test_gpu_acquire.py's CHAIN_BOUND (a dozen ulp, norm-wise over thousands of elements)
+    is a fair check of a handful of elements only where the two do not cancel.  A condition on the inputs of the steps on row 0 alone:
+    at most GRAD_CANCEL."""
+    ref = _ref_engine(fit)
+    X = ref._rows(a['X'], a['mode'])[0]
+    mu, sd_star, dmu, dsd = G.predict_grad(X, a['alpha'], a['Li'], fit.params, fit.S, fit.M)
+    sd = sd_star if a['noise'] else A.sigma(kappa(fit.params), np.sum(pred_cov_ref.factor(X, a['Li'], fit.params, fit.S, fit.M) ** 2, axis=1), False)
+    kw = {'ucb': dict(beta=a['beta']), 'mes': dict(fstar=a['fstar'])}.get(a['kind'], dict(best=a['best'], xi=a['xi']))
+    _, au, as_ = A.acquire(a['kind'], mu.ravel(), sd, minimize=a['minimize'], **kw)
+    t1 = au[:, None] * dmu; t2 = as_[:, None] * (dsd if a['noise'] else dsd * (sd_star / sd)[:, None])
+    s = float(np.linalg.norm((-1.0 if a['minimize'] else 1.0) * t1 + t2))
+    return float(np.linalg.norm(np.abs(t1) + np.abs(t2))) / s if s > 0 else np.inf
+
+
+def kg_conditioning(a, fit):
+    """acquire_kg's sums are compared with tests/kg_ref.py's at the device's own node table in the measure max |delta| / max kg_hi under
+    tests/test_gpu_acquire_kg.py's VALUE_BOUND.  Both form J chord slopes q_j = (m_j+1 - m_j) / (z_j+1 - z_j) of size up to max |b| and
+    sum their DIFFERENCES, weighted by h(-|z_j|) <= h(0) < 0.4: one ulp of a quotient (another division, a fused multiply-add) moves a
+    sum by up to J 0.4 u max |b|, whatever the sums are.  Where the lines of the reference rows are nearly parallel (few features, D = 1)
+    max kg_hi is far smaller than max |b| and that measure is no check of the kernel.  Returns J 0.4 u max |b| / (VALUE_BOUND max kg_hi)
+    from the fp64 references: a condition on the inputs, at most 1 (0 where R = 1: both sums are exactly 0)."""
+    ref = _ref_engine(fit)
+    z = KG.DEFAULT_NODES if a['z'] is None else a['z']
+    Xb = a['X'] if a['Xr'] is None else a['Xr']
+    if len(Xb) == 1:
+        return 0.0
+    cov = ref.predict_cov(a['X'], a['Li'], Xb=Xb, mode=a['mode'])
+    sd = ref.acquire(a['X'], a['alpha'], a['Li'], 'ucb', beta=0.0, mode=a['mode'], noise=a['noise'], want=('acq', 'sd'))['sd']
+    hi = ref.acquire_kg(a['X'], a['alpha'], a['Li'], Xr=a['Xr'], z=a['z'], mode=a['mode'], noise=a['noise'], minimize=a['minimize'],
+                        want=('kg_hi',))['kg_hi']
+    return float(len(z) * 0.4 * 2.0 ** -53 * np.abs(KG.slopes(cov, sd)).max() / (T_KG.VALUE_BOUND * hi.max()))
+
+
+def geometry_classes(D, S, M):
+    """the integer classes of a geometry, restated from ApplyPlan (apply.hip) and derive_geom: the column plan of the apply products
+    (n128 tiles 128 wide, then n64 tiles 64 wide, `last` live columns in the last 64-wide tile), the padding of K (Kp, gfull, gstrip;
+    `slots` = Kp / 64 partial slots against `covered`, the 64-column blocks the plan's tiles span), and the pads of J, D + 1 and S + 1"""
+    ru = lambda v, m: (v + m - 1) // m * m
+    K = 2 * (S + M); J = S + M
+    small = K <= 256
+    n128 = 0 if small else K // 128
+    n64 = -(-(K - 128 * n128) // 64)
+    last = K - 128 * n128 - 64 * (n64 - 1) if n64 else 0
+    k64 = ru(K, 64) // 64
+    gfull, gstrip = k64 // 2, k64 % 2
+    Kp = 128 * (gfull + gstrip)
+    Jp, Dp, Sp = ru(J, 128), ru(D + 1, 16), ru(S + 1, 16)
+    return dict(K=K, J=J, small=small, n128=n128, n64=n64, last=last, tiles=n128 + n64, covered=2 * n128 + n64, slots=Kp // 64, Kp=Kp,
+                gfull=gfull, gstrip=gstrip, Jp=Jp, jpad=Jp - J, Dp=Dp, dpad=Dp - (D + 1), Sp=Sp, spad=Sp - (S + 1), lowrank=Sp < Dp,
+                m_lt_s=M < S)
+
+
+# the classes the set is there for: name -> condition on geometry_classes' dict (D is passed beside it)
+SWEEP_CLASSES = {
+    'D = 1': lambda c, D: D == 1,
+    'K < 42': lambda c, D: c['K'] < 42,
+    'K = 8, strip only': lambda c, D: c['K'] == 8 and c['gfull'] == 0 and c['gstrip'] == 1 and c['tiles'] == 1,
+    'M < S': lambda c, D: c['m_lt_s'],
+    'small plan of three tiles': lambda c, D: c['small'] and c['n64'] == 3 and 128 < c['K'] <= 192,
+    'three tiles, 2 live columns in the last, four partial slots': lambda c, D: c['small'] and c['n64'] == 3 and c['last'] == 2 and c['slots'] == 4,
+    'three full 64-tiles, the fourth block all padding': lambda c, D: c['small'] and c['n64'] == 3 and c['last'] == 64 and c['slots'] == 4,
+    'more partial slots than the plan covers': lambda c, D: c['slots'] > c['covered'],
+    'Dp > 64': lambda c, D: c['Dp'] > 64,
+    'rank-S projection live, small plan': lambda c, D: c['lowrank'] and c['small'],
+    'rank-S projection live, 128-wide plan': lambda c, D: c['lowrank'] and not c['small'],
+    'rank-S projection off': lambda c, D: not c['lowrank'],
+    'D + 1 = Dp and S + 1 = Sp': lambda c, D: c['dpad'] == 0 and c['spad'] == 0,
+    'D + 1 and S + 1 one past the 16 boundary': lambda c, D: c['dpad'] == 15 and c['spad'] == 15,
+    'K = 256 = Kp, the last small plan, J = Jp': lambda c, D: c['K'] == 256 and c['small'] and c['Kp'] == 256 and c['jpad'] == 0,
+    'K = 258: first 128-wide plan, 2 live remainder columns, J one past Jp': lambda c, D: (c['K'] == 258 and c['n128'] == 2 and c['n64'] == 1
+                                                                                         and c['last'] == 2 and c['jpad'] == 127),
+    'remainder of two 64-tiles, 2 live columns in the second': lambda c, D: c['n128'] > 0 and c['n64'] == 2 and c['last'] == 2,
+    '128-wide plan with no remainder launch, K = Kp': lambda c, D: c['n128'] > 0 and c['n64'] == 0 and c['K'] == c['Kp'],
+    'a strip (odd number of 64-blocks)': lambda c, D: c['gstrip'] == 1 and c['gfull'] > 0,
+    'no strip': lambda c, D: c['gstrip'] == 0,
+    'K <= 256: no f16x3 split products': lambda c, D: c['small'],
+    'K > 256: f16x3 split products run': lambda c, D: not c['small'],
+}
+
+
+def classes_of(D, S, M):
+    c = geometry_classes(D, S, M)
+    return {name for name, cond in SWEEP_CLASSES.items() if cond(c, D)}
+
+
+# (c) outputs of which include/scfgp_hip.h documents that a row's values depend on that row alone (not on T, the row's position or the
+# chunk): sample ("the same functions on any rows", eps by the row's index), sample_grad, acquire, acquire_kg with explicit reference
+# rows, predict_cov's element guarantee, loo for rows of the same block (block 1 here), select_qei's scores
+ROW_ALONE = {'sample': ('out',), 'sample_grad': ('val', 'grad'), 'acquire': ('acq', 'mu', 'sd', 'grad'), 'acquire_kg': ('kg', 'kg_hi', 'm', 's'),
+             'predict_cov': ('cov',), 'loo': ('mu', 'sd', 'lev'), 'select_qei': ('score0',)}
+# (d) outputs of which the header says that SCFGP_F16X3 contexts agree with SCFGP_F32 bit for bit (forget: the fp64 first pass and K x K
+# stage, i.e. the factors; its mu / std come from predict's pass, for which nothing is claimed)
+F16X3_EQUAL = {'sample': ('out',), 'sample_argmax': ('idx', 'val'), 'sample_grad': ('val', 'grad'),
+               'acquire': ('acq', 'idx', 'val', 'mu', 'sd', 'grad'), 'acquire_kg': T_KG.ALL, 'predict_cov': ('cov',),
+               'condition': ('alpha', 'Li'), 'forget': ('alpha', 'Li'), 'loo': ('mu', 'sd', 'lev', 'stats'),
+               'select': ('idx', 'var', 'gain', 'sd'), 'select_iv': ('idx', 'red', 'var', 'ivar', 'sd'),
+               'select_qei': ('idx', 'gain', 'qei', 'score0', 'mstate')}
+
+
+def row_alone(a):
+    """does (c) apply to this step"""
+    ep = a['ep']
+    if ep not in ROW_ALONE:
+        return False
+    if ep == 'loo':
+        return a['block'] == 1 and not a.get('resident')
+    if ep == 'acquire_kg':
+        return a['Xr'] is not None
+    return True
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_schedule(D, S, M):
+    """the lean schedule of one geometry, a function of the geometry alone: parameters, 300 rows, an X and a y scaler, then every posterior
+    entry point in every mode it has, each at T = 257 and then on row 0 of those rows alone (`row0_of` names the step whose arguments
+    the T = 1 step takes row 0 of).  No training calls, option changes or failing calls: the sequences above cover those."""
+    count = [0]
+
+    def seed():
+        """the seed of the next group of steps: a function of the geometry, the group's number and its salt"""
+        n = count[0]; count[0] += 1
+        return int(np.random.default_rng([0x6E0, D, S, M, n, SWEEP_SALT.get((D, S, M, n), 0)]).integers(1, 2 ** 31))
+
+    algos = list(Scaler.algos)
+    h = D + 3 * S + 7 * M
+    steps = [dict(op='xscaler', algo=algos[h % 5]), dict(op='params', seed=seed(), head=True), dict(op='data', seed=seed(), N=SWEEP_N, head=True),
+             dict(op='yscaler', algo=algos[(h + 2) % 5])]
+    base = dict(op='post', mode='scaled', mask=False, minimize=False, noise=False, nsamp=7, m=5, block=1, flag=False, kind='ei', u=0.5)
+
+    def both(ep, mode='scaled', **kw):
+        """the step (mode 'pair': its raw-mode step and the y-mode step checked against it) at T = 257, then on row 0"""
+        st = dict(base, ep=ep, group=count[0], seed=seed(), **kw)
+        if ep == 'predict_y':
+            group = [dict(st, ep='predict_raw', mode='raw'), dict(st, mode='y')]
+        elif mode == 'pair':
+            group = [dict(st, mode='raw', pair=True), dict(st, mode='y', pair=True)]
+        else:
+            group = [dict(st, mode=mode)]
+        ids = [len(steps) + i for i in range(len(group))]
+        steps.extend(dict(g, T=SWEEP_T[0]) for g in group)
+        steps.extend(dict(g, T=SWEEP_T[1], row0_of=i) for g, i in zip(group, ids))
+
+    one = lambda ep, T, mode='scaled', **kw: steps.append(dict(base, ep=ep, T=T, mode=mode, group=count[0], seed=seed(), **kw))
+    both('predict')
+    both('predict_y', flag=True)                                                   # predict_raw, then predict_y with targets
+    both('predict_grad', flag=True); both('predict_grad', flag=False); both('predict_grad', 'pair', flag=True)
+    for ns in (1, 7):
+        one('sample_weights', 1, nsamp=ns)
+    both('sample', nsamp=7, noise=True); both('sample', 'raw', nsamp=1); both('sample', 'pair', nsamp=7)
+    both('sample_argmax', nsamp=7, mask=True); both('sample_argmax', 'pair', nsamp=1, minimize=True)
+    both('sample_grad', nsamp=7, flag=True, noise=True); both('sample_grad', 'raw', nsamp=7); both('sample_grad', 'pair', nsamp=1)
+    for i, kind in enumerate(A.KINDS):
+        both('acquire', ('scaled', 'raw')[i % 2], kind=kind, flag=True, noise=i % 3 == 0, minimize=i % 2 == 1, mask=i == 2, nsamp=(7, 1)[i % 2])
+    both('acquire_kg', R=SWEEP_MOVED[1], nodes=None, noise=True, mask=True)
+    both('acquire_kg', 'raw', R=SWEEP_MOVED[0], nodes=3, noise=False)
+    both('acquire_kg', R=0, nodes=17, noise=True, minimize=True)                   # the candidates are their own reference set
+    both('predict_cov', flag=False, noise=True); both('predict_cov', 'raw', flag=True)
+    one('loo', SWEEP_N, block=64, flag=True, resident=True)
+    both('loo', 'raw', block=1); both('loo', block=64)
+    both('select', mask=True); both('select', 'raw')
+    both('select_iv', flag=True, mask=True); both('select_iv', 'raw', flag=False)
+    both('select_qei', nsamp=7, flag=True, mask=True); both('select_qei', 'raw', nsamp=1, flag=False, minimize=True)
+    # condition and forget move the fit last: 300 -> 301 -> 338 -> 337 -> 300 rows (u picks forget's output groups in `call`)
+    one('condition', SWEEP_MOVED[0]); one('condition', SWEEP_MOVED[1], 'raw')
+    one('forget', SWEEP_MOVED[0], 'raw', u=2.5 / 997); one('forget', SWEEP_MOVED[1], u=1.5 / 997)
+    both('predict')                                                                # the moved fit is used once more
+    for st in steps:
+        if st['op'] == 'post' and st['ep'] == 'loo':
+            st.setdefault('resident', False)
+    return steps
+
+
+def check_sweep(steps):
+    """what the sweep schedule must hold (conditions, not tuning)"""
+    assert [st['op'] for st in steps[:4]] == ['xscaler', 'params', 'data', 'yscaler'] and steps[2]['N'] == SWEEP_N
+    post = steps[4:]
+    assert all(st['op'] == 'post' for st in post)
+    by = lambda ep: [st for st in post if st['ep'] == ep]
+    assert {st['ep'] for st in post} == set(SWEEP_ENTRY_POINTS)
+    for ep in SWEEP_ENTRY_POINTS:
+        Ts = {st['T'] for st in by(ep)}
+        if ep in ('condition', 'forget'):
+            assert Ts == set(SWEEP_MOVED), (ep, Ts)
+        elif ep != 'sample_weights':
+            assert set(SWEEP_T) <= Ts, (ep, Ts)
+        modes = {st['mode'] for st in by(ep)}
+        want = {'predict': {'scaled'}, 'predict_raw': {'raw'}, 'predict_y': {'y'}, 'sample_weights': {'scaled'}}.get(
+            ep, {'scaled', 'raw', 'y'} if ep in Y_MODE else {'scaled', 'raw'})
+        assert modes == want, (ep, modes)
+    for i, st in enumerate(steps):
+        if st['op'] == 'post' and st['mode'] == 'y':                               # a raw-mode step directly before its y-mode step
+            p = steps[i - 1]
+            assert p['seed'] == st['seed'] and p['T'] == st['T'] and p['mode'] == 'raw' and p['ep'] == st['ep'].replace('predict_y', 'predict_raw')
+        if 'row0_of' in st:
+            b = steps[st['row0_of']]
+            assert st['T'] == 1 and b['T'] == SWEEP_T[0] and b['seed'] == st['seed'] and b['ep'] == st['ep'] and b['mode'] == st['mode']
+    assert {(st['block'], st['resident']) for st in by('loo')} == {(64, True), (1, False), (64, False)}
+    assert {st['flag'] for st in by('predict_cov')} == {True, False} and {st['flag'] for st in by('select_qei')} == {True, False}
+    assert {st['R'] for st in by('acquire_kg')} == {0} | set(SWEEP_MOVED)
+    for ep in ('sample', 'sample_weights', 'sample_argmax', 'sample_grad', 'select_qei'):
+        assert {st['nsamp'] for st in by(ep)} == {1, 7}, ep
+    assert {st['kind'] for st in by('acquire')} == set(A.KINDS)
+    return dict(steps=len(steps), posterior=len(post))
+
+
+def _row0(big, T):
+    """the arguments of the T-row step made on the first T rows of a prepared step's rows: every per-row argument cut, the call's
+    scalars (incumbents, sampled maxima, weights W, reference and pending rows) kept"""
+    a = dict(big, T=T)
+    for k in ('X', 'Xraw', 'y', 'yraw', 'targets', 'sidx', 'rows'):
+        if a.get(k) is not None:
+            a[k] = np.ascontiguousarray(a[k][:T])
+    if 'w' in a:
+        a['w'] = None                                                              # as materialise: no mask on fewer rows than it keeps
+    if 'm' in a and a['ep'].startswith('select'):
+        a['m'] = min(big['m'], T)
+    if a['ep'] == 'select_iv' and a.get('ref_rows') is not None:
+        a['ref_rows'] = np.arange(0, T, 3)
+        a['Xr'] = np.ascontiguousarray(a['X'][a['ref_rows']]); a['wr'] = big['wr'][:len(a['ref_rows'])]
+    return a
+
+
+def row0_records(a, got, big_got, bits=True):
+    """(c) the outputs of the call on row 0 alone against row 0 of the larger call's: bit for bit (bits=False, for references whose
+    products promise no bits across row counts: the finite pattern and 1e-10)"""
+    recs = []
+    T = a['T']
+    for k in ROW_ALONE[a['ep']]:
+        g, b = got.get(k), big_got.get(k)
+        if g is None or b is None:
+            continue
+        g = np.asarray(g); b = np.asarray(b)[:T]
+        if a['ep'] == 'predict_cov' and a['Xb'] is None:
+            b = b[:, :T]
+        label = '(c) %s of row 0 alone against the %d-row call\'s' % (k, len(np.asarray(big_got[k])))
+        if bits:
+            recs.append((label, 'exact', g, b, None))
+        else:
+            fin = np.isfinite(g) & np.isfinite(b)
+            recs.append((label + ' finite pattern', 'exact', np.isfinite(g), np.isfinite(b), None))
+            recs.append((label, 'relnorm', g[fin], b[fin], 1e-10))
+    return recs
+
+
+def mirror_records(a, got, other, name):
+    """(d) the outputs of a second context that made the same call, where the header says the two modes agree bit for bit"""
+    recs = []
+    for k in F16X3_EQUAL.get(a['ep'], ()):
+        if k not in got or got[k] is None:
+            continue
+        g, o = got[k], other[k]
+        if isinstance(g, dict):
+            g = np.array([g[j] for j in sorted(g)], np.float64); o = np.array([o[j] for j in sorted(o)], np.float64)
+        recs.append(('(d) %s of the %s context against this one\'s' % (k, name), 'exact', np.asarray(o), np.asarray(g), None))
+    return recs
+
+
+def ratio(rec):
+    """how far into its bound a bounded record went (error / allowance; None for the exact ones and where nothing is bounded)"""
+    label, kind, got, ref, par = rec
+    with np.errstate(all='ignore'):
+        if kind == 'relnorm':
+            n = float(np.linalg.norm(np.asarray(ref)))
+            return float(np.linalg.norm(np.asarray(got) - np.asarray(ref))) / (par * n) if n > 0 else None
+        if kind == 'abs':
+            e = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64)); p = np.broadcast_to(np.asarray(par, np.float64), e.shape)
+            ok = p > 0
+            return float((e[ok] / p[ok]).max()) if np.any(ok) else None
+        if kind == 'allclose':
+            g = np.asarray(got, np.float64); r = np.asarray(ref, np.float64)
+            return float((np.abs(g - r) / (par[1] + par[0] * np.abs(r))).max()) if g.size else None
+        if kind == 'predict':
+            return float(parity.predict_ratio(got[0], got[1], ref[0], ref[1], par))
+        if kind == 'alpha':
+            return float(parity.alpha_ratio(got, ref, par))
+        if kind == 'li':
+            return float(parity.li_ratio(got, ref, par))
+        if kind == 'kinderr':
+            k, mu, sd, beta = par
+            return float(A.kind_error(k, got, ref, mu, sd, beta) / T_ACQ.PARITY_BOUND[k])
+    return None
+
+
 # ---- checks: records (label, kind, got, ref, par) -------------------------------------------------------------------------------------
 def evaluate(rec):
     """assert one record"""
@@ -744,6 +1115,10 @@ def materialise(st, fit):
         a['want_val'] = bool(st['noise'] or st.get('pair'))
     elif ep in ('sample_argmax', 'acquire'):
         a['w'] = mask(T)
+    elif ep == 'acquire_kg':
+        a['w'] = mask(T)
+        a['Xr'] = give(raw_rows(rng, st['R'], D)) if st['R'] else None      # R = 0: the candidates are their own reference set
+        a['z'] = None if st['nodes'] is None else T_KG.NODES[st['nodes']]
     elif ep == 'predict_cov':
         if st['flag'] or st['op'] == 'fail':
             Tb = int(rng.choice([1, 37, 257, 3000])) if T <= 700 else int(rng.choice([1, 37, 257]))
@@ -807,6 +1182,8 @@ def call(eng, a):
     if ep == 'acquire':
         kw = {'ucb': dict(beta=a['beta']), 'mes': dict(fstar=a['fstar'])}.get(a['kind'], dict(best=a['best'], xi=a['xi']))
         return eng.acquire(X, al, Li, a['kind'], w=a['w'], mode=mode, noise=a['noise'], minimize=a['minimize'], want=a['want'], **kw)
+    if ep == 'acquire_kg':
+        return eng.acquire_kg(X, al, Li, Xr=a['Xr'], z=a['z'], w=a['w'], mode=mode, noise=a['noise'], minimize=a['minimize'], want=T_KG.ALL)
     if ep == 'predict_cov':
         return dict(cov=eng.predict_cov(X, Li, Xb=a['Xb'], mode=mode, noise=a['noise'] and (a['Xb'] is None or a['op'] == 'fail')))
     if ep == 'condition':
@@ -840,6 +1217,12 @@ def auxiliary(eng, a, got, fit):
         aux['P'] = None if a['pending'] is None else eng.sample(a['pending'], al, Li, a['nsamp'], seed=a['seed'] % 1000, mode=mode, noise=False)
     elif ep == 'acquire' and 'grad' in a['want']:
         aux['pg'] = eng.predict_grad(X, al, Li, mode=mode)
+    elif ep == 'acquire_kg':
+        # the lines of tests/test_gpu_acquire_kg.py's _device_lines, in the step's mode: the device's own predict_cov, predict and sigma
+        Xb = X if a['Xr'] is None else a['Xr']
+        aux['cov'] = eng.predict_cov(X, Li, Xb=Xb, mode=mode)
+        aux['mu_r'], aux['sd_r'] = (eng.predict if mode == 'scaled' else eng.predict_raw)(Xb, al, Li)
+        aux['sd'] = eng.acquire(X, al, Li, 'ucb', beta=0.0, mode=mode, noise=a['noise'], want=('acq', 'sd'))['sd']
     elif ep in ('condition', 'forget') and 'alpha' in got:
         aux['probe'] = fit.fx(raw_rows(np.random.default_rng(a['seed'] + 1), 200, fit.D))
         aux['predict'] = eng.predict(aux['probe'], got['alpha'], got['Li'])
@@ -970,6 +1353,31 @@ def records(a, got, aux, fit, dtype, prev):
             _, sd_star, dmu, dstd = aux['pg']
             dsig = dstd if a['noise'] else dstd * (sd_star / sd)[:, None]
             add('grad', 'relnorm', got['grad'], (-1.0 if a['minimize'] else 1.0) * au[:, None] * dmu + as_[:, None] * dsig, T_ACQ.CHAIN_BOUND)
+    elif ep == 'acquire_kg':
+        z = KG.DEFAULT_NODES if a['z'] is None else a['z']
+        Xb = a['X'] if a['Xr'] is None else a['Xr']
+        # the lines themselves against the references, under predict_cov's and predict's bounds
+        # element by element: cov_ij = kappa <c_i, c_j> is bilinear in two factor rows, each good to half of predict_cov's bound relative
+        # to its own norm (tests/test_gpu_predict_cov.py: BOUNDS), so |delta cov_ij| <= BOUNDS kappa |c_i| |c_j|.  The norm-wise form of
+        # that test does not carry over to R = 1 or T = 1, where the matrix is a few off-diagonal elements that may cancel
+        ni = np.linalg.norm(pred_cov_ref.factor(Xs, Li, params, S, M), axis=1)
+        nj = ni if a['Xr'] is None else np.linalg.norm(pred_cov_ref.factor(ref._rows(a['Xr'], mode)[0], Li, params, S, M), axis=1)
+        add('cov of the lines', 'abs', aux['cov'], ref.predict_cov(a['X'], Li, Xb=Xb, mode=mode), T_COV.BOUNDS[dtype] * kap * np.outer(ni, nj))
+        add('mu of the reference rows', 'predict', (aux['mu_r'], aux['sd_r']),
+            (ref.predict if mode == 'scaled' else ref.predict_raw)(Xb, al, Li), dtype)
+        # tests/test_gpu_acquire_kg.py: the node table bit for bit from the device's own lines, the sums at the device's own table
+        m, s, lo, hi = KG.node_table(KG.offsets(np.ravel(aux['mu_r']), a['minimize']), KG.slopes(aux['cov'], aux['sd']), z)
+        add('m', 'exact', got['m'], m, None); add('s', 'exact', got['s'], s, None)
+        add('m is 0 at the node 0', 'exact', got['m'][:, list(z).index(0.0)] == 0.0, np.ones(len(m), bool), None)
+        kg, kg_hi = KG.bounds(got['m'], got['s'], lo, hi, z)
+        allow = T_KG.VALUE_BOUND * kg_hi.max()
+        add('kg', 'abs', got['kg'], kg, allow); add('kg_hi', 'abs', got['kg_hi'], kg_hi, allow)
+        add('0 <= kg <= kg_hi', 'exact', np.array([bool((got['kg'] >= 0).all()), bool((got['kg'] <= got['kg_hi'] + allow).all())]),
+            np.ones(2, bool), None)
+        if len(Xb) == 1:
+            add('both sums are 0 at R = 1', 'exact', np.array([np.abs(got['kg']).max(), np.abs(got['kg_hi']).max()]), np.zeros(2), None)
+        add('argmax idx', 'exact', got['idx'], int(KG.argmax(got['kg'], a['w'])), None)
+        add('argmax val', 'exact', got['val'], float(got['kg'][got['idx']]), None)
     elif ep == 'predict_cov':
         add('cov', 'relnorm', got['cov'], ref.predict_cov(a['X'], Li, Xb=a['Xb'], mode=mode, noise=a['noise'] and a['Xb'] is None),
             T_COV.BOUNDS[dtype])
@@ -1141,31 +1549,44 @@ def rel(a, b):
 
 
 class Runner(object):
-    """one context through one schedule.  make_engine(D, S, M, dtype) builds the context under test and every twin."""
+    """one context through one schedule.  make_engine(D, S, M, dtype) builds the context under test and every twin.  `ci`: a case number
+    of CASES, whose schedule make_schedule(ci) is; or a tuple (D, S, M, dtype), with explicit steps given to run() (the geometry sweep).
+    `mirror`: the dtype of a second context that lives through the same schedule and makes every posterior step's call once more, its
+    outputs compared bit for bit where F16X3_EQUAL lists them (d).  A step with `row0_of` takes row 0 of that earlier step's arguments
+    and is compared with its outputs where ROW_ALONE lists them (c)."""
 
-    def __init__(self, ci, make_engine, twins=True, on_records=None):
-        (self.D, self.S, self.M), self.dtype = CASES[ci]
+    def __init__(self, ci, make_engine, twins=True, on_records=None, mirror=None, collect=False):
+        if isinstance(ci, tuple):
+            self.D, self.S, self.M, self.dtype = ci
+        else:
+            (self.D, self.S, self.M), self.dtype = CASES[ci]
         self.ci = ci
+        self.mirror = mirror
+        self.failures = [] if collect else None       # collect: the records that miss are listed here, the schedule goes on
         self.make_engine = make_engine
         self.twins = twins
         self.on_records = on_records
         self.fit = Fit(self.D, self.S, self.M)
         self.eng = make_engine(self.D, self.S, self.M, self.dtype)
+        self.engines = [self.eng] + ([make_engine(self.D, self.S, self.M, mirror)] if mirror is not None else [])
         self.log = []
         self.prev = None
+        self.kept = {}                        # step number -> (arguments, outputs) of the steps a later `row0_of` names
         self.min_pivot2 = []
-        self.counts = dict(twin=0, records=0, failing=0)
+        self.counts = dict(twin=0, records=0, failing=0, row0=0, mirror=0)
 
     def close(self):
-        self.eng.close()
+        for e in self.engines:
+            e.close()
 
     def _where(self, i):
-        return 'step %d of case %d %s %s; steps so far: %s' % (i, self.ci, (self.D, self.S, self.M), self.dtype, self.log)
+        return 'step %d of case %s %s %s; steps so far: %s' % (i, self.ci, (self.D, self.S, self.M), self.dtype, self.log)
 
     def _resident(self):
         f = self.fit
         X, y = f.X(), f.y()
-        self.eng.set_data(X, y)
+        for e in self.engines:
+            e.set_data(X, y)
         f.resident = (X, y); f.resident_in_fit = True
 
     def _twin(self, a):
@@ -1186,6 +1607,7 @@ class Runner(object):
 
     def run(self, steps=None):
         steps = make_schedule(self.ci) if steps is None else steps
+        self.row0_wanted = {st['row0_of'] for st in steps if 'row0_of' in st}
         for i, st in enumerate(steps):
             self.log.append(' '.join([st['op']] + ['%s=%s' % (k, st[k]) for k in ('ep', 'T', 'mode', 'err', 'algo', 'N') if k in st]))
             try:
@@ -1201,15 +1623,21 @@ class Runner(object):
         ctol, gtol, ptol = SEQ_TOL[dtype]
         op = st['op']
         if op == 'xscaler':
-            f.xs = x_scaler(st['algo'], D); f.touch(); eng.set_x_scaler(f.xs)
+            f.xs = x_scaler(st['algo'], D); f.touch()
+            for e in self.engines:
+                e.set_x_scaler(f.xs)
             if f.Xraw is not None:
                 self._resident()
         elif op == 'yscaler':
-            f.ys = y_scaler(st['algo']); f.touch(); eng.set_y_scaler(f.ys)
+            f.ys = y_scaler(st['algo']); f.touch()
+            for e in self.engines:
+                e.set_y_scaler(f.ys)
             if f.Xraw is not None:
                 self._resident()
         elif op == 'params':
-            f.params = new_params(np.random.default_rng(st['seed']), D, S, M); f.touch(); eng.set_params(f.params)
+            f.params = new_params(np.random.default_rng(st['seed']), D, S, M); f.touch()
+            for e in self.engines:
+                e.set_params(f.params)
         elif op == 'data':
             rng = np.random.default_rng(st['seed'])
             f.Xraw = raw_rows(rng, st['N'], D); f.yraw = raw_targets(rng, f.Xraw); f.touch()
@@ -1258,9 +1686,14 @@ class Runner(object):
             self.prev = None
             return
         elif op == 'post':
-            a = prepare(eng, materialise(st, f), f)
+            if 'row0_of' in st:
+                a = _row0(self.kept[st['row0_of']][0], st['T'])
+            else:
+                a = prepare(eng, materialise(st, f), f)
             got = call(eng, a)
             aux = auxiliary(eng, a, got, f)
+            if i in self.row0_wanted:
+                self.kept[i] = (dict(a), got)
             if self.twins:
                 twin = self._twin(a)
                 assert got.keys() == twin.keys()
@@ -1268,13 +1701,22 @@ class Runner(object):
                     assert same_bits(got[k], twin[k]), ('(a) output %r differs from a fresh context\'s' % k)
                 self.counts['twin'] += 1
             recs = records(a, got, aux, f, dtype, self.prev)
+            if 'row0_of' in st and row_alone(a):
+                r0 = row0_records(a, got, self.kept[st['row0_of']][1], bits=getattr(eng, 'ROW_BITS', True))
+                recs += r0; self.counts['row0'] += len(r0)
+            if self.mirror is not None:
+                rm = mirror_records(a, got, call(self.engines[1], a), self.mirror)
+                recs += rm; self.counts['mirror'] += len(rm)
             if self.on_records is not None:
                 self.on_records(i, a, got, recs)
             for r in recs:
                 try:
                     evaluate(r)
                 except AssertionError as e:
-                    raise AssertionError('(b) %s %s' % (a['ep'], e))
+                    msg = '%s%s %s' % ('' if str(r[0]).startswith('(') else '(b) ', a['ep'], e)
+                    if self.failures is None:
+                        raise AssertionError(msg)
+                    self.failures.append('step %d (%s): %s' % (i, self.log[-1], msg))
             self.counts['records'] += len(recs)
             self.prev = got if st['mode'] == 'raw' else None
             # condition and forget move the fit
