@@ -433,6 +433,46 @@ int scfgp_forget(scfgp_ctx* ctx, const double* Xo, const double* yo, int64_t n, 
 int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode, int block,
               double* mu, double* std, double* lev, double* stats);
 
+/* ---- posterior covariance of the input gradient, and the active-subspace matrix of a pool (no reference counterpart) -------------------
+ * scfgp_predict_grad differentiates the two predictive moments; this is the posterior DISTRIBUTION of grad f(x) itself.  Notation of
+ * Phi = s [cos Z | sin Z], Z = X~ F_all, F_all[d] = [l_F[d,:] | F[d,:]], F = l_F r_F^T, B = A^-1 = Li^T Li, kappa =
+ * softplus(c).  grad f(x) = J(x)^T w is linear in the K weights w ~ N(alpha, kappa A^-1), hence Gaussian with mean grad mu* and
+ * covariance kappa J(x)^T A^-1 J(x).  The derivative partner of a feature row is phi'(x) = (-phi_s | phi_c) = s [-sin z | cos z].
+ * Every phase is z = x l_F [I | r_F^T] + offset, so every gradient lies in span(l_F): with q = min(D, S), Q (J x q) and P (D x q) such that
+ * F_all[d][j] = sum_i P[d][i] Q[j][i],
+ *     D <= S (dense form,  q = D): Q[j][i] = F_all[i][j], P = I            D > S (latent form, q = S): Q = [I_S | r_F^T]^T, P = l_F
+ * and per point t
+ *     Psi_t (q x K): row i = phi'_t o (Q[:,i] ; Q[:,i])     C'_t = Psi_t Li^T (q x K)     H_t = C'_t C'_t^T (q x q)
+ *     Sigma_t = kappa P H_t P^T (D x D) = Cov[grad f(x_t)]          m_t = grad mu*(x_t)  (scfgp_predict_grad's dmu)
+ * There is no noise term: the observation noise has no gradient.  mode 0: scaled Xs.  mode 1: column-selected raw Xs through the
+ * registered X scaler; with g_t[d] the derivative of its forward transform at the raw input (the factors scfgp_predict_grad applies),
+ * m_t -> g_t o m_t and Sigma_t -> diag(g_t) Sigma_t diag(g_t).  There is no raw-y mode: through a non-affine y scaler the gradient is
+ * not Gaussian (the argument of SCFGP.predict_cov).
+ * Active-subspace matrix of the call's rows, with optional weights w_t >= 0 (w == NULL: all 1):
+ *     asub = sum_t w_t (m_t m_t^T + Sigma_t) / sum_t w_t  (D x D) = E[grad f grad f^T] averaged over the rows.
+ * Outputs, each may be NULL, at least one must be given: dmu (T x D), dvar (T x D, the diagonal of Sigma_t), dcov (T x D x D), asub
+ * (D x D).  w is read only when asub is given.
+ * Limit: min(D, S) <= 64 -- a point's q derivative rows lie in one 64-row group of the block kernel, as scfgp_loo's block <= 64.
+ * Chunks: the rows go through in chunks of np points,
+ *     np = floor(32768 / gs) (64 / q)   with gs = (64 / q) q  (integer divisions; whole groups of 64 / q points in the 32 768-row buffers)
+ * and, when dcov or asub is wanted (a D x D array per point: a dcov slot, the records of asub), np = min(np, max(1, floor(64 MiB /
+ * (8 D^2)))).  HipEngine.gradcov_points_per_chunk(want_cov) returns it.
+ * Promises:
+ *  1. dmu is scfgp_predict_grad's dmu of the same mode, bit for bit.
+ *  2. A point's dvar / dcov depend on that point alone: not on T, its position or the chunk.
+ *  3. dcov[t] is symmetric bit for bit and dvar[t][d] == dcov[t][d][d] bit for bit (the lower triangle is computed, the upper is its
+ *     mirror).
+ *  4. asub is symmetric bit for bit.
+ *  5. The sums of asub are added in row order in fp64, one summation order per entry, continued across chunks: the same bits on every
+ *     run; rows of weight 0 behind the last weighted row do not change them.
+ *  6. SCFGP_F16X3 contexts agree with SCFGP_F32 bit for bit (none of these products uses the split).  C' runs in the context's
+ *     precision; H_t is formed by fp64 MFMA and everything after it is fp64.
+ *  7. Device memory does not grow with T.
+ * SCFGP_EARG (with a scfgp_last_error text, before any output is written) for bad pointers, T < 1, a bad mode, no output, a missing X
+ * scaler in mode 1, parameters not set, a negative or non-finite weight, sum w = 0, or min(D, S) > 64. */
+int scfgp_predict_gradcov(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int mode,
+                          double* dmu, double* dvar, double* dcov, double* asub);
+
 /* ---- greedy maximum-information choice of m rows from a pool (no reference counterpart) ----------------------------------------------
  * Which rows should be observed next?  The posterior of a Fourier-feature model is a Bayesian linear model in K weights, and the
  * posterior variance after an observation does not depend on the observed value, so the exact greedy batch needs neither targets nor

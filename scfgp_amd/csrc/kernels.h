@@ -388,6 +388,22 @@ template <typename T>
 void loo_blocks(const Geom& g, const T* C, const double* r, const double* y, int block, int64_t blk0, const Scal* sc, double* mu,
                 double* sd, double* lev, double* rec, double* acc, unsigned long long* bad, hipStream_t st);
 
+// ---- gradcov.hip: posterior covariance of the input gradient (scfgp_predict_gradcov) --------------------------------------------------
+// q = min(D, S) directions per point; a chunk of g.N points has gr.N = g.N q derivative rows (gr: the chunk's geometry in those rows).
+// Qt (q x Jp, type T): row i = Q[:, i] of the direction basis (dense D <= S: row i of Fall; latent D > S: [e_i | r_F[:, i]^T])
+template <typename T> void gradcov_operand(const Geom& g, const double* params, const double* Fall, T* Qt, hipStream_t st);
+// Psi (gr.Np x Kp): row t q + i = (-Phi_s[t] o Q[:, i] | Phi_c[t] o Q[:, i]), formed in fp64 and rounded once; padding columns and rows zero
+template <typename T> void gradfeat(const Geom& gr, const Geom& g, const T* Phi, const T* Qt, T* Psi, hipStream_t st);
+void gradcov_ones(double* x, int64_t n, hipStream_t st);
+// C (typed, ld Kp) = Psi Li^T.  Per point t < g.N: Sigma_t = kappa P H_t P^T (H_t = C_t C_t^T; P = l_F read from params, or I), scaled
+// on both sides by gfac[t] (g.N x D; NULL: none).  dvar (g.N x D), dcov (g.N x D x D), rec (g.N x D x D, lower triangle only:
+// wgt[t] (m[t] m[t]^T + Sigma_t); wgt NULL: 1) may each be NULL
+template <typename T>
+void gradcov_blocks(const Geom& gr, const Geom& g, const T* C, const double* params, const Scal* sc, const double* gfac, const double* m,
+                    const double* wgt, double* dvar, double* dcov, double* rec, hipStream_t st);
+// acc (D x D, lower triangle) += rec[0..n) in point order, one lane per entry
+void gradcov_reduce(const double* rec, int64_t n, int D, double* acc, hipStream_t st);
+
 // ---- select.hip: greedy maximum-information choice of m rows from a pool (scfgp_select) ---------------------------------------------
 // C (typed, ld Kp, Trows rows) = Phi_c Li^T of the pool.  Device state of one call: w (Trows: the weights; a picked row's is set to 0),
 // d (Trows: the running |c_i|^2 downdated by every pick), pval / pidx (select_partials(Trows) argmax partials of the last sweep), U

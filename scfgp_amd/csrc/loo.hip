@@ -21,9 +21,9 @@
 // outputs (e = y - mu, sigma^2 = sigma sigma), so a host that recomputes them from mu, std, lev meets the same terms.  For b = 1 the
 // joint density of a block IS the marginal of its row and is copied, not recomputed.  loo_reduce_kernel adds the records in block order.
 #include "kernels.h"
-#include "tile_engine.h"
+#include "block_gram.h"
 
-constexpr int LOO_LD = 65;                      // doubles per row of the LDS image
+constexpr int LOO_LD = BLOCK_GRAM_LD;           // doubles per row of the LDS image
 constexpr int LOO_REC = 5;                      // doubles per block record
 
 template <typename T>
@@ -32,71 +32,13 @@ __global__ __launch_bounds__(256) void loo_block_kernel(const T* __restrict__ C,
                                                         const Scal* __restrict__ sc, double* __restrict__ mu, double* __restrict__ sd,
                                                         double* __restrict__ lev, double* __restrict__ rec,
                                                         unsigned long long* __restrict__ bad) {
-    typedef MT<double, 16> M;
-    typedef typename Vec16<T>::type vec_t;
-    constexpr int VN = Vec16<T>::N;
     __shared__ double Hs[64 * LOO_LD];
     __shared__ double s_r[64], s_t[64], s_a[64], s_b[64], s_c[64], s_h[64], s_l[64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, q = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t g0 = (int64_t)blockIdx.x * gs;                 // first row of the group (chunk-local)
     const int live = (int)(N - g0 < gs ? N - g0 : gs);           // live rows of the group (>= 1)
 
-    for (int x = tid; x < 64 * LOO_LD; x += 256) Hs[x] = 0.0;
-
-    // lower 16 x 16 tiles (tm, tn <= tm) that meet a diagonal block: the first row of tm and the last row of tn lie in one block
-    unsigned need = 0;
-    {
-        int t = 0;
-        for (int tm = 0; tm < 4; ++tm)
-            for (int tn = 0; tn <= tm; ++tn, ++t)
-                if (tn == tm || (16 * tm) / b == (16 * tn + 15) / b) need |= 1u << t;
-    }
-    typename M::acc_t acc[10];
-#pragma unroll
-    for (int t = 0; t < 10; ++t) acc[t] = 0;
-
-    const int nslot = Kp / 4 / VN;                               // 16-byte slots of a wave's quarter of a row (a multiple of 8)
-    const vec_t* src[4]; bool on[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        on[f] = 16 * f + i < live;
-        src[f] = reinterpret_cast<const vec_t*>(C + (g0 + (on[f] ? 16 * f + i : 0)) * Kp) + wave * nslot + q;
-    }
-    for (int s = 0; s < nslot; s += 4) {
-        vec_t v[4];
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            if (on[f]) v[f] = src[f][s];
-            else v[f] = 0;
-        }
-#pragma unroll
-        for (int e = 0; e < VN; ++e) {
-            double a[4];
-#pragma unroll
-            for (int f = 0; f < 4; ++f) a[f] = (double)v[f][e];
-            int t = 0;
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int tn = 0; tn <= tm; ++tn, ++t)
-                    if (need >> t & 1) M::mfma(acc[t], a[tm], a[tn]);
-        }
-    }
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-            int t = 0;
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int tn = 0; tn <= tm; ++tn, ++t)
-                    if (need >> t & 1) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) Hs[(16 * tm + M::crow(lane, r)) * LOO_LD + 16 * tn + i] += acc[t][r];
-                    }
-        }
-        __syncthreads();
-    }
+    block_gram<T>(C, Kp, g0, live, b, Hs);
     if (wave != 0) return;
 
     // ---- the tail: lane = row of the group; no workgroup barrier from here on (one wave: fences order its LDS traffic) ----------

@@ -57,6 +57,7 @@ static constexpr int64_t PRED_ROWS = 32768; // predict processes test rows in ch
 #define SCFGP_ERR_PER_COND 3.0e-7
 #endif
 static void derive_geom(Geom& g, int D, int S, int M);
+static Geom chunk_geom(const Geom& g0, int64_t rows);
 
 thread_local bool g_scfgp_capturing = false;
 
@@ -804,6 +805,34 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_predict_gradcov (gradcov.hip).  Qt: the typed direction basis, once per call
+    static void gradcov_basis(scfgp_ctx* c, void* Qt) { gradcov_operand<T>(c->g, c->d_params, c->d_Fall, (T*)Qt, c->st); }
+    // a chunk of g.N points: dmu by predict_grad's own kernel (mean only) and chain rule, so that it has scfgp_predict_grad's bits; then
+    // the g.N q derivative rows Psi into p_V, C' = Psi Li^T into p_C (its by-products land in the chunk's partials and are ignored), the
+    // block kernel and, rec != NULL, the ordered sum of its records.  x: the chunk's raw rows (xmode != 0: gfac <- the scaler's factors)
+    static int gradcov_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const void* Qt, const double* x, int xmode, double* gfac,
+                             const double* wgt, double* dmu, double* dvar, double* dcov, double* rec, double* acc) {
+        const int q = std::min(g.D, g.S);
+        features(c, g);
+        { ProfScope ps(c, "gradcov_dmu");
+          predgrad<T>(g, (const T*)c->p_Phi, (const T*)c->p_V, c->alpha_pred(), (const T*)c->p_FT, nullptr, c->d_sc, dmu, nullptr, c->st);
+          if (xmode) {
+              gradcov_ones(gfac, g.N * g.D, c->st);
+              xgrad_chunk(x, g.N, g.D, xmode, c->d_xscale, dmu, gfac, c->st);
+          } }
+        if (dvar || dcov || rec) {
+            const Geom gr = chunk_geom(g, g.N * q);
+            { ProfScope ps(c, "gradfeat"); gradfeat<T>(gr, g, (const T*)c->p_Phi, (const T*)Qt, (T*)c->p_V, c->st); }
+            { ProfScope ps(c, "gradcov_apply_c");
+              SK::apply_c(gr, (const T*)c->p_V, (const T*)LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(),
+                          c->p_mupart, c->st, 0); }
+            { ProfScope ps(c, "gradcov_block");
+              gradcov_blocks<T>(gr, g, (const T*)c->p_C, c->d_params, c->d_sc, xmode ? gfac : nullptr, dmu, wgt, dvar, dcov, rec, c->st); }
+            if (rec) { ProfScope ps(c, "gradcov_reduce"); gradcov_reduce(rec, g.N, g.D, acc, c->st); }
+        }
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
     // scfgp_sample: the weights of the sample functions (sample.hip), then per chunk out (N x nsamp) = Phi* W and the epilogue
     static void weights(scfgp_ctx* c, const double* Li, const double* alpha, int nsamp, uint64_t seed, double* Z, double* W, void* Wt) {
         sample_weights<T>(c->g, Li, alpha, c->d_sc, nsamp, seed, Z, W, (T*)Wt, c->st);
@@ -1249,7 +1278,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
+// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -2372,6 +2401,111 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
         stats[0] = (double)n; stats[1] = acc[0]; stats[2] = acc[1]; stats[3] = acc[2]; stats[4] = acc[3]; stats[5] = acc[4];
         stats[6] = (double)((n + block - 1) / block); stats[7] = 0.0;
     }
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// posterior covariance of the input gradient (gradcov.hip; derivation and promises in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int GRADCOV_MAX_Q = 64;                          // a point's q rows lie in one 64-row group of the block kernel
+static constexpr int64_t GRADCOV_SLOT_BYTES = (int64_t)64 << 20;  // per-point D x D arrays of a chunk (a dcov slot, the records)
+// points per chunk (the formula of the header): whole groups of (64 / q) points in the 32 768-row chunk buffers and, where a chunk
+// carries a D x D array per point, no more points than the slot budget holds
+static int64_t gradcov_points(const Geom& g, bool want_cov) {
+    const int q = std::min(g.D, g.S), ppg = 64 / q;
+    int64_t np = PRED_ROWS / (ppg * q) * ppg;
+    if (want_cov) np = std::min(np, std::max<int64_t>(1, GRADCOV_SLOT_BYTES / (8 * (int64_t)g.D * g.D)));
+    return np;
+}
+// The chunk pipeline (RowFeed, OutRing) with the weights behind the rows of their chunk.  dmu | dvar | dcov of a chunk leave through the
+// two slots of `stage`; the records and the running D x D sums stay on the device, the sums are fetched once, at the end.
+extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
+                                     int mode, double* dmu, double* dvar, double* dcov, double* asub) {
+    if (!c) return SCFGP_EARG;
+    if (!Xs || !alpha || !Li || T < 1 || mode < 0 || mode > 1) { c->err = "predict_gradcov: bad arguments"; return SCFGP_EARG; }
+    if (!dmu && !dvar && !dcov && !asub) { c->err = "predict_gradcov: no output requested"; return SCFGP_EARG; }
+    if (mode == 1 && !c->d_xscale) { c->err = "predict_gradcov: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "predict_gradcov: parameters not set"; return SCFGP_EARG; }
+    const Geom& g0 = c->g;
+    const int D = g0.D, q = std::min(g0.D, g0.S);
+    if (q > GRADCOV_MAX_Q) { c->err = "predict_gradcov: min(D, S) must be at most 64"; return SCFGP_EARG; }
+    double sw = (double)T;
+    if (asub && w) {
+        sw = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+            if (!(w[t] >= 0.0) || !std::isfinite(w[t])) {
+                c->err = "predict_gradcov: weight " + std::to_string(t) + " is negative or not finite"; return SCFGP_EARG;
+            }
+            sw += w[t];
+        }
+        if (!(sw > 0.0)) { c->err = "predict_gradcov: the weights sum to zero"; return SCFGP_EARG; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/predict_gradcov_time.py)
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_grad(c, false))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    const bool feed_w = asub && w;
+    const int xmode = mode == 1 ? c->xs_mode : 0;
+    const int64_t DD = (int64_t)D * D;
+    const int64_t CH = gradcov_points(g0, dcov || asub), nchunks = (T + CH - 1) / CH, rows = std::min(T, CH);
+    const int64_t slot_len = rows * D * 2 + (dcov ? rows * DD : 0);
+    RowFeed feed; OutRing ring; DevTmp qt, gfac, stage, rec, acc;  // Li / two chunks of [Xs | w] | Q | g_t | two slots | records | sums
+    if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
+    if ((rc = dmalloc(c, &qt.p, c->tsize() * q * g0.Jp))) return rc;
+    if (xmode && (rc = dmalloc(c, &gfac.p, sizeof(double) * rows * D))) return rc;
+    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
+    if (asub && ((rc = dmalloc(c, &rec.p, sizeof(double) * rows * DD)) || (rc = dmalloc(c, &acc.p, sizeof(double) * DD)))) return rc;
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    DISPATCH(c, grad_operand, c);
+    DISPATCH(c, gradcov_basis, c, qt.p);
+    if (asub) HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * DD, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    if ((rc = ring.open(c))) return rc;
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(CH, T - i * CH); };
+    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * CH * D, feed_w ? w + i * CH : nullptr, rows_of(i)); };
+    auto slot_dmu = [&](int64_t i) { return stage + (i & 1) * slot_len; };
+    auto slot_dvar = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * D; };
+    auto slot_dcov = [&](int64_t i) { return stage + (i & 1) * slot_len + 2 * rows * D; };
+    auto download = [&](int64_t i) {
+        return ring.drain(i, [&]() -> int {
+            const int64_t t0 = i * CH, n = rows_of(i);
+            if (dmu) HIPCHK(c, hipMemcpyAsync(dmu + t0 * D, slot_dmu(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
+            if (dvar) HIPCHK(c, hipMemcpyAsync(dvar + t0 * D, slot_dvar(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
+            if (dcov) HIPCHK(c, hipMemcpyAsync(dcov + t0 * DD, slot_dcov(i), sizeof(double) * n * DD, hipMemcpyDeviceToHost, c->copy_st));
+            return SCFGP_OK;
+        });
+    };
+    if ((rc = upload(0))) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        const Geom g = chunk_geom(g0, rows_of(i));
+        const double *x, *wi;
+        if ((rc = feed.acquire(i, &x, &wi))) return rc;
+        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
+        if ((rc = ring.acquire(i))) return rc;
+        // the raw rows and the weights stay in the feed's half until the block kernel has read them
+        if ((rc = DISPATCH(c, gradcov_chunk, c, g, LiT, qt.p, x, xmode, gfac.p, feed_w ? wi : nullptr, slot_dmu(i), dvar ? slot_dvar(i) : nullptr,
+                           dcov ? slot_dcov(i) : nullptr, rec.p, acc.p)))
+            return rc;
+        if ((rc = feed.release(i))) return rc;
+        if ((rc = ring.computed(i))) return rc;
+        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i >= 1 && (rc = download(i - 1))) return rc;
+    }
+    if ((rc = download(nchunks - 1))) return rc;
+    std::vector<double> sums;
+    if (asub) {
+        sums.resize(DD);
+        HIPCHK(c, hipMemcpyAsync(sums.data(), acc.p, sizeof(double) * DD, hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->copy_st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    HIPCHK(c, hipGetLastError());
+    if (asub)                                                     // one division per entry of the lower triangle, mirrored
+        for (int d = 0; d < D; ++d)
+            for (int e = 0; e <= d; ++e) asub[(int64_t)d * D + e] = asub[(int64_t)e * D + d] = sums[(int64_t)d * D + e] / sw;
     return SCFGP_OK;
 }
 

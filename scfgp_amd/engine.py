@@ -275,6 +275,65 @@ class HipEngine(object):
             dmu, dsd = _scatter(dmu, cols, D_in), (None if dsd is None else _scatter(dsd, cols, D_in))
         return mu, sd, dmu, dsd
 
+    GRADCOV_MODES = {'scaled': 0, 'raw': 1}
+    GRADCOV_OUTPUTS = ('dmu', 'dvar', 'dcov', 'asub')
+
+    def gradcov_points_per_chunk(self, want_cov):
+        """Points per chunk of predict_gradcov (the formula of include/scfgp_hip.h).  want_cov: the call asks for 'dcov' or 'asub', so
+        a chunk carries a D x D array per point and stays within the 64 MiB slot budget."""
+        q = min(self.D, self.S)
+        ppg = 64 // q
+        n = 32768 // (ppg * q) * ppg
+        if want_cov:
+            n = min(n, max(1, (64 << 20) // (8 * self.D * self.D)))
+        return n
+
+    def predict_gradcov(self, Xs, alpha, Li, w=None, mode='scaled', want=('dmu', 'dvar', 'asub')):
+        """Posterior distribution of the input gradient (include/scfgp_hip.h: scfgp_predict_gradcov): a dict with the outputs named in
+        `want` -- 'dmu' (T, D) the mean (predict_grad's dmu, bit for bit), 'dvar' (T, D) the marginal variances, 'dcov' (T, D, D) the
+        covariance of grad f at every row, 'asub' (D, D) the active-subspace matrix sum_t w_t (m_t m_t^T + Sigma_t) / sum_t w_t of the
+        call's rows (w: T weights >= 0, None: all 1).  mode 'scaled': Xs as predict takes it; 'raw': unscaled Xs through the registered
+        X scaler, outputs in the D_raw raw columns with zeros for the columns the scaler dropped, as predict_grad.  Needs min(D, S) <=
+        64."""
+        if mode not in self.GRADCOV_MODES:
+            raise ValueError('predict_gradcov: mode must be one of %s' % sorted(self.GRADCOV_MODES))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.GRADCOV_OUTPUTS for k in want):
+            raise ValueError('predict_gradcov: want must name some of %s' % (self.GRADCOV_OUTPUTS,))
+        m = self.GRADCOV_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('predict_gradcov: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        D_in = Xs.shape[1]
+        if cols is not None:
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        alpha, Li = self._factors(alpha, Li)
+        T, D = Xs.shape[0], self.D
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        shapes = {'dmu': (T, D), 'dvar': (T, D), 'dcov': (T, D, D), 'asub': (D, D)}
+        out = {k: np.empty(shapes[k]) for k in self.GRADCOV_OUTPUTS if k in want}
+        self._check(self.lib.scfgp_predict_gradcov(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), m,
+                                                   *[dptr(out.get(k)) for k in self.GRADCOV_OUTPUTS]), 'predict_gradcov')
+        if cols is not None:
+            for k in out:
+                a = np.zeros(out[k].shape[:-1] + (D_in,))
+                a[..., cols] = out[k]
+                if k in ('dcov', 'asub'):                      # rows of the matrices too
+                    b = np.zeros(a.shape[:-2] + (D_in, D_in))
+                    b[..., cols, :] = a
+                    a = b
+                out[k] = a
+        return out
+
     SAMPLE_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
 
     def _factors(self, alpha, Li):

@@ -328,6 +328,13 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, y_scaler if y_units else None)
         return self.engine.sample_grad(Xs_raw, W, sidx=sidx, mode='y' if y_units else 'raw', want_val=want_val)
 
+    def pred_gradcov_raw(self, Xs_raw, x_scaler, alpha, Li, w=None, want=('dmu', 'dvar', 'asub')):
+        """Posterior mean, variance / covariance of the input gradient at the raw rows Xs_raw and their active-subspace matrix, in raw
+        X units and scaled y units (engine.predict_gradcov with mode 'raw'): a dict of the outputs named in `want`."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.predict_gradcov(Xs_raw, alpha, Li, w=w, mode='raw', want=want)
+
     def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
         """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
         self._sync_params()

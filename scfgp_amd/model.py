@@ -267,6 +267,31 @@ class SCFGP(object):
         mu_y, std_y, dmu_y, dstd_y = owner.pred_grad_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li)
         return mu_y, std_y[:, None], dmu_y, dstd_y
 
+    def predict_gradcov(self, Xs, full=False):
+        """Posterior distribution of the gradient of the latent function at the raw rows Xs, in raw X units and the SCALED target's
+        units: (mean (T,D), std (T,D)) and, with full=True, also cov (T,D,D) -- grad f(x_t) ~ N(mean[t], cov[t]), std its marginal
+        standard deviations; D the raw column count (zeros where the X scaler dropped a constant column).  There are no raw-y units:
+        through a non-affine y scaler the gradient is not Gaussian, the argument of predict_cov (include/scfgp_hip.h:
+        scfgp_predict_gradcov)."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('predict_gradcov needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        out = owner.pred_gradcov_raw(Xs, self.X_scaler, self.alpha, self.Li, want=('dmu', 'dvar') + (('dcov',) if full else ()))
+        res = (out['dmu'], np.sqrt(out['dvar']))
+        return res + (out['dcov'],) if full else res
+
+    def active_subspace(self, Xs, w=None):
+        """Active subspace of the fitted function over the raw rows Xs (weights w >= 0, None: all 1): (eigenvalues descending (D,),
+        eigenvectors (D,D) in columns, asub (D,D)) of asub = E[grad f grad f^T] averaged over the rows -- the posterior mean of the
+        gradient's outer product, sum_t w_t (m_t m_t^T + Sigma_t) / sum_t w_t, formed on the device without a (T,D,D) array; the
+        eigendecomposition of the D x D matrix runs on the host.  Raw X units, scaled target units."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('active_subspace needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        asub = owner.pred_gradcov_raw(Xs, self.X_scaler, self.alpha, self.Li, w=w, want=('asub',))['asub']
+        lam, vec = np.linalg.eigh(asub)
+        return lam[::-1].copy(), vec[:, ::-1].copy(), asub
+
     def sample(self, Xs, nsamples, seed=0, noise=False):
         """nsamples posterior sample functions of the fitted model at the raw rows Xs, in raw y units: (T, nsamples).  Column s is
         phi(x)^T w_s with w_s ~ N(alpha, kappa A^-1) (plus observation noise with noise=True), mapped through the y scaler's backward

@@ -73,5 +73,19 @@ if ctx:
                  (xp, 1, None, None, 0, xp, xp, z3, 3, 0, 1, 0, xp, xp, ip, xp, None, None)]:            # parameters not set
         assert lib.scfgp_acquire_kg(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'acquire_kg')
         n += 1
+# scfgp_predict_gradcov: the same (the weights are checked on the host before the first device call too, but behind the parameters)
+assert lib.scfgp_predict_gradcov(None, xp, 1, None, xp, xp, 0, xp, xp, xp, xp) == -1
+n += 1
+if ctx:
+    for args in [(None, 1, None, xp, xp, 0, xp, xp, xp, xp),                                             # NULL Xs
+                 (xp, 1, None, None, xp, 0, xp, xp, xp, xp),                                             # NULL alpha
+                 (xp, 1, None, xp, None, 0, xp, xp, xp, xp),                                             # NULL Li
+                 (xp, 0, None, xp, xp, 0, xp, xp, xp, xp),                                               # T < 1
+                 (xp, 1, None, xp, xp, 2, xp, xp, xp, xp),                                               # mode
+                 (xp, 1, xp, xp, xp, 0, None, None, None, None),                                         # no output
+                 (xp, 1, None, xp, xp, 1, xp, xp, xp, xp),                                               # no X scaler
+                 (xp, 1, None, xp, xp, 0, xp, None, None, xp)]:                                          # parameters not set
+        assert lib.scfgp_predict_gradcov(ctx, *args) == -1 and lib.scfgp_last_error(ctx).startswith(b'predict_gradcov')
+        n += 1
 if ctx: lib.scfgp_destroy(ctx)
 print('host-side calls under ASan/UBSan:', n + 4, 'ok')

@@ -8,7 +8,8 @@ reused) and at (20, 20, 280) with 5000 rows: predict, predict_raw, predict_y wit
 modes with and without the std gradient; sample_weights; sample in its three modes with and without noise, 3 samples; predict_cov
 symmetric at 2500 rows, cross at all rows x 50 and at 2500 x 9000 (two panels per chunk); condition in both modes; loo with blocks
 1, 7, 64 from host rows and block 7 on resident rows; select without weights and with weights around the chunk boundaries, with
-std_after.  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
+std_after; predict_gradcov with all four outputs and weights over three chunks, in raw mode, and with its default outputs over all rows
+(where the build has it: outputs that only one build produces are listed as new, not as different).  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
 Usage: python tools/posterior_ab.py [--variants _head,] [--limit SECONDS]        (default limit: 300 per child)
        python tools/posterior_ab.py --child OUT.json                             (the list, in this process, on SCFGP_LIB_VARIANT)"""
 import hashlib
@@ -79,6 +80,15 @@ def calls(D, S, M, n, dt):
     if not w.any():
         w[n // 2 - 25:n // 2 + 25] = 1.0
     yield 'select weights raw', eng.select(Xr, Li, 8, w=w, raw=True, return_std=True)
+    if hasattr(eng.lib, 'scfgp_predict_gradcov'):                # a build of an older commit lacks it: its outputs are listed as new
+        allout = ('dmu', 'dvar', 'dcov', 'asub')
+        n3 = min(n, 2 * eng.gradcov_points_per_chunk(True) + 3)   # three chunks where the call has the rows for them
+        out = eng.predict_gradcov(X[:n3], alpha, Li, w=w[:n3] + 0.5, want=allout)
+        yield 'predict_gradcov scaled %d rows' % n3, tuple(out[k] for k in allout)
+        out = eng.predict_gradcov(Xr[:2500], alpha, Li, mode='raw', want=allout)
+        yield 'predict_gradcov raw 2500 rows', tuple(out[k] for k in allout)
+        out = eng.predict_gradcov(X, alpha, Li)
+        yield 'predict_gradcov scaled %d rows, default outputs' % n, tuple(out[k] for k in ('dmu', 'dvar', 'asub'))
     eng.close()
 
 
@@ -113,11 +123,14 @@ def main(argv):
     a, b = got
     bad = 0
     print('%-78s %-14s %-14s' % ('dtype shape | call | output', repr(variants[0]), repr(variants[1])))
+    new = 0
     for key in sorted(set(a) | set(b)):
+        only = key not in a or key not in b                     # an entry point that one of the builds lacks: nothing to compare
         same = a.get(key) == b.get(key)
-        bad += not same
-        print('%-78s %-14s %-14s %s' % (key, a.get(key, '-')[:12], b.get(key, '-')[:12], 'same' if same else 'DIFFERENT'))
-    print('%d outputs, %d different' % (len(set(a) | set(b)), bad), flush=True)
+        bad += not same and not only
+        new += only
+        print('%-78s %-14s %-14s %s' % (key, a.get(key, '-')[:12], b.get(key, '-')[:12], 'new' if only else 'same' if same else 'DIFFERENT'))
+    print('%d outputs, %d different, %d in one build only' % (len(set(a) | set(b)), bad, new), flush=True)
     return 1 if bad else 0
 
 
