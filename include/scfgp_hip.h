@@ -473,6 +473,56 @@ int scfgp_loo(scfgp_ctx* ctx, const double* X, const double* y, int64_t n, const
 int scfgp_predict_gradcov(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int mode,
                           double* dmu, double* dvar, double* dcov, double* asub);
 
+/* ---- partial dependence and ICE curves of single inputs over a pool (no reference counterpart) ------------------------------------------
+ * Which inputs matter, and how?  Pool rows x_t (t < T), weights w_t >= 0 (w == NULL: all 1), W = sum w_t, a dimension d and grid values
+ * g_0 .. g_{G-1} of that dimension; x_t^{d->g} is row t with coordinate d replaced by g.
+ *     ice[t][i] = mu*(x_t^{d->g_i})                       the individual conditional expectation (ICE) curves
+ *     pd[i]     = sum_t (w_t / W) f(x_t^{d->g_i})         the partial-dependence (PD) curve, a linear functional of f: exactly Gaussian
+ * A phase is linear in x: z_j = sum_e x_e F_all[e][j] + b_j.  With the zeroed-column features phi0_t = phi(x_t^{d->0}) (phase z_tj -
+ * x_td F_all[d][j]), c_ij = cos(g_i F_all[d][j]) and s_ij = sin(g_i F_all[d][j]), the features of x_t^{d->g_i} are phi0_t rotated pair by pair:
+ *     phi_c = phi0_c c_ij - phi0_s s_ij        phi_s = phi0_s c_ij + phi0_c s_ij
+ * so with alpha = (J cosine weights | J sine weights)
+ *     ice[t][i] = sum_k Phi0[t][k] R[k][i],   R[j][i] = alpha_j c_ij + alpha_{J+j} s_ij,   R[J+j][i] = alpha_{J+j} c_ij - alpha_j s_ij
+ *     Phibar[i] = the same rotation of the mean row phibar0 = sum_t (w_t / W) phi0_t  (K numbers per dimension, whatever T is)
+ *     pd[i] = Phibar[i] . alpha      pd_cov[i][i'] = kappa Phibar[i]^T A^-1 Phibar[i'] = kappa (Cbar Cbar^T)[i][i'],  Cbar = Phibar Li^T
+ *     pd_sd[i] = sqrt(kappa |Cbar[i]|^2)
+ * pd_sd and pd_cov describe the latent function: a PD curve is not an observation, so there is no noise term.
+ * dims: ndim distinct dimensions in [0, D); grid (ndim x G): row a holds the grid values of dimension dims[a].  Outputs, each may be NULL,
+ * at least one must be given: pd (ndim x G), pd_sd (ndim x G), pd_cov (ndim x G x G), ice (ndim x T x G).  All values are in scaled y
+ * units.  mode 0: scaled rows and scaled grid values.  mode 1: column-selected raw rows through the registered X scaler, as
+ * scfgp_predict_raw; the grid is given in raw units of its column and goes through the same per-column forward transform on the device.
+ * There is no raw-y mode: the y scaler's backward transform is not affine, so a PD curve in raw y units is not Gaussian (the argument of
+ * scfgp_predict_cov and scfgp_acquire).
+ * Bounds: 1 <= G <= 1024 (the ICE block is the product of scfgp_sample), 1 <= ndim <= D, T >= 1 without limit.
+ * Rows with w_t == 0 contribute nothing to the sums: their term is selected away, not multiplied by zero, so a non-finite row of weight 0
+ * is not an error.  They still get their ice rows.
+ * How it runs.  The rows go through in chunks of 32768, at most twice: once for the sums (pd, pd_sd or pd_cov wanted), once for ice.  The
+ * sums kernel forms Z = X~ F_all by fp64 MFMA as the feature map does and, in place of its store, sums w_t phi0_t over each 128-row block
+ * for every dimension; Phi0 is never written.  A launch covers as many dimensions as keep its block records within 64 MiB.  ice stages two
+ * T_chunk x G blocks, pd_cov two G x G blocks; device memory beside the chunk buffers does not grow with T.
+ * Promises:
+ *  1. The same call gives the same bits on every run: no atomics.  Within a 128-row block (aligned to the call-wide row index; 128 divides
+ *     the chunk) the sum runs over a fixed tree: a lane's 8 rows, the 4 lanes of a column, the 4 waves of a column.  The block records are
+ *     then added in row order into running fp64 sums that stay on the device across chunks.
+ *  2. pd, pd_sd and pd_cov of a dimension do not depend on which other dimensions are in dims, nor on their order.
+ *  3. pd[a][i], pd_sd[a][i] and ice[a][t][i] depend on g_i alone among the grid values: a shorter or permuted grid gives the matching
+ *     entries.  An entry of pd_cov depends on its two grid values alone.
+ *  4. pd_cov[a] is symmetric bit for bit (scfgp_predict_cov's promise: the same kernel with both operands equal).
+ *  5. ice[a][t][:] depends on row t, the dimension, the grid, the factors and the parameters only: not on T, the row's position, the chunk
+ *     or w.
+ *  6. Appending rows with w = 0 changes no bit of pd, pd_sd or pd_cov.
+ *  7. Every combination of requested outputs gives the same bits for the outputs it shares with another: pd never takes a shortcut
+ *     through ice.
+ *  8. SCFGP_F16X3 contexts run fp32 mode's kernels and agree with an SCFGP_F32 context bit for bit.
+ * The training state of the context survives the call.
+ * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL Xs, alpha, Li, dims or grid, all four outputs NULL, T, G or
+ * ndim out of range, a dimension out of range or given twice, a bad mode, a missing X scaler in mode 1, parameters not set, a negative w,
+ * or no row with w > 0.  SCFGP_ENONFINITE for a non-finite w, a non-finite grid value (after the transform in mode 1) or a non-finite
+ * weighted sum.  The outputs are untouched in both cases and the context stays usable. */
+int scfgp_predict_pd(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
+                     const int* dims, int ndim, const double* grid, int G, int mode,
+                     double* pd, double* pd_sd, double* pd_cov, double* ice);
+
 /* ---- greedy maximum-information choice of m rows from a pool (no reference counterpart) ----------------------------------------------
  * Which rows should be observed next?  The posterior of a Fourier-feature model is a Bayesian linear model in K weights, and the
  * posterior variance after an observation does not depend on the observed value, so the exact greedy batch needs neither targets nor

@@ -58,6 +58,8 @@ SIGNATURES = {
                             _c_double_p, _c_double_p]),
     'scfgp_predict_gradcov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.c_int, _c_double_p,
                                         _c_double_p, _c_double_p, _c_double_p]),
+    'scfgp_predict_pd': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int,
+                                   _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_select': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_int, _c_i64_p, _c_double_p,
                                _c_double_p, _c_double_p]),
     'scfgp_select_iv': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int,

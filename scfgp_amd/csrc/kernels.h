@@ -404,6 +404,30 @@ void gradcov_blocks(const Geom& gr, const Geom& g, const T* C, const double* par
 // acc (D x D, lower triangle) += rec[0..n) in point order, one lane per entry
 void gradcov_reduce(const double* rec, int64_t n, int D, double* acc, hipStream_t st);
 
+// ---- pd.hip: partial dependence and ICE curves over a pool (scfgp_predict_pd) ----------------------------------------------------------
+// rows that a dimension's G grid points take in the stacked operand Phibar: a multiple of 128, so that predcov finds its padded rows
+inline int pd_grid_rows(int G) { return (int)round_up(G, 128); }
+// doubles of the block records of one chunk with ng dimensions: one record of 2 Jp doubles per (128-row block, dimension)
+int64_t pd_record_len(const Geom& g, int ng);
+// acc (ng x 2 x Jp, fp64) += the sums over the chunk's live rows n (n < g.N, wgt[n] > 0; wgt: g.Np weights with zeros on the padding, or NULL
+// for all 1) of wgt[n] phi0_n for the dimensions dims[0..ng): phi0 = the features at row n with coordinate d cleared, cosine half then sine
+// half.  rec: pd_record_len(g, ng) doubles of scratch; the block records are added in block order.
+template <typename T>
+void pd_sums(const Geom& g, const double* Xt, const double* Fall, const Scal* sc, const double* wgt, const int* dims, int ng, double* rec,
+             double* acc, hipStream_t st);
+// grid (ndim x G) <- the X scaler's forward transform (mode, sp: as pack_data) of row a in column dims[a], in place
+void pd_grid(double* grid, const int* dims, int ndim, int G, int D, int mode, const double* sp, hipStream_t st);
+// Phibar (gr.Np x Kp, type T): row a pd_grid_rows(G) + i = (acc[a] / W) rotated by grid[a][i] Fall[dims[a]][.], a < ng, i < G; all other
+// rows and the padding columns zero
+template <typename T>
+void pd_mean_rows(const Geom& gr, const Geom& g, const double* acc, double W, const double* Fall, const int* dims, const double* grid, int ng,
+                  int G, T* Phibar, hipStream_t st);
+// R (sample_w_rows(K) x sample_w_cols(G), type T, zero outside K x G): alpha rotated by grid_d[i] Fall[d][.], so that Phi0 R = the ICE block
+template <typename T>
+void pd_ice_weights(const Geom& g, const double* alpha, const double* Fall, int d, const double* grid_d, int G, T* R, hipStream_t st);
+// save != 0: keep (g.Np) <- column d of Xt, which is cleared; save == 0: the column is put back
+void pd_column(const Geom& g, double* Xt, int d, int save, double* keep, hipStream_t st);
+
 // ---- select.hip: greedy maximum-information choice of m rows from a pool (scfgp_select) ---------------------------------------------
 // C (typed, ld Kp, Trows rows) = Phi_c Li^T of the pool.  Device state of one call: w (Trows: the weights; a picked row's is set to 0),
 // d (Trows: the running |c_i|^2 downdated by every pick), pval / pidx (select_partials(Trows) argmax partials of the last sweep), U

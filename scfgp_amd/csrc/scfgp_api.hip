@@ -128,7 +128,7 @@ struct scfgp_ctx {
     // Ranks decide together (common.h: XS_*).  `unsettled`: a precision level was raised (or refused) since the last sum over
     // ranks, so the next exchange 1 carries every rank's attainable level and scfgp_factor commits to the lowest before pass 2
     // runs; cap(): the highest level this rank can run at.  test_*: fault injection for the tests (scfgp_set_option).
-    bool unsettled = false; int test_deny_level = 0, test_fail_stage = 0;
+    bool unsettled = false; int test_deny_level = 0, test_fail_stage = 0, test_pd_group = 0;
     int cap() const { return esc_denied > 0 ? esc_denied - 1 : 2; }
     double* x3_xu() { return d_x3 + (int64_t)Dpp * g.Jp + 8; }
     hipEvent_t ev_fence = nullptr;                                          // scfgp_stream_fence
@@ -833,6 +833,44 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
+    // scfgp_predict_pd (pd.hip).  The sums of a chunk's packed rows for ng dimensions, added into the call's running sums
+    static int pd_sums_chunk(scfgp_ctx* c, const Geom& g, const double* wgt, const int* dims, int ng, double* rec, double* acc) {
+        ProfScope ps(c, "pd_sums");
+        pd_sums<T>(g, c->p_Xt, c->d_Fall, c->d_sc, wgt, dims, ng, rec, acc, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // the curves of ng dimensions: their stacked mean rows Phibar into p_Phi (gr: the geometry in those rows), Cbar = Phibar Li^T into p_C;
+    // pd = the sum of mupart in rowpredict's order, sd = sqrt(kappa sum vpart) by kg_sigma's arithmetic.  pd, scratch, sd: gr.Np each
+    static int pd_curves(scfgp_ctx* c, const Geom& gr, const void* LiT, const double* acc, double W, const int* dims, const double* grid, int ng,
+                         int G, double* pd, double* scratch, double* sd) {
+        ProfScope ps(c, "pd_curves");
+        pd_mean_rows<T>(gr, c->g, acc, W, c->d_Fall, dims, grid, ng, G, (T*)c->p_Phi, c->st);
+        SK::apply_c(gr, (const T*)c->p_Phi, (const T*)LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(),
+                    c->p_mupart, c->st, 0);
+        SK::rowpredict(gr, c->p_mupart, c->p_vpart, c->d_sc, pd, scratch, c->st);
+        kg_sigma(gr, ApplyKernels<T>::partials(gr), c->p_vpart, c->d_sc, 0, sd, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // the covariance of dimension number a of the last pd_curves: predcov on its own rows of p_C twice, so the result is symmetric bit for bit
+    static int pd_cov_dim(scfgp_ctx* c, int a, int G, double* out) {
+        const T* Ca = (const T*)c->p_C + (int64_t)a * pd_grid_rows(G) * c->g.Kp;
+        predcov<T>(c->g, Ca, Ca, G, G, 0, 0, c->d_sc, out, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // the ICE block of dimension d over the chunk's packed rows: column d of p_Xt is cleared for the feature map and put back
+    static int pd_ice_chunk(scfgp_ctx* c, const Geom& g, int d, const double* grid_d, int G, void* R, double* keep, double* out) {
+        pd_column(g, c->p_Xt, d, 1, keep, c->st);
+        { ProfScope ps(c, "pd_ice_featuremap"); features(c, g); }
+        { ProfScope ps(c, "pd_ice_product");
+          pd_ice_weights<T>(c->g, c->alpha_pred(), c->d_Fall, d, grid_d, G, (T*)R, c->st);
+          sample_product<T>(g, (const T*)c->p_Phi, (const T*)R, G, 0, 0, 0, -1, c->d_yscale, c->d_sc, out, c->st); }
+        pd_column(g, c->p_Xt, d, 0, keep, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
     // scfgp_sample: the weights of the sample functions (sample.hip), then per chunk out (N x nsamp) = Phi* W and the epilogue
     static void weights(scfgp_ctx* c, const double* Li, const double* alpha, int nsamp, uint64_t seed, double* Z, double* W, void* Wt) {
         sample_weights<T>(c->g, Li, alpha, c->d_sc, nsamp, seed, Z, W, (T*)Wt, c->st);
@@ -1278,7 +1316,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
+// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_predict_pd, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -2510,6 +2548,203 @@ extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, 
 }
 
 // ----------------------------------------------------------------------------------------------
+// partial dependence and ICE curves over a pool (pd.hip; derivation and promises in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int PD_MAX_G = SAMPLE_MAX;                       // the ICE block is sample_product's shape
+static constexpr int64_t PD_RECORD_BYTES = GRADCOV_SLOT_BYTES;    // block records of one launch of the sums kernel
+// Two passes of the chunk pipeline.  The first (pd, pd_sd or pd_cov wanted) feeds [Xs | w] and leaves the running sums of the zeroed-column
+// features on the device, the dimensions in groups whose block records fit PD_RECORD_BYTES; the sums are checked, then the curves come
+// from the stacked mean rows in groups of dimensions that fit the chunk buffers.  The second (ice wanted) feeds Xs again and sends one
+// T_chunk x G block per (chunk, dimension) through the two slots of an OutRing.  No output is written before the last refusal is past.
+extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
+                                const int* dims, int ndim, const double* grid, int G, int mode, double* pd, double* pd_sd, double* pd_cov,
+                                double* ice) {
+    if (!c) return SCFGP_EARG;
+    if (!Xs || !alpha || !Li || !dims || !grid) { c->err = "predict_pd: bad arguments"; return SCFGP_EARG; }
+    if (!pd && !pd_sd && !pd_cov && !ice) { c->err = "predict_pd: no output requested"; return SCFGP_EARG; }
+    const Geom& g0 = c->g;
+    const int D = g0.D;
+    if (T < 1) { c->err = "predict_pd: T must be at least 1"; return SCFGP_EARG; }
+    if (G < 1 || G > PD_MAX_G) { c->err = "predict_pd: G must lie in 1..1024"; return SCFGP_EARG; }
+    if (ndim < 1 || ndim > D) { c->err = "predict_pd: ndim must lie in 1..D"; return SCFGP_EARG; }
+    if (mode < 0 || mode > 1) { c->err = "predict_pd: bad mode"; return SCFGP_EARG; }
+    {
+        std::vector<char> seen(D, 0);
+        for (int a = 0; a < ndim; ++a) {
+            if (dims[a] < 0 || dims[a] >= D) { c->err = "predict_pd: dimension " + std::to_string(dims[a]) + " is out of range"; return SCFGP_EARG; }
+            if (seen[dims[a]]) { c->err = "predict_pd: dimension " + std::to_string(dims[a]) + " is given twice"; return SCFGP_EARG; }
+            seen[dims[a]] = 1;
+        }
+    }
+    if (mode == 1 && !c->d_xscale) { c->err = "predict_pd: no X scaler set"; return SCFGP_EARG; }
+    if (!c->have_params) { c->err = "predict_pd: parameters not set"; return SCFGP_EARG; }
+    double W = (double)T;
+    if (w) {
+        bool nonfinite = false, positive = false;
+        W = 0.0;
+        for (int64_t t = 0; t < T; ++t) {
+            if (w[t] < 0.0) { c->err = "predict_pd: negative weight at row " + std::to_string(t); return SCFGP_EARG; }
+            if (!std::isfinite(w[t])) nonfinite = true;
+            else if (w[t] > 0.0) positive = true;
+            W += w[t];
+        }
+        if (nonfinite || !std::isfinite(W)) { c->err = "predict_pd: non-finite weights"; return SCFGP_ENONFINITE; }
+        if (!positive) { c->err = "predict_pd: no row has a positive weight"; return SCFGP_EARG; }
+    }
+    const int xmode = mode == 1 ? c->xs_mode : 0;
+    const int64_t NG = (int64_t)ndim * G;
+    if (!xmode)
+        for (int64_t e = 0; e < NG; ++e)
+            if (!std::isfinite(grid[e])) { c->err = "predict_pd: non-finite grid value"; return SCFGP_ENONFINITE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/pd_time.py)
+    int rc;
+    if ((rc = ensure_pred_chunk(c))) return rc;
+    if ((rc = ensure_pred_factor(c))) return rc;
+    const bool curves = pd || pd_sd || pd_cov;
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, Jp2 = 2 * (int64_t)g0.Jp;
+    const int Gp = pd_grid_rows(G);
+    DevTmp d_dims, d_grid, wchunk;                                // dims | the (transformed) grid | w of the chunk, padded
+    if ((rc = dmalloc(c, &d_dims.p, sizeof(int) * ndim))) return rc;
+    if ((rc = dmalloc(c, &d_grid.p, sizeof(double) * NG))) return rc;
+    if (w && curves && (rc = dmalloc(c, &wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
+    const int* dv = (const int*)d_dims.p;
+    HIPCHK(c, hipMemcpyAsync(d_dims.p, dims, sizeof(int) * ndim, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(d_grid.p, grid, sizeof(double) * NG, hipMemcpyHostToDevice, c->st));
+    if (xmode) {
+        std::vector<double> hg(NG);
+        pd_grid(d_grid, dv, ndim, G, D, xmode, c->d_xscale, c->st);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(hg.data(), d_grid.p, sizeof(double) * NG, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        for (int64_t e = 0; e < NG; ++e)
+            if (!std::isfinite(hg[e])) { c->err = "predict_pd: non-finite grid value after the X scaler"; return SCFGP_ENONFINITE; }
+    }
+    RowFeed feed;                                                 // Li / two chunks of [Xs | w], for both passes
+    if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
+    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
+    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
+    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
+    std::vector<double> h_pd, h_sd;
+    if (curves) {
+        // ---- pass 1: the running sums, ndim x 2 x Jp ----
+        const Geom gmax = chunk_geom(g0, rows);
+        int ngs = (int)std::min<int64_t>(ndim, std::max<int64_t>(1, PD_RECORD_BYTES / (int64_t)sizeof(double) / pd_record_len(gmax, 1)));
+        if (c->test_pd_group > 0) ngs = std::min(ngs, c->test_pd_group);
+        DevTmp rec, acc, flag;
+        if ((rc = dmalloc(c, &rec.p, sizeof(double) * pd_record_len(gmax, ngs)))) return rc;
+        if ((rc = dmalloc(c, &acc.p, sizeof(double) * ndim * Jp2))) return rc;
+        if ((rc = dmalloc(c, &flag.p, sizeof(int) * 4))) return rc;
+        HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * ndim * Jp2, c->st));
+        HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int) * 4, c->st));
+        auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
+        if ((rc = upload(0))) return rc;
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const Geom g = chunk_geom(g0, rows_of(i));
+            const double *x, *wraw;
+            if ((rc = feed.acquire(i, &x, &wraw))) return rc;
+            pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, wchunk.p, c->st, xmode, c->d_xscale);
+            if ((rc = feed.release(i))) return rc;
+            for (int a0 = 0; a0 < ndim; a0 += ngs)
+                if ((rc = DISPATCH(c, pd_sums_chunk, c, g, wchunk.p, dv + a0, std::min(ngs, ndim - a0), rec.p, acc + a0 * Jp2))) return rc;
+            if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        }
+        update_check_finite(acc, ndim * Jp2, (int*)flag.p, c->st);
+        int hflag[4];
+        HIPCHK(c, hipMemcpyAsync(hflag, flag.p, sizeof(hflag), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->copy_st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        HIPCHK(c, hipGetLastError());
+        if (hflag[1]) { c->err = "predict_pd: non-finite weighted sum of the features"; return SCFGP_ENONFINITE; }
+        // ---- the curves: groups of dimensions whose stacked rows fit the chunk buffers ----
+        int ngc = (int)std::min<int64_t>(ndim, PRED_ROWS / Gp);
+        if (c->test_pd_group > 0) ngc = std::min(ngc, c->test_pd_group);
+        const int64_t GG = (int64_t)G * G;
+        DevTmp cur, stage; OutRing ring;                          // pd | scratch | sd of a group | two slots of G x G
+        if ((rc = dmalloc(c, &cur.p, sizeof(double) * 3 * PRED_ROWS))) return rc;
+        if (pd_cov && (rc = dmalloc(c, &stage.p, sizeof(double) * 2 * GG))) return rc;
+        if ((rc = ring.open(c))) return rc;
+        h_pd.resize(NG); h_sd.resize(NG);
+        int64_t nslot = 0, prev = 0;
+        auto download = [&](int64_t k, int64_t a) {
+            return ring.drain(k, [&]() -> int {
+                HIPCHK(c, hipMemcpyAsync(pd_cov + a * GG, stage + (k & 1) * GG, sizeof(double) * GG, hipMemcpyDeviceToHost, c->copy_st));
+                return SCFGP_OK;
+            });
+        };
+        for (int a0 = 0; a0 < ndim; a0 += ngc) {
+            const int ng = std::min(ngc, ndim - a0);
+            const Geom gr = chunk_geom(g0, (int64_t)ng * Gp);
+            if ((rc = DISPATCH(c, pd_curves, c, gr, LiT, acc + a0 * Jp2, W, dv + a0, d_grid + (int64_t)a0 * G, ng, G, cur.p, cur + PRED_ROWS,
+                               cur + 2 * PRED_ROWS)))
+                return rc;
+            HIPCHK(c, hipMemcpy2DAsync(h_pd.data() + (int64_t)a0 * G, sizeof(double) * G, cur.p, sizeof(double) * Gp, sizeof(double) * G, ng,
+                                       hipMemcpyDeviceToHost, c->st));
+            HIPCHK(c, hipMemcpy2DAsync(h_sd.data() + (int64_t)a0 * G, sizeof(double) * G, cur + 2 * PRED_ROWS, sizeof(double) * Gp,
+                                       sizeof(double) * G, ng, hipMemcpyDeviceToHost, c->st));
+            if (pd_cov)
+                for (int a = 0; a < ng; ++a, ++nslot) {
+                    if ((rc = ring.acquire(nslot))) return rc;
+                    if ((rc = DISPATCH(c, pd_cov_dim, c, a, G, stage + (nslot & 1) * GG))) return rc;
+                    if ((rc = ring.computed(nslot))) return rc;
+                    if (nslot >= 1 && (rc = download(nslot - 1, prev))) return rc;
+                    prev = a0 + a;
+                }
+            // the copies out of cur and predcov's reads of p_C are on the context's stream, ahead of the next group's kernels
+        }
+        if (pd_cov && nslot >= 1 && (rc = download(nslot - 1, prev))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->copy_st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        HIPCHK(c, hipGetLastError());
+    }
+    if (ice) {
+        // ---- pass 2: one T_chunk x G block per (chunk, dimension) ----
+        OutRing ring; DevTmp stage, R, keep;                      // two blocks | the rotated weights | the saved column
+        // The rows go through the feed of pass 1 again.  Both streams have drained, so its events are all past; the jobs go on from an
+        // even number, so that the halves alternate as before and a wait for reuse meets a recorded (or never used) event.
+        const int64_t j0 = curves ? (nchunks + 1) / 2 * 2 : 0;
+        if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * G))) return rc;
+        if ((rc = dmalloc(c, &R.p, c->tsize() * sample_w_rows(g0.K) * sample_w_cols(G)))) return rc;
+        if ((rc = dmalloc(c, &keep.p, sizeof(double) * PRED_ROWS))) return rc;
+        if ((rc = ring.open(c))) return rc;
+        auto upload = [&](int64_t i) { return feed.upload(j0 + i, Xs + i * PRED_ROWS * D, nullptr, rows_of(i)); };
+        auto slot = [&](int64_t k) { return stage + (k & 1) * rows * G; };
+        auto download = [&](int64_t k) {
+            const int64_t i = k / ndim, a = k % ndim;
+            return ring.drain(k, [&]() -> int {
+                HIPCHK(c, hipMemcpyAsync(ice + (a * T + i * PRED_ROWS) * G, slot(k), sizeof(double) * rows_of(i) * G, hipMemcpyDeviceToHost,
+                                         c->copy_st));
+                return SCFGP_OK;
+            });
+        };
+        if ((rc = upload(0))) return rc;
+        int64_t k = 0;
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const Geom g = chunk_geom(g0, rows_of(i));
+            const double* x;
+            if ((rc = feed.acquire(j0 + i, &x))) return rc;
+            pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
+            if ((rc = feed.release(j0 + i))) return rc;
+            for (int a = 0; a < ndim; ++a, ++k) {
+                if ((rc = ring.acquire(k))) return rc;
+                if ((rc = DISPATCH(c, pd_ice_chunk, c, g, dims[a], d_grid + (int64_t)a * G, G, R.p, keep.p, slot(k)))) return rc;
+                if ((rc = ring.computed(k))) return rc;
+                if (a == 0 && i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+                if (k >= 1 && (rc = download(k - 1))) return rc;
+            }
+        }
+        if ((rc = download(k - 1))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->copy_st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        HIPCHK(c, hipGetLastError());
+    }
+    if (pd) memcpy(pd, h_pd.data(), sizeof(double) * NG);
+    if (pd_sd) memcpy(pd_sd, h_sd.data(), sizeof(double) * NG);
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // greedy maximum-information choice of m rows from a pool (select.hip; derivation in include/scfgp_hip.h)
 // ----------------------------------------------------------------------------------------------
 static constexpr int SELECT_MAX_M = 4096;
@@ -3180,6 +3415,7 @@ extern "C" int scfgp_set_option(scfgp_ctx* c, const char* name, int64_t value) {
     else if (s == "cond_threshold_w") c->escw_thr = (double)value;
     else if (s == "roctx") c->roctx_on = value != 0;
     else if (s == "test_deny_level") { c->test_deny_level = (int)value; return SCFGP_OK; }       // tests: levels >= value are refused as if out of memory
+    else if (s == "test_pd_group") { c->test_pd_group = (int)value; return SCFGP_OK; }         // tests: scfgp_predict_pd takes at most `value` dimensions per group
     else if (s == "test_fail_stage") { c->test_fail_stage = (int)value; return SCFGP_OK; }       // tests: the next sweep `value` (1..3) fails
     else { c->err = "unknown option " + s; return SCFGP_EARG; }
     // kernels not run so far, buffers not allocated so far: the next scfgp_train starts with an eager iteration again

@@ -334,6 +334,57 @@ class HipEngine(object):
                 out[k] = a
         return out
 
+    PD_MODES = {'scaled': 0, 'raw': 1}
+    PD_OUTPUTS = ('pd', 'sd', 'cov', 'ice')
+
+    def predict_pd(self, Xs, alpha, Li, dims, grid, w=None, mode='scaled', want=('pd', 'sd')):
+        """Partial-dependence and ICE curves of single inputs over the pool rows Xs (include/scfgp_hip.h: scfgp_predict_pd): a dict with
+        the outputs named in `want` -- 'pd' (ndim, G) the PD curve of every dimension in `dims` over its row of `grid` (ndim, G), 'sd'
+        (ndim, G) its latent posterior standard deviation, 'cov' (ndim, G, G) its posterior covariance, 'ice' (ndim, T, G) the individual
+        curves; all in scaled y units.  w: T weights >= 0 (None: all 1); rows of weight 0 count for 'ice' only.  mode 'scaled': Xs and the
+        grid as predict takes them; 'raw': unscaled Xs through the registered X scaler, `dims` naming raw columns (none that the scaler
+        dropped) and the grid in raw units of its column.  1 <= G <= 1024."""
+        if mode not in self.PD_MODES:
+            raise ValueError('predict_pd: mode must be one of %s' % sorted(self.PD_MODES))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in self.PD_OUTPUTS for k in want):
+            raise ValueError('predict_pd: want must name some of %s' % (self.PD_OUTPUTS,))
+        m = self.PD_MODES[mode]
+        Xs = np.asarray(Xs, dtype=np.float64)
+        if Xs.ndim != 2:
+            raise TypeError('Xs must be a 2-d float64 array')
+        cols = getattr(self, '_xcols', None) if m else None
+        if m and cols is None:
+            raise ValueError('predict_pd: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+        if cols is not None:
+            where = {int(cc): i for i, cc in enumerate(cols)}
+            if any(int(d) not in where for d in dims):
+                raise ValueError('predict_pd: dims names a column that the X scaler dropped or that does not exist')
+            dims = np.array([where[int(d)] for d in dims], dtype=np.int64)
+            Xs = Xs[:, cols]
+        Xs = np.ascontiguousarray(Xs)
+        if Xs.shape[1] != self.D:
+            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        if grid.ndim != 2 or grid.shape[0] != dims.size:
+            raise ValueError('grid must be (ndim, G) with one row per entry of dims')
+        alpha, Li = self._factors(alpha, Li)
+        T, nd, G = Xs.shape[0], int(dims.size), int(grid.shape[1])
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+            if w.size != T:
+                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        dims32 = np.ascontiguousarray(dims, dtype=np.int32)
+        shapes = {'pd': (nd, G), 'sd': (nd, G), 'cov': (nd, G, G), 'ice': (nd, T, G)}
+        out = {k: np.empty(shapes[k]) for k in self.PD_OUTPUTS if k in want}
+        rc = self.lib.scfgp_predict_pd(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), dims32.ctypes.data_as(C.POINTER(C.c_int)), nd,
+                                       dptr(grid), G, m, *[dptr(out.get(k)) for k in self.PD_OUTPUTS])
+        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
+            raise FloatingPointError('predict_pd: %s' % self.last_error())
+        self._check(rc, 'predict_pd')
+        return out
+
     SAMPLE_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
 
     def _factors(self, alpha, Li):

@@ -335,6 +335,13 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.predict_gradcov(Xs_raw, alpha, Li, w=w, mode='raw', want=want)
 
+    def pred_pd_raw(self, Xs_raw, x_scaler, alpha, Li, dims, grid, w=None, want=('pd', 'sd')):
+        """Partial-dependence and ICE curves of the raw columns `dims` over the raw pool rows Xs_raw, the grid (ndim, G) in raw units of
+        its columns, the curves in scaled y units (engine.predict_pd with mode 'raw'): a dict of the outputs named in `want`."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.predict_pd(Xs_raw, alpha, Li, dims, grid, w=w, mode='raw', want=want)
+
     def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
         """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
         self._sync_params()

@@ -292,6 +292,37 @@ class SCFGP(object):
         lam, vec = np.linalg.eigh(asub)
         return lam[::-1].copy(), vec[:, ::-1].copy(), asub
 
+    def partial_dependence(self, X, dims=None, grid=20, weights=None, ice=False, cov=False):
+        """Partial-dependence (PD) curves of single inputs over the raw pool rows X, with their exact posterior uncertainty: a dict with
+        'dims' (the raw columns, default: every column the X scaler kept), 'grid' (ndim, G) in raw X units, 'pd' (ndim, G) the curve
+        pd[d][i] = sum_t w_t f(x_t with column d set to grid[d][i]) / sum_t w_t, 'sd' (ndim, G) its latent posterior standard deviation,
+        'importance' (ndim,) the standard deviation of pd[d] over its grid (the PD-based importance measure) and, on request, 'cov'
+        (ndim, G, G) the posterior covariance of every curve and 'ice' (ndim, T, G) the individual conditional expectation curves.
+        grid: an integer G for that many quantiles of the pool's own column (per dimension), or an array (G,) shared by all dimensions or
+        (ndim, G).  weights: T row weights >= 0.  pd, sd, cov and ice are in the SCALED target's units: the y scaler's backward transform
+        is not affine, so a PD curve in raw y units is not Gaussian -- the argument of predict_cov and acquire (include/scfgp_hip.h:
+        scfgp_predict_pd)."""
+        owner = getattr(self.pred_func, '__self__', None)
+        if not isinstance(owner, CompiledFuncs):
+            raise TypeError('partial_dependence needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        X = np.asarray(X, dtype=np.float64)
+        kept = [int(cc) for cc in self.X_scaler.data['cols']]
+        dims = kept if dims is None else [int(d) for d in np.atleast_1d(dims)]
+        if np.ndim(grid) == 0:
+            G = int(grid)
+            q = (np.arange(G) + 0.5) / G
+            grid = np.stack([np.quantile(X[:, d], q) for d in dims])
+        else:
+            grid = np.asarray(grid, dtype=np.float64)
+            if grid.ndim == 1:
+                grid = np.tile(grid, (len(dims), 1))
+        want = ('pd', 'sd') + (('cov',) if cov else ()) + (('ice',) if ice else ())
+        out = owner.pred_pd_raw(X, self.X_scaler, self.alpha, self.Li, dims, grid, w=weights, want=want)
+        out['dims'] = np.array(dims)
+        out['grid'] = grid
+        out['importance'] = out['pd'].std(axis=1)
+        return out
+
     def sample(self, Xs, nsamples, seed=0, noise=False):
         """nsamples posterior sample functions of the fitted model at the raw rows Xs, in raw y units: (T, nsamples).  Column s is
         phi(x)^T w_s with w_s ~ N(alpha, kappa A^-1) (plus observation noise with noise=True), mapped through the y scaler's backward

@@ -8,8 +8,9 @@ reused) and at (20, 20, 280) with 5000 rows: predict, predict_raw, predict_y wit
 modes with and without the std gradient; sample_weights; sample in its three modes with and without noise, 3 samples; predict_cov
 symmetric at 2500 rows, cross at all rows x 50 and at 2500 x 9000 (two panels per chunk); condition in both modes; loo with blocks
 1, 7, 64 from host rows and block 7 on resident rows; select without weights and with weights around the chunk boundaries, with
-std_after; predict_gradcov with all four outputs and weights over three chunks, in raw mode, and with its default outputs over all rows
-(where the build has it: outputs that only one build produces are listed as new, not as different).  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
+std_after; predict_gradcov with all four outputs and weights over three chunks, in raw mode, and with its default outputs over all rows;
+predict_pd with all four outputs and weights over all rows for three dimensions, in raw mode, and with its default outputs for every
+dimension (each of the last two where the build has it: outputs that only one build produces are listed as new, not as different).  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
 Usage: python tools/posterior_ab.py [--variants _head,] [--limit SECONDS]        (default limit: 300 per child)
        python tools/posterior_ab.py --child OUT.json                             (the list, in this process, on SCFGP_LIB_VARIANT)"""
 import hashlib
@@ -89,6 +90,17 @@ def calls(D, S, M, n, dt):
         yield 'predict_gradcov raw 2500 rows', tuple(out[k] for k in allout)
         out = eng.predict_gradcov(X, alpha, Li)
         yield 'predict_gradcov scaled %d rows, default outputs' % n, tuple(out[k] for k in ('dmu', 'dvar', 'asub'))
+    if hasattr(eng.lib, 'scfgp_predict_pd'):                     # the same: new in a build that has it
+        allpd = ('pd', 'sd', 'cov', 'ice')
+        dims = [0, D - 1, D // 2]
+        lo, hi = X[:, dims].min(0), X[:, dims].max(0)
+        grid = lo[:, None] + (hi - lo)[:, None] * np.linspace(0.0, 1.0, 7)[None, :]
+        out = eng.predict_pd(X, alpha, Li, dims, grid, w=w + 0.5, want=allpd)
+        yield 'predict_pd scaled %d rows' % n, tuple(out[k] for k in allpd)
+        out = eng.predict_pd(Xr[:2500], alpha, Li, dims, 1.5 * grid + 0.25, mode='raw', want=allpd)
+        yield 'predict_pd raw 2500 rows', tuple(out[k] for k in allpd)
+        out = eng.predict_pd(X, alpha, Li, list(range(D)), np.tile(np.linspace(0.1, 0.9, 5), (D, 1)))
+        yield 'predict_pd scaled %d rows, every dimension, default outputs' % n, tuple(out[k] for k in ('pd', 'sd'))
     eng.close()
 
 
