@@ -2,6 +2,7 @@
 // the staged evaluation  pass1 | factor | pass2 | adjoint | pass3 | finish  and predict.
 #include "../../include/scfgp_hip.h"
 #include "kernels.h"
+#include "api_host.h"
 
 #include <dlfcn.h>
 // RCCL: types and prototypes only -- the library is looked up at run time (scfgp_comm_init), no link-time dependency.  A ROCm
@@ -1328,6 +1329,19 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 // enqueues in the order "compute slot k, upload job k + 1, drain slot k - 1" and drains the last slot behind the loop: the host's
 // blocking copies in both directions fall under the next chunk's kernels, and device memory does not grow with the row count.
 // The waits for reuse run from the third job or slot on.
+//
+// Around it the entry points share (the parts that need no HIP are in api_host.h; each is described where it is defined): RowJobs, the
+// job schedule that RowFeed::upload(job, jobs) stages from (`base` shifts the feed's job number behind an earlier schedule; the loops stay
+// in the entry points, since where release, ring.acquire, ring.computed and the downloads fall differs); scan_weights, one pass over a
+// weight vector (all callers report the first negative row even behind a non-finite one, scfgp_predict_gradcov the first entry that is
+// either); Fail and need_model, the one way to refuse a call; load_factor's short form; BestBlock, the running best of a pool sweep.
+// Not through these helpers, and why:
+//   scfgp_loo with resident rows      the rows are read where they lie on the device: its loop skips the uploads and the feed
+//   scfgp_select_iv                   two schedules in a row (the reference chunks, then the pool): a one-line lambda picks a job's
+//   scfgp_condition, scfgp_forget     load_factor's long form (update_gather): other buffers, and the finite check of what was loaded
+//   scfgp_predict_grad, _raw, _y      scaler checks under their own names and texts, apart from predict_impl's parameter check
+//   scfgp_select, _select_iv, _qei    bare int flags, fetched twice under two different synchronisations: a helper would not be shorter
+// scfgp_forget's second phase and scfgp_predict_pd's second pass use RowJobs through `base`: their feed goes on counting.
 template <int N> struct Events {                                  // call-scoped events: released on every return path
     hipEvent_t e[N] = {};
     int create(scfgp_ctx* c) {
@@ -1355,6 +1369,8 @@ struct RowFeed {
         HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
         return SCFGP_OK;
     }
+    // a job of a schedule, as the feed's job base + job
+    int upload(int64_t job, const RowJobs& j, int64_t base = 0) { return upload(base + job, j.x(job, c->g.D), j.targets(job), j.rows(job)); }
     int acquire(int64_t job, const double** x, const double** y = nullptr) {
         const int h = (int)(job & 1);
         HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[h], 0));
@@ -1414,6 +1430,49 @@ static int load_factor(scfgp_ctx* c, double* raw, const double* Li, PadFn pad, d
     DISPATCH(c, type_factor, c, L64, LiT, Li_typed);
     return SCFGP_OK;
 }
+// The usual operands: L64 is d_T1, the typed Li^T goes to d_AbarT (scratch outside adjoint..pass3) and is handed back in *LiT, the
+// typed Li to p_Li (typed_Li), alpha to alpha_pred().  The caller synchronises the stream before the feed's buffer is reused.
+static int load_factor(scfgp_ctx* c, RowFeed& feed, const double* Li, PadFn pad, bool typed_Li, const double* alpha, const void** LiT) {
+    *LiT = c->d_AbarT;
+    return load_factor(c, feed.raw, Li, pad, c->d_T1, c->d_AbarT, typed_Li ? c->p_Li : nullptr, alpha, alpha ? c->alpha_pred() : nullptr);
+}
+
+// One way to refuse a call: "<who>: <what>" is the context's error text.
+struct Fail {
+    scfgp_ctx* c; const char* who;
+    int set(const std::string& what, int code) const { c->err = std::string(who) + ": " + what; return code; }
+    int arg(const std::string& what) const { return set(what, SCFGP_EARG); }
+    int nonfinite(const std::string& what) const { return set(what, SCFGP_ENONFINITE); }
+};
+// what a posterior entry point needs of the context before it reads its other arguments' values
+static int need_model(const Fail& f, bool x_scaler, bool y_scaler = false) {
+    if (x_scaler && !f.c->d_xscale) return f.arg("no X scaler set");
+    if (y_scaler && !f.c->d_yscale) return f.arg("no y scaler set");
+    if (!f.c->have_params) return f.arg("parameters not set");
+    return SCFGP_OK;
+}
+
+// The running best of a pool sweep: n (value, row) pairs and one double that holds the call's int flags, behind the workgroups' records
+// of two chunks (values of slot 0, of slot 1, then the rows of each; chunk i writes slot i & 1): 4 * nrec + 2 * n + 1 doubles.
+struct BestBlock {
+    double* rec = nullptr; int64_t n = 0, nrec = 0;
+    static int64_t doubles(int64_t n, int64_t nrec) { return 4 * nrec + 2 * n + 1; }
+    void carve(double* base, int64_t n_, int64_t nrec_) { rec = base; n = n_; nrec = nrec_; }
+    double* v() const { return rec + 4 * nrec; }
+    long long* t() const { return (long long*)(v() + n); }
+    int* flag() const { return (int*)(v() + 2 * n); }
+    double* rec_v(int64_t i) const { return rec + (i & 1) * nrec; }
+    long long* rec_t(int64_t i) const { return (long long*)(rec + (2 + (i & 1)) * nrec); }
+    int clear(scfgp_ctx* c) const { HIPCHK(c, hipMemsetAsync(flag(), 0, sizeof(double), c->st)); return SCFGP_OK; }
+    // host: 2 * n + 1 doubles, [v | t | flags]; both streams have drained on return, so the caller can refuse before it writes an output
+    int fetch(scfgp_ctx* c, double* host) const {
+        HIPCHK(c, hipMemcpyAsync(host, v(), sizeof(double) * (2 * n + 1), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(c, hipStreamSynchronize(c->copy_st));
+        HIPCHK(c, hipStreamSynchronize(c->st));
+        return SCFGP_OK;
+    }
+    int host_flag(const double* host, int k = 0) const { int f[2]; memcpy(f, host + 2 * n, sizeof(f)); return f[k]; }
+};
 
 // raw_mode: apply the registered X scaler while packing; post: y-scaler backward transform of the outputs on
 // the device and, with targets ys, the six validation metrics; dmu != NULL: also the gradients of mu (and, dstd != NULL, of std) in
@@ -1422,10 +1481,10 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
                         double* mu, double* sd, int raw_mode, int post = 0, const double* ys = nullptr,
                         double* metrics = nullptr, double* dmu = nullptr, double* dstd = nullptr) {
     if (!c || !Xs || !alpha || !Li || !mu || !sd || T < 1) { if (c) c->err = "predict: bad arguments"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "predict: parameters not set"; return SCFGP_EARG; }
+    int rc;
+    if ((rc = need_model({c, "predict"}, false))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     const bool grad = dmu != nullptr;
     if (grad && (rc = ensure_pred_grad(c, dstd != nullptr))) return rc;
@@ -1434,8 +1493,8 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 2 * T))) return rc;
     double* d_mu = d_out; double* d_sd = d_out + T;
     // the sweep operand is Li^T itself: sigma* needs rowsum((Phi* Li^T)^2) (SCFGP/SCFGP.py:144), a triangular product
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, nullptr, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, false, alpha, &LiT))) return rc;
     DevTmp d_grad;                                                // dmu | dstd of all T rows (T x D each)
     if (grad) {
         if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D * (dstd ? 2 : 1)))) return rc;
@@ -1444,19 +1503,18 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
     }
     double* d_dmu = d_grad; double* d_dsd = grad && dstd ? d_grad + T * g0.D : nullptr;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    const int nchunks = (int)((T + PRED_ROWS - 1) / PRED_ROWS);
+    const RowJobs jobs = {Xs, nullptr, T, PRED_ROWS};
+    const int nchunks = (int)jobs.count();
     if (post && ys) {
         if ((rc = dmalloc(c, &d_ys.p, sizeof(double) * (T + 8)))) return rc;
         if ((rc = dmalloc(c, &d_part.p, sizeof(double) * 4 * YPOST_BLOCKS * nchunks))) return rc;
         HIPCHK(c, hipMemcpyAsync(d_ys, ys, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
         ypost_mean(d_ys, T, d_ys + T, c->st);
     }
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = i * PRED_ROWS;
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const int64_t t0 = jobs.row0(i);
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, raw_mode ? c->xs_mode : 0, c->d_xscale);
@@ -1474,7 +1532,7 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
         if (post)
             ypost_chunk(d_mu + t0, d_sd + t0, d_ys.p ? d_ys + t0 : nullptr, g.N, c->ys_mode, c->d_yscale, d_ys.p ? d_ys + T : nullptr,
                         d_part.p ? d_part + 4 * YPOST_BLOCKS * i : nullptr, c->st);
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
     }
     HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
@@ -1578,7 +1636,7 @@ static int sample_check(scfgp_ctx* c, bool ptrs_ok, int nsamp, const char* who) 
 extern "C" int scfgp_sample_weights(scfgp_ctx* c, const double* alpha, const double* Li, int nsamp, uint64_t seed, double* W) {
     if (!c) return SCFGP_EARG;
     if (int rc = sample_check(c, alpha && Li && W, nsamp, "sample_weights")) return rc;
-    if (!c->have_params) { c->err = "sample_weights: parameters not set"; return SCFGP_EARG; }
+    if (int rc = need_model({c, "sample_weights"}, false)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     SampleW sw;
     if (int rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw)) return rc;
@@ -1595,40 +1653,37 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
     if (!c) return SCFGP_EARG;
     int rc;
     if ((rc = sample_check(c, Xs && alpha && Li && out && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample"))) return rc;
-    if (mode >= 1 && !c->d_xscale) { c->err = "sample: no X scaler set"; return SCFGP_EARG; }
-    if (mode == 2 && !c->d_yscale) { c->err = "sample: no y scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "sample: parameters not set"; return SCFGP_EARG; }
+    if ((rc = need_model({c, "sample"}, mode >= 1, mode == 2))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     if ((rc = ensure_pred_chunk(c))) return rc;
     SampleW sw;
     if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const RowJobs jobs = {Xs, nullptr, T, PRED_ROWS};
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count();
     RowFeed feed; OutRing ring; DevTmp stage;                     // two chunks of Xs | two chunks of samples
     if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * nsamp))) return rc;
     if ((rc = ring.open(c))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
     auto slot = [&](int64_t i) { return stage + (i & 1) * rows * nsamp; };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
     auto download = [&](int64_t i) {
         return ring.drain(i, [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(out + i * PRED_ROWS * nsamp, slot(i), sizeof(double) * rows_of(i) * nsamp, hipMemcpyDeviceToHost, c->copy_st));
+            HIPCHK(c, hipMemcpyAsync(out + jobs.row0(i) * nsamp, slot(i), sizeof(double) * jobs.rows(i) * nsamp, hipMemcpyDeviceToHost, c->copy_st));
             return SCFGP_OK;
         });
     };
     const int ymode = mode == 2 ? c->ys_mode : -1;
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
         if ((rc = ring.acquire(i))) return rc;
-        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, i * PRED_ROWS, seed, noise, ymode, slot(i)))) return rc;
+        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, noise, ymode, slot(i)))) return rc;
         if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(nchunks - 1))) return rc;
@@ -1640,38 +1695,35 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
 
 // scfgp_sample's pipeline without the OutRing: the weights w travel as the feed's targets and reach the product's epilogue through
 // pack_data's zero-padded copy; per chunk the workgroups' records (two slots, alternating) are merged into nsamp running (value, row)
-// pairs on the device.  The run owns its buffers: bestv | bestt | flag (nsamp, nsamp, 1: contiguous) are valid once the context's
-// stream has drained.  xraw: the rows go through the registered X scaler.
+// pairs on the device.  The run owns its buffers: `best` (n = nsamp) is valid once the context's stream has drained.  xraw: the rows go
+// through the registered X scaler.
 struct SampleArgmaxRun {
     RowFeed feed; DevTmp wchunk, rec;                             // two chunks of [Xs | w] | w of the chunk, padded | records, running best, flag
-    double* bestv = nullptr; long long* bestt = nullptr; int* flag = nullptr;
+    BestBlock best;
 };
 static int sample_argmax_run(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const void* Wt, int nsamp, bool xraw, int minimize,
                              SampleArgmaxRun& r) {
     const Geom& g0 = c->g;
     int rc;
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const RowJobs jobs = {Xs, w, T, PRED_ROWS};
+    const int64_t nchunks = jobs.count();
     const int64_t nrec = sample_blocks(round_up(std::min<int64_t>(T, PRED_ROWS), 256), c->tsize()) * nsamp;      // records of a chunk
     if ((rc = r.feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0))))) return rc;
     if (w && (rc = dmalloc(c, &r.wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
-    if ((rc = dmalloc(c, &r.rec.p, sizeof(double) * (4 * nrec + 2 * nsamp + 1)))) return rc;
-    double* rec = r.rec;
-    r.bestv = rec + 4 * nrec;
-    r.bestt = (long long*)(r.bestv + nsamp);
-    r.flag = (int*)(r.bestv + 2 * nsamp);
-    HIPCHK(c, hipMemsetAsync(r.flag, 0, sizeof(double), c->st));
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return r.feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
+    if ((rc = dmalloc(c, &r.rec.p, sizeof(double) * BestBlock::doubles(nsamp, nrec)))) return rc;
+    r.best.carve(r.rec, nsamp, nrec);
+    const BestBlock& best = r.best;
+    if ((rc = best.clear(c))) return rc;
+    if ((rc = r.feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wraw;
         if ((rc = r.feed.acquire(i, &x, &wraw))) return rc;
         pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, r.wchunk.p, c->st, xraw ? c->xs_mode : 0, c->d_xscale);
         if ((rc = r.feed.release(i))) return rc;
-        const SampleArgmaxBufs b = {rec + (i & 1) * nrec, (long long*)(rec + (2 + (i & 1)) * nrec), r.bestv, r.bestt, r.flag};
-        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, Wt, nsamp, r.wchunk.p, minimize, i * PRED_ROWS, b))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        const SampleArgmaxBufs b = {best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
+        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, Wt, nsamp, r.wchunk.p, minimize, jobs.row0(i), b))) return rc;
+        if (i + 1 < nchunks && (rc = r.feed.upload(i + 1, jobs))) return rc;
     }
     return SCFGP_OK;
 }
@@ -1683,18 +1735,13 @@ extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, co
     if (!c) return SCFGP_EARG;
     int rc;
     if ((rc = sample_check(c, Xs && alpha && Li && idx && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_argmax"))) return rc;
-    if (mode >= 1 && !c->d_xscale) { c->err = "sample_argmax: no X scaler set"; return SCFGP_EARG; }
-    if (mode == 2 && !c->d_yscale) { c->err = "sample_argmax: no y scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "sample_argmax: parameters not set"; return SCFGP_EARG; }
+    const Fail fail = {c, "sample_argmax"};
+    if ((rc = need_model(fail, mode >= 1, mode == 2))) return rc;
     if (w) {
-        bool nonfinite = false, positive = false;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "sample_argmax: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) positive = true;
-        }
-        if (nonfinite) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-        if (!positive) { c->err = "sample_argmax: no row has a positive weight"; return SCFGP_EARG; }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) return fail.nonfinite("non-finite rows, weights or factors");
+        if (!ws.positive) return fail.arg("no row has a positive weight");
     }
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_pred_chunk(c))) return rc;
@@ -1702,15 +1749,11 @@ extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, co
     if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
     SampleArgmaxRun run;
     if ((rc = sample_argmax_run(c, Xs, T, w, sw.wt.p, nsamp, mode >= 1, minimize, run))) return rc;
-    if (mode == 2 && val) sample_argmax_finalize(run.bestv, nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
+    if (mode == 2 && val) sample_argmax_finalize(run.best.v(), nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
     HIPCHK(c, hipGetLastError());
     std::vector<double> h(2 * nsamp + 1);                         // the outputs are written on success only
-    HIPCHK(c, hipMemcpyAsync(h.data(), run.bestv, sizeof(double) * (2 * nsamp + 1), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    int flag;
-    memcpy(&flag, &h[2 * nsamp], sizeof(int));
-    if (flag) { c->err = "sample_argmax: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+    if ((rc = run.best.fetch(c, h.data()))) return rc;
+    if (run.best.host_flag(h.data())) return fail.nonfinite("non-finite rows, weights or factors");
     memcpy(idx, &h[nsamp], sizeof(int64_t) * nsamp);
     if (val) memcpy(val, h.data(), sizeof(double) * nsamp);
     return SCFGP_OK;
@@ -1725,81 +1768,73 @@ extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const do
                              const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize, double* acq,
                              int64_t* idx, double* val, double* mu, double* sd, double* grad) {
     if (!c) return SCFGP_EARG;
-    auto bad = [&](const char* what) { c->err = std::string("acquire: ") + what; return SCFGP_EARG; };
-    if (!Xs || !alpha || !Li) return bad("NULL Xs, alpha or Li");
-    if (T < 1) return bad("T must be at least 1");
-    if (kind < 0 || kind > 4) return bad("kind must lie in 0..4");
-    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
+    const Fail fail = {c, "acquire"};
+    if (!Xs || !alpha || !Li) return fail.arg("NULL Xs, alpha or Li");
+    if (T < 1) return fail.arg("T must be at least 1");
+    if (kind < 0 || kind > 4) return fail.arg("kind must lie in 0..4");
+    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
     const int need = kind == 0 ? 1 : (kind == 4 ? 0 : 2);
-    if (npar != need) return bad("npar does not match the kind");
-    if (need && !par) return bad("NULL par");
-    if (kind == 4 && (!fstar || nstar < 1 || nstar > ACQUIRE_MAX_STAR)) return bad("MES needs fstar with 1 <= nstar <= 1024");
-    if (kind != 4 && (fstar || nstar)) return bad("fstar given for a kind other than MES");
-    if (!acq && !idx && !grad) return bad("no output requested (acq, idx and grad are all NULL)");
-    if (val && !idx) return bad("val without idx");
-    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
-    if (!c->have_params) return bad("parameters not set");
+    if (npar != need) return fail.arg("npar does not match the kind");
+    if (need && !par) return fail.arg("NULL par");
+    if (kind == 4 && (!fstar || nstar < 1 || nstar > ACQUIRE_MAX_STAR)) return fail.arg("MES needs fstar with 1 <= nstar <= 1024");
+    if (kind != 4 && (fstar || nstar)) return fail.arg("fstar given for a kind other than MES");
+    if (!acq && !idx && !grad) return fail.arg("no output requested (acq, idx and grad are all NULL)");
+    if (val && !idx) return fail.arg("val without idx");
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     AcquireSpec spec = {kind, {0.0, 0.0}, nullptr, kind == 4 ? nstar : 0, noise ? 1 : 0, minimize ? 1 : 0};
     bool nonfinite = false;
     for (int i = 0; i < need; ++i) { spec.par[i] = par[i]; if (!std::isfinite(par[i])) nonfinite = true; }
     for (int i = 0; i < spec.nstar; ++i) if (!std::isfinite(fstar[i])) nonfinite = true;
-    if (!nonfinite && kind == 0 && par[0] < 0.0) return bad("beta must not be negative");
-    if (!nonfinite && (kind >= 1 && kind <= 3) && par[1] < 0.0) return bad("xi must not be negative");
+    if (!nonfinite && kind == 0 && par[0] < 0.0) return fail.arg("beta must not be negative");
+    if (!nonfinite && (kind >= 1 && kind <= 3) && par[1] < 0.0) return fail.arg("xi must not be negative");
     if (w) {
-        bool positive = false;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "acquire: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) positive = true;
-        }
-        if (!nonfinite && !positive) return bad("no row has a positive weight");
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) nonfinite = true;
+        if (!nonfinite && !ws.positive) return fail.arg("no row has a positive weight");
     }
-    if (nonfinite) { c->err = "acquire: non-finite par, fstar or weights"; return SCFGP_ENONFINITE; }
+    if (nonfinite) return fail.nonfinite("non-finite par, fstar or weights");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if (grad && (rc = ensure_pred_grad(c, true))) return rc;
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const RowJobs jobs = {Xs, w, T, PRED_ROWS};
+    const int64_t nchunks = jobs.count();
     const int64_t nrec = acquire_blocks(PRED_ROWS);
     RowFeed feed; DevTmp d_out, d_grad, work;     // Li / two chunks of [Xs | w] | mu, sd, acq of all T rows | grad of all T rows | chunk scratch
     if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0)), (int64_t)g0.K * g0.K))) return rc;
     if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 3 * T))) return rc;
     // work: w of the chunk, padded | a_u | a_sigma | d sigma / d x of the chunk | records of two chunks | running best, flag | fstar
     const int64_t n_dsd = grad ? PRED_ROWS * g0.D : 0;
-    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + n_dsd + 4 * nrec + 3 + ACQUIRE_MAX_STAR)))) return rc;
+    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + n_dsd + BestBlock::doubles(1, nrec) + ACQUIRE_MAX_STAR)))) return rc;
     double* d_mu = d_out; double* d_sd = d_out + T; double* d_acq = d_out + 2 * T;
     double* d_w = work; double* d_au = work + PRED_ROWS; double* d_as = work + 2 * PRED_ROWS; double* d_dsd = work + 3 * PRED_ROWS;
-    double* d_rec = d_dsd + n_dsd;
-    double* d_bestv = d_rec + 4 * nrec;
-    long long* d_bestt = (long long*)(d_bestv + 1);
-    int* d_flag = (int*)(d_bestv + 2);
-    double* d_fstar = d_bestv + 3;
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
+    BestBlock best;
+    best.carve(d_dsd + n_dsd, 1, nrec);
+    double* d_fstar = best.rec + BestBlock::doubles(1, nrec);
+    if ((rc = best.clear(c))) return rc;
     if (kind == 4) {
         HIPCHK(c, hipMemcpyAsync(d_fstar, fstar, sizeof(double) * nstar, hipMemcpyHostToDevice, c->st));
         spec.fstar = d_fstar;
     }
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, nullptr, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, false, alpha, &LiT))) return rc;
     if (grad) {
         if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D))) return rc;
         DISPATCH(c, grad_operand, c);
         DISPATCH(c, type_factor, c, c->d_T1, nullptr, c->p_Li);
     }
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * g0.D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = i * PRED_ROWS;
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const int64_t t0 = jobs.row0(i);
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wraw;
         if ((rc = feed.acquire(i, &x, &wraw))) return rc;
         pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if (!grad && (rc = feed.release(i))) return rc;
-        const AcquireBufs b = {d_mu + t0, d_sd + t0, d_acq + t0, d_au, d_as, d_rec + (i & 1) * nrec, (long long*)(d_rec + (2 + (i & 1)) * nrec),
-                               d_bestv, d_bestt, d_flag};
+        const AcquireBufs b = {d_mu + t0, d_sd + t0, d_acq + t0, d_au, d_as, best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
         if ((rc = DISPATCH(c, acquire_chunk, c, g, LiT, spec, w ? d_w : nullptr, t0, b))) return rc;
         if (grad) {
             double* gm = d_grad + t0 * g0.D;
@@ -1808,16 +1843,12 @@ extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const do
             if (mode == 1 && c->xs_mode) xgrad_chunk(x, g.N, g0.D, c->xs_mode, c->d_xscale, gm, nullptr, c->st);
             if ((rc = feed.release(i))) return rc;
         }
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
     }
     HIPCHK(c, hipGetLastError());
     double h[3];                                                  // the running best and the flag first: the outputs are written on success only
-    HIPCHK(c, hipMemcpyAsync(h, d_bestv, sizeof(h), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    int flag;
-    memcpy(&flag, &h[2], sizeof(int));
-    if (flag) { c->err = "acquire: an eligible row has a non-finite mu, sigma or value, or sigma = 0"; return SCFGP_ENONFINITE; }
+    if ((rc = best.fetch(c, h))) return rc;
+    if (best.host_flag(h)) return fail.nonfinite("an eligible row has a non-finite mu, sigma or value, or sigma = 0");
     if (acq) HIPCHK(c, hipMemcpyAsync(acq, d_acq, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (mu) HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (sd) HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
@@ -1838,45 +1869,42 @@ extern "C" int scfgp_acquire_kg(scfgp_ctx* c, const double* Xc, int64_t T, const
                                 const double* Li, const double* z, int J, int mode, int noise, int minimize, double* kg, double* kg_hi,
                                 int64_t* idx, double* val, double* m, double* s) {
     if (!c) return SCFGP_EARG;
-    auto bad = [&](const char* what) { c->err = std::string("acquire_kg: ") + what; return SCFGP_EARG; };
-    if (!Xc || !alpha || !Li || !z) return bad("NULL Xc, alpha, Li or z");
-    if (T < 1) return bad("T must be at least 1");
+    const Fail fail = {c, "acquire_kg"};
+    if (!Xc || !alpha || !Li || !z) return fail.arg("NULL Xc, alpha, Li or z");
+    if (T < 1) return fail.arg("T must be at least 1");
     if (!Xr) {
-        if (T > PRED_ROWS) return bad("the symmetric form (Xr == NULL) takes 1..32768 rows");
+        if (T > PRED_ROWS) return fail.arg("the symmetric form (Xr == NULL) takes 1..32768 rows");
         Xr = Xc; R = T;
-    } else if (R < 1 || R > PRED_ROWS) return bad("R must lie in 1..32768");
-    if (J < 3 || J > KG_MAX_NODES) return bad("J must lie in 3..32");
-    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
-    if (!kg && !kg_hi && !idx && !m && !s) return bad("no output requested (kg, kg_hi, idx, m and s are all NULL)");
-    if (val && !idx) return bad("val without idx");
-    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
-    if (!c->have_params) return bad("parameters not set");
+    } else if (R < 1 || R > PRED_ROWS) return fail.arg("R must lie in 1..32768");
+    if (J < 3 || J > KG_MAX_NODES) return fail.arg("J must lie in 3..32");
+    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
+    if (!kg && !kg_hi && !idx && !m && !s) return fail.arg("no output requested (kg, kg_hi, idx, m and s are all NULL)");
+    if (val && !idx) return fail.arg("val without idx");
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     bool nonfinite = false;
     for (int j = 0; j < J; ++j) if (!std::isfinite(z[j])) nonfinite = true;
     if (!nonfinite) {
         int zeros = z[0] == 0.0 ? 1 : 0;
         for (int j = 1; j < J; ++j) {
-            if (!(z[j] > z[j - 1])) return bad("the nodes must be strictly increasing");
+            if (!(z[j] > z[j - 1])) return fail.arg("the nodes must be strictly increasing");
             if (z[j] == 0.0) ++zeros;
         }
-        if (zeros != 1) return bad("exactly one node must be 0.0");
+        if (zeros != 1) return fail.arg("exactly one node must be 0.0");
     }
     if (w) {
-        bool positive = false;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "acquire_kg: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) positive = true;
-        }
-        if (!nonfinite && !positive) return bad("no row has a positive weight");
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) nonfinite = true;
+        if (!nonfinite && !ws.positive) return fail.arg("no row has a positive weight");
     }
-    if (nonfinite) { c->err = "acquire_kg: non-finite nodes or weights"; return SCFGP_ENONFINITE; }
+    if (nonfinite) return fail.nonfinite("non-finite nodes or weights");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, njobs = nchunks + 1;
+    const RowJobs jobs = {Xc, w, T, PRED_ROWS, Xr, R};              // job 0: the reference rows
+    const int64_t njobs = jobs.count();
     const int64_t nrec = acquire_blocks(PRED_ROWS), SR = kg_state_rows();
     const bool table = m || s;
     RowFeed feed; DevTmp d_out, work;             // Li / two jobs of [X | w] | kg, kg_hi (and m, s) of all T rows | chunk scratch
@@ -1884,55 +1912,43 @@ extern "C" int scfgp_acquire_kg(scfgp_ctx* c, const double* Xc, int64_t T, const
     if ((rc = dmalloc(c, &d_out.p, sizeof(double) * T * (2 + (table ? 2 * J : 0))))) return rc;
     // work: w of the chunk, padded | sigma of the chunk | d_r | z as given | nodes and h(-|z|) | records of two chunks | running best, flags |
     // bmin, bmax and the (m, s) states per row and column split
-    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + 96 + 4 * nrec + 3 + SR * (2 + 2 * J))))) return rc;
+    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + 96 + BestBlock::doubles(1, nrec) + SR * (2 + 2 * J))))) return rc;
     double* d_kg = d_out; double* d_hi = d_out + T; double* d_m = table ? d_out + 2 * T : nullptr; double* d_s = table ? d_m + T * J : nullptr;
     double* d_w = work; double* d_sd = work + PRED_ROWS; double* d_d = work + 2 * PRED_ROWS; double* d_z = work + 3 * PRED_ROWS;
     double* d_zf = d_z + 32;
-    double* d_rec = d_zf + 64;
-    double* d_bestv = d_rec + 4 * nrec;
-    long long* d_bestt = (long long*)(d_bestv + 1);
-    int* d_flag = (int*)(d_bestv + 2);                            // [0]: a candidate (acquire_argmax); [1]: a reference row
-    double* d_stb = d_bestv + 3; double* d_stm = d_stb + 2 * SR; double* d_sts = d_stm + SR * J;
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(double), c->st));
+    BestBlock best;                                               // flag [0]: a candidate (acquire_argmax); [1]: a reference row
+    best.carve(d_zf + 64, 1, nrec);
+    double* d_stb = best.rec + BestBlock::doubles(1, nrec); double* d_stm = d_stb + 2 * SR; double* d_sts = d_stm + SR * J;
+    if ((rc = best.clear(c))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_z, z, sizeof(double) * J, hipMemcpyHostToDevice, c->st));
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    auto job_rows = [&](int64_t job) { return job == 0 ? R : std::min<int64_t>(PRED_ROWS, T - (job - 1) * PRED_ROWS); };
-    auto upload = [&](int64_t job) {
-        if (job == 0) return feed.upload(0, Xr, nullptr, R);
-        return feed.upload(job, Xc + (job - 1) * PRED_ROWS * g0.D, w ? w + (job - 1) * PRED_ROWS : nullptr, job_rows(job));
-    };
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, job_rows(job));
+        const Geom g = chunk_geom(g0, jobs.rows(job));
         const double *x, *wraw;
         if ((rc = feed.acquire(job, &x, &wraw))) return rc;
-        const bool cand = job > 0;
+        const bool cand = !jobs.lead(job);
         pack_data(g, x, cand && w ? wraw : nullptr, nullptr, c->p_Xt, cand && w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(job))) return rc;
-        const int64_t i = job - 1, t0 = i * PRED_ROWS;
+        const int64_t i = jobs.chunk(job), t0 = i * PRED_ROWS;
         const KgBufs b = {d_d, d_zf, d_sd, d_stm, d_sts, d_stb, cand ? d_kg + t0 : nullptr, cand ? d_hi + t0 : nullptr,
                           cand && table ? d_m + t0 * J : nullptr, cand && table ? d_s + t0 * J : nullptr};
         if (!cand) {
-            if ((rc = DISPATCH(c, kg_ref_chunk, c, g, LiT, minimize ? 1 : 0, d_z, J, b, d_flag))) return rc;
+            if ((rc = DISPATCH(c, kg_ref_chunk, c, g, LiT, minimize ? 1 : 0, d_z, J, b, best.flag()))) return rc;
         } else {
             if ((rc = DISPATCH(c, kg_chunk, c, g, LiT, R, J, noise ? 1 : 0, b))) return rc;
-            const AcquireBufs ab = {b.kg_hi, d_sd, b.kg, nullptr, nullptr, d_rec + (i & 1) * nrec, (long long*)(d_rec + (2 + (i & 1)) * nrec),
-                                    d_bestv, d_bestt, d_flag};
+            const AcquireBufs ab = {b.kg_hi, d_sd, b.kg, nullptr, nullptr, best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
             acquire_argmax(g, w ? d_w : nullptr, t0, i == 0, ab, c->st);
         }
-        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
+        if (job + 1 < njobs && (rc = feed.upload(job + 1, jobs))) return rc;
     }
     HIPCHK(c, hipGetLastError());
     double h[3];                                                  // the running best and the flags first: the outputs are written on success only
-    HIPCHK(c, hipMemcpyAsync(h, d_bestv, sizeof(h), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    int flag[2];
-    memcpy(flag, &h[2], sizeof(flag));
-    if (flag[1]) { c->err = "acquire_kg: a reference row has a non-finite mean"; return SCFGP_ENONFINITE; }
-    if (flag[0]) { c->err = "acquire_kg: an eligible candidate has a non-finite value or sigma, or sigma = 0"; return SCFGP_ENONFINITE; }
+    if ((rc = best.fetch(c, h))) return rc;
+    if (best.host_flag(h, 1)) return fail.nonfinite("a reference row has a non-finite mean");
+    if (best.host_flag(h, 0)) return fail.nonfinite("an eligible candidate has a non-finite value or sigma, or sigma = 0");
     if (kg) HIPCHK(c, hipMemcpyAsync(kg, d_kg, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (kg_hi) HIPCHK(c, hipMemcpyAsync(kg_hi, d_hi, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
     if (m) HIPCHK(c, hipMemcpyAsync(m, d_m, sizeof(double) * T * J, hipMemcpyDeviceToHost, c->st));
@@ -1951,23 +1967,20 @@ extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, cons
     if (!c) return SCFGP_EARG;
     int rc;
     if ((rc = sample_check(c, Xs && W && grad && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_grad"))) return rc;
-    if (mode >= 1 && !c->d_xscale) { c->err = "sample_grad: no X scaler set"; return SCFGP_EARG; }
-    if (mode == 2 && !c->d_yscale) { c->err = "sample_grad: no y scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "sample_grad: parameters not set"; return SCFGP_EARG; }
+    const Fail fail = {c, "sample_grad"};
+    if ((rc = need_model(fail, mode >= 1, mode == 2))) return rc;
     const Geom& g0 = c->g;
     std::vector<double> hs;                                       // sidx as the feed's targets
     if (sidx) {
         hs.resize(T);
         for (int64_t t = 0; t < T; ++t) {
-            if (sidx[t] < 0 || sidx[t] >= nsamp) {
-                c->err = "sample_grad: sample index " + std::to_string(sidx[t]) + " at row " + std::to_string(t) + " is outside [0, nsamp)";
-                return SCFGP_EARG;
-            }
+            if (sidx[t] < 0 || sidx[t] >= nsamp)
+                return fail.arg("sample index " + std::to_string(sidx[t]) + " at row " + std::to_string(t) + " is outside [0, nsamp)");
             hs[t] = (double)sidx[t];
         }
     }
     for (int64_t e = 0, n = (int64_t)g0.K * nsamp; e < n; ++e)
-        if (!std::isfinite(W[e])) { c->err = "sample_grad: non-finite weights"; return SCFGP_ENONFINITE; }
+        if (!std::isfinite(W[e])) return fail.nonfinite("non-finite weights");
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_grad(c, false))) return rc;
@@ -1979,33 +1992,31 @@ extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, cons
     HIPCHK(c, hipMemcpyAsync(wraw, W, sizeof(double) * g0.K * nsamp, hipMemcpyHostToDevice, c->st));
     samplegrad_weights(wraw, g0.K, nsamp, wt, c->st);
     DISPATCH(c, grad_operand, c);
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, slot_len = rows * (g0.D + 1);
+    const RowJobs jobs = {Xs, sidx ? hs.data() : nullptr, T, PRED_ROWS};
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count(), slot_len = rows * (g0.D + 1);
     RowFeed feed; OutRing ring;
     if ((rc = feed.open(c, PRED_ROWS * (g0.D + (sidx ? 1 : 0))))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
     if ((rc = ring.open(c))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
     auto slot_grad = [&](int64_t i) { return stage + (i & 1) * slot_len; };
     auto slot_val = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * g0.D; };
-    auto upload = [&](int64_t i) {
-        return feed.upload(i, Xs + i * PRED_ROWS * g0.D, sidx ? hs.data() + i * PRED_ROWS : nullptr, rows_of(i));
-    };
     auto download = [&](int64_t i) {
         return ring.drain(i, [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(grad + i * PRED_ROWS * g0.D, slot_grad(i), sizeof(double) * rows_of(i) * g0.D, hipMemcpyDeviceToHost, c->copy_st));
-            if (val) HIPCHK(c, hipMemcpyAsync(val + i * PRED_ROWS, slot_val(i), sizeof(double) * rows_of(i), hipMemcpyDeviceToHost, c->copy_st));
+            const int64_t t0 = jobs.row0(i), n = jobs.rows(i);
+            HIPCHK(c, hipMemcpyAsync(grad + t0 * g0.D, slot_grad(i), sizeof(double) * n * g0.D, hipMemcpyDeviceToHost, c->copy_st));
+            if (val) HIPCHK(c, hipMemcpyAsync(val + t0, slot_val(i), sizeof(double) * n, hipMemcpyDeviceToHost, c->copy_st));
             return SCFGP_OK;
         });
     };
     const int xmode = mode >= 1 ? c->xs_mode : 0;
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *sraw;
         if ((rc = feed.acquire(i, &x, &sraw))) return rc;
         pack_data(g, x, sidx ? sraw : nullptr, nullptr, c->p_Xt, schunk.p, c->st, xmode, c->d_xscale);
         if ((rc = ring.acquire(i))) return rc;
-        if ((rc = DISPATCH(c, sample_grad_chunk, c, g, wt.p, schunk.p, i * PRED_ROWS, nsamp, slot_val(i), slot_grad(i)))) return rc;
+        if ((rc = DISPATCH(c, sample_grad_chunk, c, g, wt.p, schunk.p, jobs.row0(i), nsamp, slot_val(i), slot_grad(i)))) return rc;
         // the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is released after them), the y
         // scaler's at the scaled value, which its backward transform then replaces
         if (xmode) xgrad_chunk(x, g.N, g0.D, xmode, c->d_xscale, slot_grad(i), nullptr, c->st);
@@ -2015,7 +2026,7 @@ extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, cons
             sample_argmax_finalize(slot_val(i), (int)g.N, c->ys_mode, c->d_yscale, c->d_sc, c->st);
         }
         if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(nchunks - 1))) return rc;
@@ -2039,19 +2050,16 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
     if (!Xa || !Li || !cov || mode < 0 || mode > 1) { c->err = "predict_cov: bad arguments"; return SCFGP_EARG; }
     const bool sym = Xb == nullptr;
     if (sym) Tb = Ta;
-    if (Ta < 1) { c->err = "predict_cov: Ta must be at least 1"; return SCFGP_EARG; }
-    if (Tb < 1 || Tb > PRED_ROWS) {
-        c->err = sym ? "predict_cov: the symmetric form takes 1..32768 rows" : "predict_cov: Tb must lie in 1..32768";
-        return SCFGP_EARG;
-    }
-    if (!sym && noise) { c->err = "predict_cov: noise is defined for the symmetric form (Xb == NULL) only"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "predict_cov: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "predict_cov: parameters not set"; return SCFGP_EARG; }
+    const Fail fail = {c, "predict_cov"};
+    if (Ta < 1) return fail.arg("Ta must be at least 1");
+    if (Tb < 1 || Tb > PRED_ROWS) return fail.arg(sym ? "the symmetric form takes 1..32768 rows" : "Tb must lie in 1..32768");
+    if (!sym && noise) return fail.arg("noise is defined for the symmetric form (Xb == NULL) only");
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp;
     const size_t ts = c->tsize();
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     // panel height: whole 128-row tiles within COV_PANEL_BYTES, no more than a chunk holds
@@ -2060,16 +2068,12 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
     RowFeed feed; OutRing ring; DevTmp stage;                     // Li / two chunks of X | two panels of the result
     if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * R * Tb))) return rc;
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, true, nullptr, &LiT))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     if ((rc = ring.open(c))) return rc;
-    // uploads: job 0 is Xb in the cross form, the chunks of Xa follow
-    const int64_t nchunks = (Ta + PRED_ROWS - 1) / PRED_ROWS, first = sym ? 0 : 1, njobs = nchunks + first;
-    auto job_rows = [&](int64_t job) { return job < first ? Tb : std::min<int64_t>(PRED_ROWS, Ta - (job - first) * PRED_ROWS); };
-    auto upload = [&](int64_t job) {
-        return feed.upload(job, job < first ? Xb : Xa + (job - first) * PRED_ROWS * g0.D, nullptr, job_rows(job));
-    };
+    const RowJobs jobs = {Xa, nullptr, Ta, PRED_ROWS, Xb, Tb};       // job 0 is Xb in the cross form, the chunks of Xa follow
+    const int64_t njobs = jobs.count();
     // panel p: rows [row0, row0 + n) of the result
     struct Panel { int64_t row0, n; };
     auto slot = [&](int64_t p) { return stage + (p & 1) * R * Tb; };
@@ -2081,17 +2085,17 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
     };
     int64_t npanel = 0;
     Panel prev = {0, 0};
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, job_rows(job));
+        const Geom g = chunk_geom(g0, jobs.rows(job));
         const double* x;
         if ((rc = feed.acquire(job, &x))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(job))) return rc;
-        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, job < first ? c->p_V : c->p_C))) return rc;
-        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
-        if (job < first) continue;
-        const int64_t t0 = (job - first) * PRED_ROWS;
+        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, jobs.lead(job) ? c->p_V : c->p_C))) return rc;
+        if (job + 1 < njobs && (rc = feed.upload(job + 1, jobs))) return rc;
+        if (jobs.lead(job)) continue;
+        const int64_t t0 = jobs.row0(job);
         const void* Cb = sym ? c->p_C : c->p_V;
         for (int64_t r0 = 0; r0 < g.N; r0 += R, ++npanel) {
             const Panel pn = {t0 + r0, std::min<int64_t>(R, g.N - r0)};
@@ -2173,11 +2177,10 @@ static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const dou
                           c->u_flag))) return rc;
     if (wide) Impl<double>::type_factor(c, c->u_Li, ops.LiT, ops.Li);
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, X + i * PRED_ROWS * g0.D, y + i * PRED_ROWS, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
+    const RowJobs jobs = {X, y, n, PRED_ROWS};
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *yi;
         if ((rc = feed.acquire(i, &x, &yi))) return rc;
         pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
@@ -2187,7 +2190,7 @@ static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const dou
                        : DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), ops, out))) return rc;
         if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
         if (rr) update_sumsq(c->u_r, g.N, rr, c->st);
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
     }
     // non-finite rows or targets have reached C^T C or C^T r by now
     update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
@@ -2208,12 +2211,11 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
     if (!c) return SCFGP_EARG;
     if (!Xn || !yn || !alpha || !Li || !alpha_out || !Li_out || mode < 0 || mode > 1) { c->err = "condition: bad arguments"; return SCFGP_EARG; }
     if (n < 1) { c->err = "condition: n must be at least 1"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "condition: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "condition: parameters not set"; return SCFGP_EARG; }
+    int rc;
+    if ((rc = need_model({c, "condition"}, mode == 1))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    int rc;
     RowFeed feed;
     if ((rc = update_gather(c, feed, Xn, yn, n, alpha, Li, mode, nullptr))) return rc;
     const KUpdate k = update_buffers(c);
@@ -2259,13 +2261,13 @@ extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, in
     if (stats && !mu) { c->err = "forget: stats need mu and std"; return SCFGP_EARG; }
     if (!alpha_out && !mu) { c->err = "forget: no output asked for"; return SCFGP_EARG; }
     if (n < 1) { c->err = "forget: n must be at least 1"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "forget: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "forget: parameters not set"; return SCFGP_EARG; }
+    int rc;
+    if ((rc = need_model({c, "forget"}, mode == 1))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
-    int rc;
+    const RowJobs jobs = {Xo, yo, n, PRED_ROWS};
+    const int64_t nchunks = jobs.count();
     if ((rc = ensure_forget(c))) return rc;
     double* rec = c->f_out + 4 * PRED_ROWS; double* acc = c->f_out + 7 * PRED_ROWS;
     // In fp32 contexts the first pass is the fp64 one: the error of C^T C is divided by lam_min(S) here, and what the fp32 chains of the
@@ -2293,22 +2295,20 @@ extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, in
         HIPCHK(c, hipMemsetAsync(acc, 0, sizeof(double) * 3, c->st));
         OutRing ring;
         if ((rc = ring.open(c))) return rc;
-        auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, n - i * PRED_ROWS); };
-        // the feed's jobs go on counting behind the first pass's, so its halves and events keep their order
-        auto upload = [&](int64_t i) { return feed.upload(nchunks + i, Xo + i * PRED_ROWS * g0.D, yo + i * PRED_ROWS, rows_of(i)); };
+        // the feed's jobs go on counting behind the first pass's (base nchunks), so its halves and events keep their order
         auto slot = [&](int64_t i) { return c->f_out + (i & 1) * 2 * PRED_ROWS; };
         auto download = [&](int64_t i) {
             return ring.drain(i, [&]() -> int {
-                const int64_t t0 = i * PRED_ROWS, m = rows_of(i);
+                const int64_t t0 = jobs.row0(i), m = jobs.rows(i);
                 const double* o = slot(i);
                 HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
                 HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
                 return SCFGP_OK;
             });
         };
-        if ((rc = upload(0))) return rc;
+        if ((rc = feed.upload(0, jobs, nchunks))) return rc;
         for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, rows_of(i));
+            const Geom g = chunk_geom(g0, jobs.rows(i));
             const double *x, *yi;
             if ((rc = feed.acquire(nchunks + i, &x, &yi))) return rc;
             pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
@@ -2318,7 +2318,7 @@ extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, in
             if ((rc = DISPATCH(c, predict_chunk, c, g, c->u_LiT, o, o + PRED_ROWS))) return rc;
             if (stats) forget_stats(o, o + PRED_ROWS, c->u_y, g.N, PRED_ROWS, rec, acc, c->st);
             if ((rc = ring.computed(i))) return rc;
-            if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+            if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs, nchunks))) return rc;
             if (i >= 1 && (rc = download(i - 1))) return rc;
         }
         if ((rc = download(nchunks - 1))) return rc;
@@ -2370,31 +2370,29 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
         n = c->Nstore;
     }
     if (n < 1) { c->err = "loo: n must be at least 1"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "loo: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "loo: parameters not set"; return SCFGP_EARG; }
+    int rc;
+    if ((rc = need_model({c, "loo"}, mode == 1))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t CH = PRED_ROWS / block * block;               // rows per chunk: whole blocks
-    const int64_t nchunks = (n + CH - 1) / CH;
-    int rc;
+    const RowJobs jobs = {X, y, n, CH};
+    const int64_t nchunks = jobs.count();
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     if ((rc = ensure_loo(c))) return rc;
     RowFeed feed; OutRing ring;                                   // Li in host layout / two chunks of [X | y] (resident rows: Li only)
     if ((rc = feed.open(c, resident ? 0 : PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
     const unsigned long long bad0[2] = {0ull, ~0ull};
     HIPCHK(c, hipMemsetAsync(c->l_acc, 0, sizeof(double) * 8, c->st));
     HIPCHK(c, hipMemcpyAsync(c->l_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     if ((rc = ring.open(c))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(CH, n - i * CH); };
-    auto upload = [&](int64_t i) { return resident ? SCFGP_OK : feed.upload(i, X + i * CH * g0.D, y + i * CH, rows_of(i)); };
     auto slot = [&](int64_t i) { return c->l_out + (i & 1) * 3 * PRED_ROWS; };
     auto download = [&](int64_t i) {
         return ring.drain(i, [&]() -> int {
-            const int64_t t0 = i * CH, m = rows_of(i);
+            const int64_t t0 = jobs.row0(i), m = jobs.rows(i);
             const double* o = slot(i);
             HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
             HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
@@ -2402,10 +2400,10 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
             return SCFGP_OK;
         });
     };
-    if ((rc = upload(0))) return rc;
+    if (!resident && (rc = feed.upload(0, jobs))) return rc;    // resident rows are read where they lie: nothing is uploaded
     for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = i * CH;
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const int64_t t0 = jobs.row0(i);
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         if (resident) {
             pack_data(g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->p_Xt, c->l_y, c->st);
         } else {
@@ -2418,7 +2416,7 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
         double* o = slot(i);
         if ((rc = DISPATCH(c, loo_chunk, c, g, LiT, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS))) return rc;
         if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (!resident && i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(nchunks - 1))) return rc;
@@ -2462,32 +2460,29 @@ extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, 
     if (!c) return SCFGP_EARG;
     if (!Xs || !alpha || !Li || T < 1 || mode < 0 || mode > 1) { c->err = "predict_gradcov: bad arguments"; return SCFGP_EARG; }
     if (!dmu && !dvar && !dcov && !asub) { c->err = "predict_gradcov: no output requested"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "predict_gradcov: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "predict_gradcov: parameters not set"; return SCFGP_EARG; }
+    const Fail fail = {c, "predict_gradcov"};
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     const Geom& g0 = c->g;
     const int D = g0.D, q = std::min(g0.D, g0.S);
-    if (q > GRADCOV_MAX_Q) { c->err = "predict_gradcov: min(D, S) must be at most 64"; return SCFGP_EARG; }
+    if (q > GRADCOV_MAX_Q) return fail.arg("min(D, S) must be at most 64");
     double sw = (double)T;
     if (asub && w) {
-        sw = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-            if (!(w[t] >= 0.0) || !std::isfinite(w[t])) {
-                c->err = "predict_gradcov: weight " + std::to_string(t) + " is negative or not finite"; return SCFGP_EARG;
-            }
-            sw += w[t];
-        }
-        if (!(sw > 0.0)) { c->err = "predict_gradcov: the weights sum to zero"; return SCFGP_EARG; }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_bad() >= 0) return fail.arg("weight " + std::to_string(ws.first_bad()) + " is negative or not finite");
+        sw = ws.sum;
+        if (!(sw > 0.0)) return fail.arg("the weights sum to zero");
     }
     HIPCHK(c, hipSetDevice(c->device));
     if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/predict_gradcov_time.py)
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_grad(c, false))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     const bool feed_w = asub && w;
     const int xmode = mode == 1 ? c->xs_mode : 0;
     const int64_t DD = (int64_t)D * D;
-    const int64_t CH = gradcov_points(g0, dcov || asub), nchunks = (T + CH - 1) / CH, rows = std::min(T, CH);
+    const RowJobs jobs = {Xs, feed_w ? w : nullptr, T, gradcov_points(g0, dcov || asub)};
+    const int64_t nchunks = jobs.count(), rows = std::min(T, jobs.CH);
     const int64_t slot_len = rows * D * 2 + (dcov ? rows * DD : 0);
     RowFeed feed; OutRing ring; DevTmp qt, gfac, stage, rec, acc;  // Li / two chunks of [Xs | w] | Q | g_t | two slots | records | sums
     if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
@@ -2495,30 +2490,28 @@ extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, 
     if (xmode && (rc = dmalloc(c, &gfac.p, sizeof(double) * rows * D))) return rc;
     if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
     if (asub && ((rc = dmalloc(c, &rec.p, sizeof(double) * rows * DD)) || (rc = dmalloc(c, &acc.p, sizeof(double) * DD)))) return rc;
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
     DISPATCH(c, grad_operand, c);
     DISPATCH(c, gradcov_basis, c, qt.p);
     if (asub) HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * DD, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     if ((rc = ring.open(c))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(CH, T - i * CH); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * CH * D, feed_w ? w + i * CH : nullptr, rows_of(i)); };
     auto slot_dmu = [&](int64_t i) { return stage + (i & 1) * slot_len; };
     auto slot_dvar = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * D; };
     auto slot_dcov = [&](int64_t i) { return stage + (i & 1) * slot_len + 2 * rows * D; };
     auto download = [&](int64_t i) {
         return ring.drain(i, [&]() -> int {
-            const int64_t t0 = i * CH, n = rows_of(i);
+            const int64_t t0 = jobs.row0(i), n = jobs.rows(i);
             if (dmu) HIPCHK(c, hipMemcpyAsync(dmu + t0 * D, slot_dmu(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
             if (dvar) HIPCHK(c, hipMemcpyAsync(dvar + t0 * D, slot_dvar(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
             if (dcov) HIPCHK(c, hipMemcpyAsync(dcov + t0 * DD, slot_dcov(i), sizeof(double) * n * DD, hipMemcpyDeviceToHost, c->copy_st));
             return SCFGP_OK;
         });
     };
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wi;
         if ((rc = feed.acquire(i, &x, &wi))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
@@ -2529,7 +2522,7 @@ extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, 
             return rc;
         if ((rc = feed.release(i))) return rc;
         if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
         if (i >= 1 && (rc = download(i - 1))) return rc;
     }
     if ((rc = download(nchunks - 1))) return rc;
@@ -2576,33 +2569,29 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
             seen[dims[a]] = 1;
         }
     }
-    if (mode == 1 && !c->d_xscale) { c->err = "predict_pd: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "predict_pd: parameters not set"; return SCFGP_EARG; }
+    const Fail fail = {c, "predict_pd"};
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     double W = (double)T;
     if (w) {
-        bool nonfinite = false, positive = false;
-        W = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-            if (w[t] < 0.0) { c->err = "predict_pd: negative weight at row " + std::to_string(t); return SCFGP_EARG; }
-            if (!std::isfinite(w[t])) nonfinite = true;
-            else if (w[t] > 0.0) positive = true;
-            W += w[t];
-        }
-        if (nonfinite || !std::isfinite(W)) { c->err = "predict_pd: non-finite weights"; return SCFGP_ENONFINITE; }
-        if (!positive) { c->err = "predict_pd: no row has a positive weight"; return SCFGP_EARG; }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        W = ws.sum;
+        if (ws.first_nonfinite >= 0 || !std::isfinite(W)) return fail.nonfinite("non-finite weights");
+        if (!ws.positive) return fail.arg("no row has a positive weight");
     }
     const int xmode = mode == 1 ? c->xs_mode : 0;
     const int64_t NG = (int64_t)ndim * G;
     if (!xmode)
         for (int64_t e = 0; e < NG; ++e)
-            if (!std::isfinite(grid[e])) { c->err = "predict_pd: non-finite grid value"; return SCFGP_ENONFINITE; }
+            if (!std::isfinite(grid[e])) return fail.nonfinite("non-finite grid value");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/pd_time.py)
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     const bool curves = pd || pd_sd || pd_cov;
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = (T + PRED_ROWS - 1) / PRED_ROWS, Jp2 = 2 * (int64_t)g0.Jp;
+    const RowJobs jobs = {Xs, w, T, PRED_ROWS}, rows_only = {Xs, nullptr, T, PRED_ROWS};      // pass 1 | pass 2
+    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count(), Jp2 = 2 * (int64_t)g0.Jp;
     const int Gp = pd_grid_rows(G);
     DevTmp d_dims, d_grid, wchunk;                                // dims | the (transformed) grid | w of the chunk, padded
     if ((rc = dmalloc(c, &d_dims.p, sizeof(int) * ndim))) return rc;
@@ -2622,10 +2611,9 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
     }
     RowFeed feed;                                                 // Li / two chunks of [Xs | w], for both passes
     if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, pad_square, c->d_T1, c->d_AbarT, c->p_Li, alpha, c->alpha_pred()))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
     std::vector<double> h_pd, h_sd;
     if (curves) {
         // ---- pass 1: the running sums, ndim x 2 x Jp ----
@@ -2638,17 +2626,16 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
         if ((rc = dmalloc(c, &flag.p, sizeof(int) * 4))) return rc;
         HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * ndim * Jp2, c->st));
         HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int) * 4, c->st));
-        auto upload = [&](int64_t i) { return feed.upload(i, Xs + i * PRED_ROWS * D, w ? w + i * PRED_ROWS : nullptr, rows_of(i)); };
-        if ((rc = upload(0))) return rc;
+        if ((rc = feed.upload(0, jobs))) return rc;
         for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, rows_of(i));
+            const Geom g = chunk_geom(g0, jobs.rows(i));
             const double *x, *wraw;
             if ((rc = feed.acquire(i, &x, &wraw))) return rc;
             pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, wchunk.p, c->st, xmode, c->d_xscale);
             if ((rc = feed.release(i))) return rc;
             for (int a0 = 0; a0 < ndim; a0 += ngs)
                 if ((rc = DISPATCH(c, pd_sums_chunk, c, g, wchunk.p, dv + a0, std::min(ngs, ndim - a0), rec.p, acc + a0 * Jp2))) return rc;
-            if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+            if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
         }
         update_check_finite(acc, ndim * Jp2, (int*)flag.p, c->st);
         int hflag[4];
@@ -2708,20 +2695,19 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
         if ((rc = dmalloc(c, &R.p, c->tsize() * sample_w_rows(g0.K) * sample_w_cols(G)))) return rc;
         if ((rc = dmalloc(c, &keep.p, sizeof(double) * PRED_ROWS))) return rc;
         if ((rc = ring.open(c))) return rc;
-        auto upload = [&](int64_t i) { return feed.upload(j0 + i, Xs + i * PRED_ROWS * D, nullptr, rows_of(i)); };
         auto slot = [&](int64_t k) { return stage + (k & 1) * rows * G; };
         auto download = [&](int64_t k) {
             const int64_t i = k / ndim, a = k % ndim;
             return ring.drain(k, [&]() -> int {
-                HIPCHK(c, hipMemcpyAsync(ice + (a * T + i * PRED_ROWS) * G, slot(k), sizeof(double) * rows_of(i) * G, hipMemcpyDeviceToHost,
+                HIPCHK(c, hipMemcpyAsync(ice + (a * T + jobs.row0(i)) * G, slot(k), sizeof(double) * jobs.rows(i) * G, hipMemcpyDeviceToHost,
                                          c->copy_st));
                 return SCFGP_OK;
             });
         };
-        if ((rc = upload(0))) return rc;
+        if ((rc = feed.upload(0, rows_only, j0))) return rc;
         int64_t k = 0;
         for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, rows_of(i));
+            const Geom g = chunk_geom(g0, jobs.rows(i));
             const double* x;
             if ((rc = feed.acquire(j0 + i, &x))) return rc;
             pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
@@ -2730,7 +2716,7 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
                 if ((rc = ring.acquire(k))) return rc;
                 if ((rc = DISPATCH(c, pd_ice_chunk, c, g, dims[a], d_grid + (int64_t)a * G, G, R.p, keep.p, slot(k)))) return rc;
                 if ((rc = ring.computed(k))) return rc;
-                if (a == 0 && i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+                if (a == 0 && i + 1 < nchunks && (rc = feed.upload(i + 1, rows_only, j0))) return rc;
                 if (k >= 1 && (rc = download(k - 1))) return rc;
             }
         }
@@ -2761,32 +2747,26 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     if (!Xc || !Li || !idx || mode < 0 || mode > 1) { c->err = "select: bad arguments"; return SCFGP_EARG; }
     if (T < 1 || T > SELECT_MAX_T) { c->err = "select: T must lie in 1..1048576"; return SCFGP_EARG; }
     if (m < 1 || m > SELECT_MAX_M) { c->err = "select: m must lie in 1..4096"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "select: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "select: parameters not set"; return SCFGP_EARG; }
-    if (c->g.Kp > SELECT_MAX_KP) { c->err = "select: K above 8192 is not supported"; return SCFGP_EARG; }
+    const Fail fail = {c, "select"};
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
+    if (c->g.Kp > SELECT_MAX_KP) return fail.arg("K above 8192 is not supported");
     int64_t eligible = T;
     if (w) {
-        bool nonfinite = false;
-        eligible = 0;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "select: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) ++eligible;
-        }
-        if (nonfinite) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) return fail.nonfinite("non-finite rows, weights or factors");
+        eligible = ws.positive;
     }
-    if (m > eligible) {
-        c->err = "select: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
-        return SCFGP_EARG;
-    }
+    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp;
     const size_t ts = c->tsize();
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
+    const RowJobs jobs = {Xc, nullptr, T, PRED_ROWS};
+    const int64_t nchunks = jobs.count();
     // the last chunk's product writes whole 256-row blocks
-    const int64_t Crows = (nchunks - 1) * PRED_ROWS + round_up(T - (nchunks - 1) * PRED_ROWS, 256);
-    int rc;
+    const int64_t Crows = jobs.row0(nchunks - 1) + round_up(jobs.rows(nchunks - 1), 256);
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     RowFeed feed; DevTmp Cbuf, rows, picks;                       // Li / two chunks of X | C | w, d, std, partials | U, cp, a, part, idx, var, gain, flag
@@ -2794,9 +2774,8 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
     if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
         (void)hipGetLastError();
-        c->err = "select: no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
-                 std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)";
-        return SCFGP_EHIP;
+        return fail.set("no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
+                        std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)", SCFGP_EHIP);
     }
     const int npart = select_partials(T), nlchunk = (m + 63) / 64;
     const int64_t npp = round_up(npart, 8), mp = round_up(m, 8);
@@ -2811,21 +2790,19 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
     HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
     if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
     else select_ones(b.w, T, c->st);
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, update_load_factor, true, nullptr, &LiT))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     if ((rc = sd_done.create(c))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xc + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
-    if ((rc = upload(0))) return rc;
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, (char*)Cbuf.p + ts * (size_t)(i * PRED_ROWS) * Kp))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, (char*)Cbuf.p + ts * (size_t)jobs.row0(i) * Kp))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
     }
     DISPATCH(c, pick_init, c, b, Cbuf.p);
     HIPCHK(c, hipGetLastError());
@@ -2871,43 +2848,38 @@ extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const 
     if (T < 1 || T > SELECT_MAX_T) { c->err = "select_iv: T must lie in 1..1048576"; return SCFGP_EARG; }
     if (m < 1 || m > SELECT_MAX_M) { c->err = "select_iv: m must lie in 1..4096"; return SCFGP_EARG; }
     if (Xr && R < 1) { c->err = "select_iv: R must be at least 1"; return SCFGP_EARG; }
-    if (mode == 1 && !c->d_xscale) { c->err = "select_iv: no X scaler set"; return SCFGP_EARG; }
-    if (!c->have_params) { c->err = "select_iv: parameters not set"; return SCFGP_EARG; }
-    if (c->g.Kp > SELECT_IV_MAX_KP) { c->err = "select_iv: K above 4096 is not supported"; return SCFGP_EARG; }
+    const Fail fail = {c, "select_iv"};
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
+    if (c->g.Kp > SELECT_IV_MAX_KP) return fail.arg("K above 4096 is not supported");
     const int64_t Rn = Xr ? R : T;
     bool nonfinite = false;
     int64_t eligible = T;
     if (w) {
-        eligible = 0;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "select_iv: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) ++eligible;
-        }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) nonfinite = true;
+        eligible = ws.positive;
     }
     if (wr) {
-        bool positive = false;
-        for (int64_t i = 0; i < Rn; ++i) {
-            if (wr[i] < 0.0) { c->err = "select_iv: negative reference weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(wr[i])) nonfinite = true;
-            else if (wr[i] > 0.0) positive = true;
-        }
-        if (!nonfinite && !positive) { c->err = "select_iv: no reference row has a positive weight"; return SCFGP_EARG; }
+        const WeightScan ws = scan_weights(wr, Rn);
+        if (ws.first_negative >= 0) return fail.arg("negative reference weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) nonfinite = true;
+        if (!nonfinite && !ws.positive) return fail.arg("no reference row has a positive weight");
     }
-    if (nonfinite) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    if (m > eligible) {
-        c->err = "select_iv: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
-        return SCFGP_EARG;
-    }
+    if (nonfinite) return fail.nonfinite("non-finite rows, weights or factors");
+    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp, K2 = Kp * Kp;
     const size_t ts = c->tsize();
-    const int64_t npool = (T + PRED_ROWS - 1) / PRED_ROWS, nref = Xr ? (R + PRED_ROWS - 1) / PRED_ROWS : 0, njobs = nref + npool;
+    // jobs 0 .. nref - 1: the chunks of the reference rows (their weights as targets); then the pool's, which carry wr where the pool is
+    // its own reference
+    const RowJobs ref = {Xr, wr, Xr ? R : 0, PRED_ROWS}, pool = {Xc, Xr ? nullptr : wr, T, PRED_ROWS};
+    const int64_t npool = pool.count(), nref = ref.count(), njobs = nref + npool;
     const int64_t nqchunks = (Rn + PRED_ROWS - 1) / PRED_ROWS;
     // the last chunk's product writes whole 256-row blocks
-    const int64_t Crows = (npool - 1) * PRED_ROWS + round_up(T - (npool - 1) * PRED_ROWS, 256);
-    int rc;
+    const int64_t Crows = pool.row0(npool - 1) + round_up(pool.rows(npool - 1), 256);
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     const int nts = (int)(Kp / g0.tile), ntiles = nts * (nts + 1) / 2;
@@ -2922,9 +2894,8 @@ extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const 
     if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
     if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
         (void)hipGetLastError();
-        c->err = "select_iv: no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
-                 std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)";
-        return SCFGP_EHIP;
+        return fail.set("no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
+                        std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)", SCFGP_EHIP);
     }
     if ((rc = dmalloc(c, &Qbuf.p, (sizeof(double) + ts) * K2))) return rc;
     const int npart = select_partials(T), nlchunk = (m + 63) / 64;
@@ -2944,23 +2915,15 @@ extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const 
     HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
     if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
     else select_ones(b.w, T, c->st);
-    const void* LiT = c->d_AbarT;                                 // AbarT is scratch outside adjoint..pass3
-    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->d_T1, c->d_AbarT, c->p_Li))) return rc;
+    const void* LiT;
+    if ((rc = load_factor(c, feed, Li, update_load_factor, true, nullptr, &LiT))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
     if ((rc = sd_done.create(c))) return rc;
-    // jobs 0 .. nref - 1: the chunks of the reference rows; then the pool's
-    auto rows_of = [&](int64_t job) {
-        return job < nref ? std::min<int64_t>(PRED_ROWS, R - job * PRED_ROWS) : std::min<int64_t>(PRED_ROWS, T - (job - nref) * PRED_ROWS);
-    };
-    auto upload = [&](int64_t job) {
-        if (job < nref) return feed.upload(job, Xr + job * PRED_ROWS * g0.D, wr ? wr + job * PRED_ROWS : nullptr, rows_of(job));
-        const int64_t i = job - nref;
-        return feed.upload(job, Xc + i * PRED_ROWS * g0.D, !Xr && wr ? wr + i * PRED_ROWS : nullptr, rows_of(job));
-    };
+    auto upload = [&](int64_t job) { return job < nref ? feed.upload(job, ref) : feed.upload(job - nref, pool, nref); };
     if ((rc = upload(0))) return rc;
     int64_t nq = 0;                                               // chunks summed into Q so far
     for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, rows_of(job));
+        const Geom g = chunk_geom(g0, job < nref ? ref.rows(job) : pool.rows(job - nref));
         const bool in_q = job < nref || !Xr, weighted = in_q && wr;
         const double *x, *om;
         if ((rc = feed.acquire(job, &x, &om))) return rc;
@@ -3019,35 +2982,29 @@ extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const
                                 const double* Li, int nsamp, uint64_t seed, double best, double xi, int m, int mode, int minimize,
                                 int64_t* idx, double* gain, double* score0, double* mstate, double* qei) {
     if (!c) return SCFGP_EARG;
-    auto bad = [&](const char* what) { c->err = std::string("select_qei: ") + what; return SCFGP_EARG; };
-    if (!Xc || !alpha || !Li || !idx) return bad("NULL Xc, alpha, Li or idx");
-    if (T < 1 || T > SELECT_MAX_T) return bad("T must lie in 1..1048576");
-    if (m < 1 || m > SELECT_MAX_M) return bad("m must lie in 1..4096");
-    if (nsamp < 1 || nsamp > SAMPLE_MAX) return bad("nsamp must lie in 1..1024");
-    if (mode < 0 || mode > 1) return bad("mode must be 0 or 1 (there is no raw-y mode)");
-    if (np < 0) return bad("np must not be negative");
-    if (np > 0 && !Xp) return bad("np > 0 with NULL Xp");
-    if (mode == 1 && !c->d_xscale) return bad("no X scaler set");
-    if (!c->have_params) return bad("parameters not set");
+    const Fail fail = {c, "select_qei"};
+    if (!Xc || !alpha || !Li || !idx) return fail.arg("NULL Xc, alpha, Li or idx");
+    if (T < 1 || T > SELECT_MAX_T) return fail.arg("T must lie in 1..1048576");
+    if (m < 1 || m > SELECT_MAX_M) return fail.arg("m must lie in 1..4096");
+    if (nsamp < 1 || nsamp > SAMPLE_MAX) return fail.arg("nsamp must lie in 1..1024");
+    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
+    if (np < 0) return fail.arg("np must not be negative");
+    if (np > 0 && !Xp) return fail.arg("np > 0 with NULL Xp");
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
     bool nonfinite = !std::isfinite(best) || !std::isfinite(xi);
-    if (!nonfinite && xi < 0.0) return bad("xi must not be negative");
+    if (!nonfinite && xi < 0.0) return fail.arg("xi must not be negative");
     int64_t eligible = T;
     if (w) {
-        eligible = 0;
-        for (int64_t i = 0; i < T; ++i) {
-            if (w[i] < 0.0) { c->err = "select_qei: negative weight at row " + std::to_string(i); return SCFGP_EARG; }
-            if (!std::isfinite(w[i])) nonfinite = true;
-            else if (w[i] > 0.0) ++eligible;
-        }
+        const WeightScan ws = scan_weights(w, T);
+        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
+        if (ws.first_nonfinite >= 0) nonfinite = true;
+        eligible = ws.positive;
     }
-    if (nonfinite) { c->err = "select_qei: non-finite best, xi or weights"; return SCFGP_ENONFINITE; }
-    if (m > eligible) {
-        c->err = "select_qei: m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight";
-        return SCFGP_EARG;
-    }
+    if (nonfinite) return fail.nonfinite("non-finite best, xi or weights");
+    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g0 = c->g;
-    int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     SampleW sw;
     if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
@@ -3055,9 +3012,8 @@ extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const
     if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
     if (hipMalloc((void**)&Fbuf.p, sizeof(double) * T * nsamp) != hipSuccess) {
         (void)hipGetLastError();
-        c->err = "select_qei: no device memory for the pool's samples (" + std::to_string(T) + " x " + std::to_string(nsamp) + " x 8 = " +
-                 std::to_string((unsigned long long)(sizeof(double) * T * nsamp)) + " bytes)";
-        return SCFGP_EHIP;
+        return fail.set("no device memory for the pool's samples (" + std::to_string(T) + " x " + std::to_string(nsamp) + " x 8 = " +
+                        std::to_string((unsigned long long)(sizeof(double) * T * nsamp)) + " bytes)", SCFGP_EHIP);
     }
     const int64_t nblk = selectqei_blocks(T), mp = round_up(m, 8);
     if ((rc = dmalloc(c, &state.p, sizeof(double) * (2 * T + nsamp + 2 * nblk + 2 * mp + 3)))) return rc;
@@ -3070,26 +3026,25 @@ extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const
     else select_ones(b.w, T, c->st);
     SampleArgmaxRun pend;                                         // the pending rows: every one of them is eligible
     if (np > 0 && (rc = sample_argmax_run(c, Xp, np, nullptr, sw.wt.p, nsamp, mode == 1, minimize, pend))) return rc;
-    auto rows_of = [&](int64_t i) { return std::min<int64_t>(PRED_ROWS, T - i * PRED_ROWS); };
-    auto upload = [&](int64_t i) { return feed.upload(i, Xc + i * PRED_ROWS * g0.D, nullptr, rows_of(i)); };
-    const int64_t nchunks = (T + PRED_ROWS - 1) / PRED_ROWS;
-    if ((rc = upload(0))) return rc;
+    const RowJobs jobs = {Xc, nullptr, T, PRED_ROWS};
+    const int64_t nchunks = jobs.count();
+    if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, rows_of(i));
+        const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
         pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, i * PRED_ROWS, seed, 0, -1, Fbuf + i * PRED_ROWS * nsamp))) return rc;
-        if (i + 1 < nchunks && (rc = upload(i + 1))) return rc;
+        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, 0, -1, Fbuf + jobs.row0(i) * nsamp))) return rc;
+        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
     }
     const double base = b.sgn * best + xi;
-    selectqei_state(b, np > 0 ? pend.bestv : nullptr, base, 1, c->st);
+    selectqei_state(b, np > 0 ? pend.best.v() : nullptr, base, 1, c->st);
     selectqei_sweep(b, 0, c->st);
     HIPCHK(c, hipGetLastError());
     int flags[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(&flags[0], b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    if (np > 0) HIPCHK(c, hipMemcpyAsync(&flags[1], pend.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    if (np > 0) HIPCHK(c, hipMemcpyAsync(&flags[1], pend.best.flag(), sizeof(int), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->copy_st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (flags[0] || flags[1]) { c->err = "select_qei: a non-finite sampled value at an eligible or pending row"; return SCFGP_ENONFINITE; }
