@@ -2,9 +2,10 @@
 Stale-state sequences across the posterior entry points (not a test, not a conftest: the helper of tests/test_posterior_sequence_ref.py
 and tests/test_gpu_posterior_sequence.py).
 
-One context lives through a seeded schedule of calls: the fifteen posterior entry points added after tests/test_gpu_round3.py's sequence
+One context lives through a seeded schedule of calls: the eighteen posterior entry points added after tests/test_gpu_round3.py's sequence
 test was written (predict_raw, predict_y, predict_grad, sample, sample_weights, sample_argmax, sample_grad, acquire, predict_cov,
-condition, forget, loo, select, select_iv, select_qei) and predict, in the modes their registered scalers allow, with set_params,
+condition, forget, loo, select, select_iv, select_qei, predict_gradcov, predict_pd, acquire_kg) and predict, in the modes their
+registered scalers allow, with set_params,
 scaler changes, the training calls of that test and documented failing calls between them.  Every posterior step is checked
 
   (a) bit for bit against a TWIN: a fresh context with the same parameters, scalers, options and resident rows that makes the same call
@@ -24,9 +25,15 @@ a y-mode step follows a raw-mode step on the same rows and is checked, as the ow
 DEVICE's raw-mode outputs of that step with those tests' tolerances.
 
 The geometry sweep (SWEEP_GEOMETRIES, sweep_schedule; the helper of tests/test_posterior_geometry_ref.py and
-tests/test_gpu_posterior_geometry.py) uses the same runner, references and records on a lean schedule per geometry, scfgp_acquire_kg
-included (it joins that schedule only), with two further checks: (c) a call on row 0 alone against row 0 of the 257-row call, bit for
-bit, and (d) an f16x3 context against the f32 context, bit for bit.
+tests/test_gpu_posterior_geometry.py) uses the same runner, references and records on a lean schedule per geometry (scfgp_acquire_kg
+was once in that schedule only; it now lives through the sequences too), with two further checks: (c) a call on row 0 alone against
+row 0 of the 257-row call, bit for bit, and (d) an f16x3 context against the f32 context, bit for bit.
+
+Input conditions.  Some checks are fair only for inputs that are not a cancellation or near-degenerate: kg_conditioning (acquire_kg),
+pd_cancellation (predict_pd's sums), conditioned_row0 and acquire_grad_cancellation
+(steps on row 0 alone).  They are computed from the fp64 references alone and never change a bound.  The sweep meets them through the
+salt of a group's seed; a sequence, whose fit is known only once its schedule has run so far, repeats the draw of such a step at run time
+until the condition holds (materialise).  Both CPU tiers assert every one of them.
 """
 import functools
 
@@ -36,7 +43,9 @@ from oracle import scfgp_oracle as O
 from scfgp_amd.scaler import Scaler
 from tests import acquire_ref as A
 from tests import condition_ref, forget_ref, loo_ref, parity, pred_cov_ref
+from tests import gradcov_ref as GC
 from tests import kg_ref as KG
+from tests import pd_ref as PD
 from tests import pred_grad_ref as G
 from tests import sample_argmax_ref as AM
 from tests import sample_grad_ref as SG
@@ -49,6 +58,8 @@ from tests import test_gpu_acquire as T_ACQ
 from tests import test_gpu_acquire_kg as T_KG
 from tests import test_gpu_predict_cov as T_COV
 from tests import test_gpu_predict_grad as T_PG
+from tests import test_gpu_predict_gradcov as T_GC
+from tests import test_gpu_predict_pd as T_PD
 from tests import test_gpu_round3 as T_R3
 from tests import test_gpu_sample as T_SMP
 from tests import test_gpu_sample_grad as T_SG
@@ -61,15 +72,30 @@ DTYPES = ('f64', 'f32')
 CASES = [(g, dt) for g in GEOMETRIES for dt in DTYPES]
 SIZES = (1, 37, 255, 256, 257, 700, 3000)                                # either side of the 256-row padding
 BIG = (32768, 32769, 65536 + 300)                                        # one chunk exactly, two chunks, three (both halves reused)
-# scripted big visits per geometry, at entry points whose CPU reference is affordable at that size
-BIG_VISITS = {0: (('condition', BIG[0]), ('sample_argmax', BIG[2])), 1: (('acquire', BIG[1]), ('predict_raw', BIG[0])),
+def gradcov_points_per_chunk(D, S, want_cov):
+    """include/scfgp_hip.h's np of scfgp_predict_gradcov restated: whole groups of 64 / q points (q = min(D, S)) in the 32 768-row
+    buffers and, where a D x D array per point is wanted (dcov, asub), at most a 64 MiB slot of them"""
+    q = min(D, S)
+    gs = (64 // q) * q
+    n = (32768 // gs) * (64 // q)
+    return min(n, max(1, (64 << 20) // (8 * D * D))) if want_cov else n
+
+
+# scripted big visits per geometry, at entry points whose CPU reference is affordable at that size; predict_gradcov at three of its own
+# chunks (the chunk of geometry 1 with a D x D array per point), predict_pd at three row chunks
+BIG_GRADCOV = 2 * gradcov_points_per_chunk(5, 4, True) + 300
+BIG_VISITS = {0: (('condition', BIG[0]), ('sample_argmax', BIG[2]), ('predict_pd', BIG[2])),
+              1: (('acquire', BIG[1]), ('predict_raw', BIG[0]), ('predict_gradcov', BIG_GRADCOV)),
               2: (('sample', BIG[2]),), 3: (('predict_grad', BIG[1]),)}
 POSTERIOR = ('predict_raw', 'predict_y', 'predict_grad', 'sample', 'sample_weights', 'sample_argmax', 'sample_grad', 'acquire',
-             'predict_cov', 'condition', 'forget', 'loo', 'select', 'select_iv', 'select_qei')
+             'predict_cov', 'condition', 'forget', 'loo', 'select', 'select_iv', 'select_qei', 'predict_gradcov', 'predict_pd', 'acquire_kg')
 # the first posterior call of case i: ensure_pred_factor, ensure_update, ensure_loo and ensure_forget are each reached first somewhere
 FIRST = ('predict_grad', 'condition', 'loo', 'forget', 'select_iv', 'predict_cov', 'acquire', 'sample')
 Y_MODE = ('predict_grad', 'sample', 'sample_argmax', 'sample_grad')      # entry points with a raw-y mode (predict_y is one by itself)
 NSAMP = (1, 7, 300)
+GRID = (1, 9, 64)                                                        # grid values per dimension of a predict_pd step
+KG_REFS = (0, 37)                                                        # reference rows of an acquire_kg step (0: the candidates themselves)
+KG_NODES = (None, 3, 17)                                                 # its nodes: the default set, or tests/test_gpu_acquire_kg.py's NODES
 PICKS = (1, 5, 40)
 OPTIONS = [('gram64', (0, 2, 3)), ('factor_form', (-1, 1)), ('lowrank_bwd', (-1, 0, 1)), ('gram_nsplit', (0, 3)), ('gram_taper', (0, 1)),
            ('apply_dma', (-1, 0, 1, 2))]                                 # those of the round-3 sequence test
@@ -91,9 +117,9 @@ def kappa(params):
 CONST_COL = 1                                                            # a constant raw column: every X scaler drops it
 
 
-def raw_rows(rng, n, D):
-    """(n, D + 1) positive raw rows, column CONST_COL constant"""
-    X = np.exp(0.5 * rng.standard_normal((n, D)))
+def raw_rows(rng, n, D, spread=1.0):
+    """(n, D + 1) positive raw rows, column CONST_COL constant (spread < 1: a narrower pool around the same centre)"""
+    X = np.exp(0.5 * spread * rng.standard_normal((n, D)))
     return np.ascontiguousarray(np.insert(X, CONST_COL, 2.5, axis=1))
 
 
@@ -295,6 +321,106 @@ class RefEngine(object):
             mu, sd = y_tail(self.ys, mu, sd); sd = sd.ravel()
         return mu, sd, dmu, (dsd if want_std else None)
 
+    def gradcov_points_per_chunk(self, want_cov):
+        return gradcov_points_per_chunk(self.D, self.S, want_cov)
+
+    def predict_gradcov(self, Xs, alpha, Li, w=None, mode='scaled', want=('dmu', 'dvar', 'asub')):
+        """tests/gradcov_ref.py's dense closed form, 256 rows at a time (the T x K x D Jacobian of a long call does not fit); raw mode
+        chained as g o m and diag(g) Sigma diag(g).  dmu is this engine's predict_grad's (the header's promise 1); Sigma_t and asub are
+        made symmetric, which the closed form's products are up to their last bits."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if mode not in ('scaled', 'raw') or not want or any(k not in T_GC.ALL for k in want):
+            raise ValueError('predict_gradcov: bad mode or want')
+        X, J, cols, width = self._rows(Xs, mode)
+        T, D = X.shape
+        wv = np.ones(T)
+        if 'asub' in want and w is not None:
+            wv = np.asarray(w, np.float64).reshape(-1)
+            if wv.size != T or not np.all(np.isfinite(wv)) or np.any(wv < 0) or not wv.sum() > 0:
+                raise ValueError('predict_gradcov: a negative or non-finite weight, or weights that sum to zero')
+        dv = np.empty((T, D)); dc = np.empty((T, D, D)) if 'dcov' in want else None; acc = np.zeros((D, D))
+        if set(want) - {'dmu'}:
+            with np.errstate(all='ignore'):
+                for t0 in range(0, T, 256):
+                    sl = slice(t0, min(T, t0 + 256))
+                    m, Sig = GC.gradcov(X[sl], alpha, Li, self.params, self.S, self.M, g=None if J is None else J[sl])
+                    Sig = 0.5 * (Sig + Sig.transpose(0, 2, 1))
+                    dv[sl] = np.diagonal(Sig, axis1=1, axis2=2)
+                    if dc is not None:
+                        dc[sl] = Sig
+                    if 'asub' in want:
+                        acc += np.einsum('t,tde->de', wv[sl], m[:, :, None] * m[:, None, :] + Sig)
+
+        def wide(a, matrix=False):
+            if cols is None:
+                return a
+            o = np.zeros(a.shape[:-1] + (width,)); o[..., cols] = a
+            if matrix:                                                       # rows of the matrices too
+                b = np.zeros(o.shape[:-2] + (width, width)); b[..., cols, :] = o
+                o = b
+            return o
+
+        out = {}
+        if 'dmu' in want:
+            out['dmu'] = self.predict_grad(Xs, alpha, Li, mode=mode, want_std=False)[2]
+        if 'dvar' in want:
+            out['dvar'] = wide(dv)
+        if 'dcov' in want:
+            out['dcov'] = wide(dc, True)
+        if 'asub' in want:
+            A_ = acc / wv.sum()
+            out['asub'] = wide(0.5 * (A_ + A_.T), True)
+        return out
+
+    def pd_scaled(self, Xs, dims, grid, mode):
+        """the arguments of predict_pd in scaled units: (rows, dims as scaled columns, grid); in raw mode every grid value goes through
+        the X scaler's forward transform of its own column, on the host"""
+        dims = [int(d) for d in np.asarray(dims).reshape(-1)]
+        grid = np.asarray(grid, np.float64)
+        if grid.ndim != 2 or grid.shape[0] != len(dims) or len(set(dims)) != len(dims):
+            raise ValueError('predict_pd: grid must be (ndim, G) with one row per distinct entry of dims')
+        X = self._rows(Xs, mode)[0]
+        if mode == 'scaled':
+            if any(not 0 <= d < X.shape[1] for d in dims):
+                raise ValueError('predict_pd: dimension out of range')
+            return X, dims, grid
+        Xr = np.asarray(Xs, np.float64)
+        kept = list(self.xs.data['cols'])
+        if any(d not in kept for d in dims):
+            raise ValueError('predict_pd: dims names a column that the X scaler dropped or that does not exist')
+        fin = np.flatnonzero(np.isfinite(Xr).all(axis=1))
+        base = Xr[fin[0]] if fin.size else np.ones(Xr.shape[1])
+        out = np.empty_like(grid)
+        with np.errstate(all='ignore'):
+            for a, cc in enumerate(dims):
+                fake = np.repeat(base[None, :], grid.shape[1], 0); fake[:, cc] = grid[a]
+                out[a] = self.xs.forward_transform(fake)[:, kept.index(cc)]
+        return X, [kept.index(d) for d in dims], out
+
+    def predict_pd(self, Xs, alpha, Li, dims, grid, w=None, mode='scaled', want=('pd', 'sd')):
+        """tests/pd_ref.py's closed form (pinned to its brute force by tests/test_pd_ref.py); cov is made symmetric, which the closed
+        form's product is up to its last bits"""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if mode not in ('scaled', 'raw') or not want or any(k not in T_PD.ALL for k in want):
+            raise ValueError('predict_pd: bad mode or want')
+        X, dims, grid = self.pd_scaled(Xs, dims, grid, mode)
+        live = np.ones(len(X), bool)
+        if w is not None:
+            w = np.asarray(w, np.float64).reshape(-1)
+            if w.size != len(X) or np.any(w < 0) or (np.all(np.isfinite(w)) and not np.any(w > 0)):
+                raise ValueError('predict_pd: a negative weight, or no row of positive weight')
+            if not np.all(np.isfinite(w)):
+                raise FloatingPointError('predict_pd: non-finite weights')
+            live = w > 0
+        if not _finite(grid):
+            raise FloatingPointError('predict_pd: non-finite grid')
+        if set(want) - {'ice'} and not _finite(X[live]):
+            raise FloatingPointError('predict_pd: non-finite weighted sum of the features')
+        with np.errstate(all='ignore'):
+            pd, sd, cov, ice, _ = PD.closed(X, w, alpha, Li, self.params, self.S, self.M, dims, grid, want_ice='ice' in want)
+        out = dict(pd=pd, sd=sd, cov=0.5 * (cov + cov.transpose(0, 2, 1)), ice=ice)
+        return {k: out[k] for k in T_PD.ALL if k in want}
+
     # samples
     def sample_weights(self, alpha, Li, nsamp, seed=0):
         return SR.weights(alpha, Li, kappa(self.params), nsamp, seed)
@@ -430,6 +556,10 @@ class RefEngine(object):
 
 
 # ---- schedules -------------------------------------------------------------------------------------------------------------------------
+OLD_POSTERIOR = POSTERIOR[:15]                                           # the entry points the sequences held before the last three joined
+NEWEST = POSTERIOR[15:]
+
+
 def _posterior_block(ep, rng, T=None):
     """one posterior step, or a raw-mode step and the y-mode step that is checked against it"""
     st = dict(op='post', ep=ep, T=int(rng.choice(SIZES)) if T is None else int(T), seed=int(rng.integers(1, 2 ** 31)), u=float(rng.random()))
@@ -449,6 +579,23 @@ def _posterior_block(ep, rng, T=None):
     return [st]
 
 
+def _newest_block(ep, rng, T=None):
+    """one step of predict_gradcov, predict_pd or acquire_kg: _posterior_block's draw from the generator of the new blocks, and the
+    options of these three.  predict_gradcov, predict_pd: weights by `mask`, all four outputs or the two cheap ones by `flag`; predict_pd's
+    grid and dimensions.  acquire_kg: reference rows and nodes; the candidates are their own reference set up to 700 rows only (the
+    reference's node table is T x R per node).  `new` marks the steps that were not in the schedules before these three joined; `redraw`
+    those whose draw is repeated at run time until their input condition holds (materialise)."""
+    st = _posterior_block(ep, rng, T)[0]
+    st['G'] = int(rng.choice(GRID)); st['pdims'] = str(rng.choice(['all', 'one']))
+    st['R'] = int(rng.choice(KG_REFS)); st['nodes'] = KG_NODES[int(rng.integers(len(KG_NODES)))]
+    if st['R'] == 0 and st['T'] > 700:
+        st['R'] = KG_REFS[1]
+    st['new'] = True
+    if ep in ('acquire_kg', 'predict_pd'):
+        st['redraw'] = True
+    return [st]
+
+
 def _failing_blocks(rng):
     """documented error returns, each followed directly by a valid call of another entry point that shares its buffers"""
     seed = lambda: int(rng.integers(1, 2 ** 31))
@@ -463,16 +610,39 @@ def _failing_blocks(rng):
     ]
 
 
+def _newest_failing_blocks(rng):
+    """the same for predict_gradcov and predict_pd, from the generator of the new blocks"""
+    seed = lambda: int(rng.integers(1, 2 ** 31))
+    base = dict(op='post', mode='scaled', mask=False, minimize=False, noise=False, nsamp=7, m=5, block=7, flag=False, kind='ei', u=0.5,
+                G=9, pdims='all', R=37, nodes=None, new=True)
+    fail = lambda ep, err, T, **kw: dict(base, op='fail', ep=ep, err=err, T=T, seed=seed(), **kw)
+    ok = lambda ep, T, **kw: dict(base, ep=ep, T=T, seed=seed(), **kw)
+    return [
+        # weights that sum to 0, then the sibling block kernel
+        [fail('predict_gradcov', 'arg', 257, flag=True), ok('loo', 256)],
+        # a NaN in a row of positive weight, found on the device; then the product of the ICE block's shape
+        [fail('predict_pd', 'nonfinite', 700, flag=True), ok('sample', 255)],
+        # a NaN row is no error of predict_gradcov: it stays in that point's outputs (promise 2)
+        [ok('predict_gradcov', 255, nan_row=True, want=('dmu', 'dvar', 'dcov')), ok('predict_cov', 37)],
+    ]
+
+
 def _draw(ci, sub):
+    """The blocks of the fifteen older entry points, their order and the head are drawn exactly as before predict_gradcov, predict_pd
+    and acquire_kg joined (one generator, the same calls in the same order), so that every older step keeps its arguments, its seed and
+    its place among the older steps; none of the new steps moves the fit, so the older steps also see the fit they saw.  The new blocks
+    come from a second generator and are inserted into that order, behind the early y scaler and before the closing predict."""
     (D, S, M), dtype = CASES[ci]
     gi = GEOMETRIES.index((D, S, M))
     rng = np.random.default_rng([0x5EC, ci, sub])
     algos = list(Scaler.algos)
     blocks = []
-    for ep in POSTERIOR + ('predict',):
+    for ep in OLD_POSTERIOR + ('predict',):
         for _ in range(2):
             blocks.append(_posterior_block(ep, rng))
     for ep, T in BIG_VISITS[gi]:
+        if ep in NEWEST:
+            continue
         b = _posterior_block(ep, rng, T)[:1]
         b[0].update(nsamp=7, m=5, flag=ep == 'predict_grad', mode='raw' if ep == 'predict_raw' else 'scaled', pair=False)
         blocks.append(b)
@@ -500,6 +670,20 @@ def _draw(ci, sub):
         blocks[f['loo']], blocks[f['predict_cov']] = blocks[f['predict_cov']], blocks[f['loo']]
     head = [dict(op='xscaler', algo=algos[ci % 5]), dict(op='params', seed=int(rng.integers(1, 2 ** 31)), head=True),
             dict(op='data', seed=int(rng.integers(1, 2 ** 31)), N=3000, head=True)]
+    # the three newest entry points: twice each, their scripted big visits and their failing blocks, from a generator of their own
+    rng2 = np.random.default_rng([0x5ED, ci, sub])
+    fresh = []
+    for ep in NEWEST:
+        for _ in range(2):
+            fresh.append(_newest_block(ep, rng2))
+    for ep, T in BIG_VISITS[gi]:
+        if ep in NEWEST:
+            b = _newest_block(ep, rng2, T)
+            b[0].update(nsamp=7, m=5, flag=True, mode='scaled', G=5, pdims='all')      # every output; all D = 7 dimensions of predict_pd
+            fresh.append(b)
+    fresh += _newest_failing_blocks(rng2)
+    for b in fresh:
+        blocks.insert(int(rng2.integers(3, len(blocks))), b)
     return _resolve(head + [st for b in blocks for st in b], D)
 
 
@@ -563,12 +747,18 @@ def check_schedule(steps, ci):
         assert all(any(is_post[:i]) and any(is_post[i + 1:]) for i in at), (op, 'posterior calls before and after')
     fails = [(i, st) for i, st in enumerate(steps) if st['op'] == 'fail']
     assert len(fails) >= 3 and len({st['err'] for _, st in fails}) >= 2, fails
-    follow = {'forget': 'condition', 'loo': 'predict_grad', 'predict_cov': 'loo', 'sample_argmax': 'acquire'}
+    follow = {'forget': 'condition', 'loo': 'predict_grad', 'predict_cov': 'loo', 'sample_argmax': 'acquire', 'predict_gradcov': 'loo',
+              'predict_pd': 'sample'}
+    assert set(follow) == {st['ep'] for _, st in fails}
     for i, st in fails:
         nxt = steps[i + 1]
         assert nxt['op'] == 'post' and nxt['ep'] == follow[st['ep']], (st, nxt)
     i = next(i for i, st in fails if st['ep'] == 'sample_argmax')
     assert steps[i - 1]['ep'] == 'sample' and steps[i - 1].get('nan_row')          # a NaN row through `sample`, then the failing call
+    i = next(i for i, st in enumerate(steps) if st['op'] == 'post' and st['ep'] == 'predict_gradcov' and st.get('nan_row'))
+    assert 'asub' not in steps[i]['want'] and steps[i + 1]['op'] == 'post' and steps[i + 1]['ep'] == 'predict_cov'   # a NaN row that is no error
+    assert all(bool(st.get('redraw')) == (st['ep'] in ('acquire_kg', 'predict_pd')) for st in post)
+    assert all(bool(st.get('new')) == (st['ep'] in NEWEST) for st in post if st['ep'] in NEWEST + ('acquire', 'predict_raw', 'condition'))
     N = 0
     for st in steps:
         if st['op'] == 'data':
@@ -607,6 +797,8 @@ def check_all_schedules():
     for dt in DTYPES:
         seen = {st['T'] for (g, d), s in zip(CASES, scheds) if d == dt for st in s if st['op'] == 'post'}
         assert set(BIG) <= seen, (dt, sorted(seen))
+        big = {(st['ep'], st['T']) for (g, d), s in zip(CASES, scheds) if d == dt for st in s if st['op'] == 'post' and st['flag']}
+        assert {('predict_gradcov', BIG_GRADCOV), ('predict_pd', BIG[2])} <= big and BIG_GRADCOV == 16684, (dt, sorted(big))
     algos = {st['algo'] for s in scheds for st in s if st['op'] in ('xscaler', 'yscaler')}
     assert algos == set(Scaler.algos)
     return scheds
@@ -628,7 +820,9 @@ SWEEP_GEOMETRIES = [
     (33, 3, 158),     # K = 322: remainder of two 64-tiles, the second with 2 live columns
     (5, 4, 188),      # K = 384: 128-wide plan with no remainder launch; K = Kp
 ]
-SWEEP_ENTRY_POINTS = ('predict',) + POSTERIOR + ('acquire_kg',)          # all seventeen
+SWEEP_ENTRY_POINTS = ('predict',) + POSTERIOR                            # all nineteen
+SWEEP_OLD_GROUPS = (2, 40)                                               # first and last group of the seventeen older entry points
+SWEEP_GRID = (9, 1)                                                      # grid values of the two predict_pd groups
 SWEEP_T = (257, 1)                                                       # one row past the 256-row padding, and its row 0 alone
 SWEEP_N = 300                                                            # rows in the fit
 SWEEP_MOVED = (1, 37)                                                    # rows condition and forget move; R of acquire_kg; pending / Xb rows
@@ -640,18 +834,21 @@ SWEEP_MOVED = (1, 37)                                                    # rows 
 # a correct fp32 predict stands inside half its bound, and acquire's gradient terms do not cancel (acquire_grad_cancellation);
 # and the lines of an acquire_kg step on 257 rows are not near-parallel (kg_conditioning <= 1; at D = 1, K = 8 no draw of the step with
 # 37 reference rows meets it, and that step is exempt); tests/test_posterior_geometry_ref.py asserts all of it on the CPU references.  These are conditions on the choice of inputs, computed from the fp64 references alone, not tolerances.
+# The groups of predict_gradcov and predict_pd (41 to 44) are held to conditioned_row0 for dmu, dvar, dcov and ice, to pd_cancellation >=
+# PD_CANCEL, and to a correct fp32 evaluation of every one of their steps (row 0 alone included) inside half the fp32 bound; only the
+# first of the three ever turned a salt down.  No step of either entry point is exempt.
 # (D, S, M) -> {group number: salt}; every other group: 0
 _SALT = {
     (1, 2, 2): {0: 1, 5: 1, 6: 1, 15: 1, 16: 1, 18: 13, 19: 1, 21: 13, 24: 237, 34: 1, 35: 2},
     (7, 12, 3): {12: 1, 14: 2, 18: 2, 21: 6, 22: 9},
-    (70, 5, 60): {6: 3, 13: 1, 14: 1, 16: 2, 21: 2, 22: 1},
+    (70, 5, 60): {6: 3, 13: 1, 14: 1, 16: 2, 21: 2, 22: 1, 41: 1},
     (15, 15, 60): {18: 1, 19: 1, 21: 10, 22: 1},
-    (16, 16, 70): {12: 1, 14: 2, 16: 2, 19: 2, 21: 14, 22: 6, 24: 1},
-    (6, 5, 91): {4: 2, 6: 6, 14: 1, 15: 3, 16: 8, 17: 1, 20: 2, 21: 4},
-    (9, 8, 120): {14: 1, 15: 3, 16: 2, 21: 1, 35: 1},
-    (40, 6, 123): {10: 1, 12: 1, 13: 1, 14: 2, 18: 2, 21: 11, 22: 8, 35: 1},
-    (33, 3, 158): {4: 2, 5: 1, 6: 3, 10: 1, 14: 2, 15: 3, 16: 5, 18: 5, 19: 2, 20: 3, 21: 8, 22: 2},
-    (5, 4, 188): {4: 4, 6: 2, 16: 4, 17: 2, 20: 3, 21: 2},
+    (16, 16, 70): {12: 1, 14: 2, 16: 2, 19: 2, 21: 14, 22: 6, 24: 1, 44: 1},
+    (6, 5, 91): {4: 2, 6: 6, 14: 1, 15: 3, 16: 8, 17: 1, 20: 2, 21: 4, 41: 3, 42: 3},
+    (9, 8, 120): {14: 1, 15: 3, 16: 2, 21: 1, 35: 1, 42: 9},
+    (40, 6, 123): {10: 1, 12: 1, 13: 1, 14: 2, 18: 2, 21: 11, 22: 8, 35: 1, 42: 6, 43: 1},
+    (33, 3, 158): {4: 2, 5: 1, 6: 3, 10: 1, 14: 2, 15: 3, 16: 5, 18: 5, 19: 2, 20: 3, 21: 8, 22: 2, 41: 1, 42: 10},
+    (5, 4, 188): {4: 4, 6: 2, 16: 4, 17: 2, 20: 3, 21: 2, 41: 2, 42: 20},
 }
 SWEEP_SALT = {g + (n,): v for g, d in _SALT.items() for n, v in d.items()}
 ROW0_NORM = 0.5
@@ -709,6 +906,17 @@ def kg_conditioning(a, fit):
     return float(len(z) * 0.4 * 2.0 ** -53 * np.abs(KG.slopes(cov, sd)).max() / (T_KG.VALUE_BOUND * hi.max()))
 
 
+PD_CANCEL = 0.08
+
+
+def pd_cancellation(a, fit):
+    """tests/pd_ref.py's cancellation of a predict_pd step with sums: how much of a feature row's norm survives the weighted mean over
+    the step's rows.  A condition on the inputs, at least PD_CANCEL (the figure tests/test_pd_ref.py holds the own GPU tests' inputs to):
+    pd, sd and cov are bounded relative to their own norms, which is a fair check only where the mean row is no cancellation."""
+    X, dims, _ = _ref_engine(fit).pd_scaled(a['X'], a['dims'], a['grid'], a['mode'])
+    return PD.cancellation(X, a['w'], fit.params, fit.S, fit.M, dims)
+
+
 def geometry_classes(D, S, M):
     """the integer classes of a geometry, restated from ApplyPlan (apply.hip) and derive_geom: the column plan of the apply products
     (n128 tiles 128 wide, then n64 tiles 64 wide, `last` live columns in the last 64-wide tile), the padding of K (Kp, gfull, gstrip;
@@ -763,16 +971,18 @@ def classes_of(D, S, M):
 
 # (c) outputs of which include/scfgp_hip.h documents that a row's values depend on that row alone (not on T, the row's position or the
 # chunk): sample ("the same functions on any rows", eps by the row's index), sample_grad, acquire, acquire_kg with explicit reference
-# rows, predict_cov's element guarantee, loo for rows of the same block (block 1 here), select_qei's scores
+# rows, predict_cov's element guarantee, loo for rows of the same block (block 1 here), select_qei's scores, predict_gradcov's promise 2
+# (dvar, dcov; its dmu is predict_grad's, of which no such promise is made) and predict_pd's promise 5 (ice)
 ROW_ALONE = {'sample': ('out',), 'sample_grad': ('val', 'grad'), 'acquire': ('acq', 'mu', 'sd', 'grad'), 'acquire_kg': ('kg', 'kg_hi', 'm', 's'),
-             'predict_cov': ('cov',), 'loo': ('mu', 'sd', 'lev'), 'select_qei': ('score0',)}
+             'predict_cov': ('cov',), 'loo': ('mu', 'sd', 'lev'), 'select_qei': ('score0',), 'predict_gradcov': ('dvar', 'dcov'),
+             'predict_pd': ('ice',)}
 # (d) outputs of which the header says that SCFGP_F16X3 contexts agree with SCFGP_F32 bit for bit (forget: the fp64 first pass and K x K
 # stage, i.e. the factors; its mu / std come from predict's pass, for which nothing is claimed)
 F16X3_EQUAL = {'sample': ('out',), 'sample_argmax': ('idx', 'val'), 'sample_grad': ('val', 'grad'),
                'acquire': ('acq', 'idx', 'val', 'mu', 'sd', 'grad'), 'acquire_kg': T_KG.ALL, 'predict_cov': ('cov',),
                'condition': ('alpha', 'Li'), 'forget': ('alpha', 'Li'), 'loo': ('mu', 'sd', 'lev', 'stats'),
                'select': ('idx', 'var', 'gain', 'sd'), 'select_iv': ('idx', 'red', 'var', 'ivar', 'sd'),
-               'select_qei': ('idx', 'gain', 'qei', 'score0', 'mstate')}
+               'select_qei': ('idx', 'gain', 'qei', 'score0', 'mstate'), 'predict_gradcov': T_GC.ALL, 'predict_pd': T_PD.ALL}
 
 
 def row_alone(a):
@@ -842,6 +1052,12 @@ def sweep_schedule(D, S, M):
     one('condition', SWEEP_MOVED[0]); one('condition', SWEEP_MOVED[1], 'raw')
     one('forget', SWEEP_MOVED[0], 'raw', u=2.5 / 997); one('forget', SWEEP_MOVED[1], u=1.5 / 997)
     both('predict')                                                                # the moved fit is used once more
+    # the two newest entry points come last, so that every group above keeps its number, seed and salt; they run on the moved fit, which
+    # takes ensure_pred_factor through once more
+    both('predict_gradcov', flag=True, mask=True)                                  # all four outputs, zeros behind the last weighted row
+    both('predict_gradcov', 'raw', flag=False)                                     # dmu and dvar only: the long chunks
+    both('predict_pd', flag=True, mask=True, G=SWEEP_GRID[0], pdims='all')         # pd_ref.dims_for(D), all four outputs
+    both('predict_pd', 'raw', nsamp=1, G=SWEEP_GRID[1], pdims='one', want=('pd', 'ice'))
     for st in steps:
         if st['op'] == 'post' and st['ep'] == 'loo':
             st.setdefault('resident', False)
@@ -878,6 +1094,11 @@ def check_sweep(steps):
     for ep in ('sample', 'sample_weights', 'sample_argmax', 'sample_grad', 'select_qei'):
         assert {st['nsamp'] for st in by(ep)} == {1, 7}, ep
     assert {st['kind'] for st in by('acquire')} == set(A.KINDS)
+    assert {(st['mode'], st['flag'], st['mask']) for st in by('predict_gradcov')} == {('scaled', True, True), ('raw', False, False)}
+    assert {(st['mode'], st['G'], st['pdims'], st['mask'], st.get('want')) for st in by('predict_pd')} == {
+        ('scaled', 9, 'all', True, None), ('raw', 1, 'one', False, ('pd', 'ice'))}
+    new = [st['ep'] for st in post if st.get('group', 0) > SWEEP_OLD_GROUPS[1]]     # the new groups stand at the end
+    assert new == ['predict_gradcov'] * 4 + ['predict_pd'] * 4 and [st['ep'] for st in post[-8:]] == new
     return dict(steps=len(steps), posterior=len(post))
 
 
@@ -907,10 +1128,14 @@ def row0_records(a, got, big_got, bits=True):
         g, b = got.get(k), big_got.get(k)
         if g is None or b is None:
             continue
-        g = np.asarray(g); b = np.asarray(b)[:T]
+        rows = len(np.asarray(b))
+        if a['ep'] == 'predict_pd':                                                # ice is (ndim, T, G): the rows are its second axis
+            rows = np.asarray(b).shape[1]; g = np.asarray(g); b = np.asarray(b)[:, :T]
+        else:
+            g = np.asarray(g); b = np.asarray(b)[:T]
         if a['ep'] == 'predict_cov' and a['Xb'] is None:
             b = b[:, :T]
-        label = '(c) %s of row 0 alone against the %d-row call\'s' % (k, len(np.asarray(big_got[k])))
+        label = '(c) %s of row 0 alone against the %d-row call\'s' % (k, rows)
         if bits:
             recs.append((label, 'exact', g, b, None))
         else:
@@ -1000,7 +1225,7 @@ def perturbed(rec, factor=10.0):
     the record has nothing to move (an empty output, a zero allowance)"""
     label, kind, got, ref, par = rec
     if kind == 'exact':
-        g = np.array(got)
+        g = np.array(got, order='C')                              # C order: ravel() below must be a view
         if g.size == 0:
             return None
         if g.dtype.kind == 'f':
@@ -1016,7 +1241,7 @@ def perturbed(rec, factor=10.0):
     if kind == 'relnorm':
         if np.size(ref) == 0:
             return None
-        g = np.array(ref, np.float64); g.ravel()[0] += factor * par * np.linalg.norm(ref)
+        g = np.array(ref, np.float64, order='C'); g.ravel()[0] += factor * par * np.linalg.norm(ref)
         return (label, kind, g, ref, par) if np.linalg.norm(ref) > 0 else None
     if kind == 'abs':
         g = np.array(np.broadcast_to(np.asarray(ref, np.float64), np.broadcast(np.asarray(ref), np.asarray(par)).shape))
@@ -1027,7 +1252,7 @@ def perturbed(rec, factor=10.0):
         g.ravel()[i] += factor * p.ravel()[i]
         return (label, kind, g, ref, par)
     if kind == 'allclose':
-        g = np.array(ref, np.float64)
+        g = np.array(ref, np.float64, order='C')
         i = np.flatnonzero(np.isfinite(g.ravel()))
         if i.size == 0:
             return None
@@ -1040,13 +1265,13 @@ def perturbed(rec, factor=10.0):
     if kind in ('alpha', 'li'):
         t = parity.TOL[par]
         b, tau = (t['vbeta'], t['vtau']) if kind == 'alpha' else (t['lbeta'], t['ltau'])
-        g = np.array(ref, np.float64)
+        g = np.array(ref, np.float64, order='C')
         tile = g[:parity.TILE]
         g.ravel()[0] += factor * (b * np.linalg.norm(tile) + tau * np.linalg.norm(ref))
         return (label, kind, g, ref, par)
     if kind == 'kinderr':
         k, mu, sd, beta = par
-        g = np.array(ref, np.float64)
+        g = np.array(ref, np.float64, order='C')
         i = int(np.argmax(np.abs(g) >= 1e-300)) if k not in ('ucb', 'logei') else 0
         scale = (abs(np.ravel(mu)[0]) + beta * np.ravel(sd)[0]) if k == 'ucb' else max(1.0, abs(g[0])) if k == 'logei' else abs(g[i])
         g[i] += factor * T_ACQ.PARITY_BOUND[k] * scale
@@ -1065,8 +1290,58 @@ def same_bits(a, b):
 
 
 # ---- one step: arguments, the call, the auxiliary calls, the records ---------------------------------------------------------------------
+REDRAWS = 64
+
+
 def materialise(st, fit):
-    """the arrays of a posterior step, drawn from its seed; rows in the mode's units"""
+    """the arrays of a posterior step, drawn from its seed; rows in the mode's units.  A step marked `redraw` (acquire_kg and predict_pd
+    in the sequences, whose fit is known only once the schedule has run so far) is drawn from seed, seed + 1, .. until its
+    input condition holds (input_condition): a condition on the inputs, computed from the fp64 references alone"""
+    if not st.get('redraw'):
+        return _materialise(st, fit)
+    for j in range(REDRAWS):
+        draw = dict(st, seed=st['seed'] + j, draw=j)
+        if j and st['ep'] == 'acquire_kg':
+            # On a fit of thousands of rows the lines are far apart against their slopes: with the observation noise in sigma and 31
+            # nodes, 1 draw in 18 meets the condition at 3000 fitted rows and none at 36 000; without the noise and with 3 nodes nearly
+            # every draw does.  So a repeated draw takes these two options from its seed as well.  The runner's log names the draw
+            # that was used with its options, and the CPU tier asserts the coverage of the options as they ran, not as scheduled.
+            r = np.random.default_rng([st['seed'], j])
+            draw.update(noise=bool(r.integers(2)), nodes=KG_NODES[int(r.integers(len(KG_NODES)))])
+        if j and st['ep'] == 'predict_pd':
+            # Under an X scaler that spreads the phases over many periods (D = 40, standardised columns) the mean feature row of a few
+            # hundred rows is a cancellation whatever the seed.  A repeated draw narrows the pool instead: the rows' log-normal spread is
+            # halved from draw to draw, down to PD_SPREAD_MIN.  Every row carries the sums with its drawn weight, so the block tree and
+            # the running sums across chunks are exercised as on the first draw.
+            draw['spread'] = max(PD_SPREAD_MIN, 0.5 ** j)
+        a = _materialise(draw, fit)
+        if input_condition(a, fit):
+            return a
+    raise AssertionError('no draw of this step meets its input condition: %r' % (st,))
+
+
+PD_SPREAD_MIN = 1.0 / 64
+
+
+def input_condition(a, fit):
+    """acquire_kg: kg_conditioning <= 1; predict_pd with sums: pd_cancellation >= PD_CANCEL"""
+    if a['ep'] == 'acquire_kg':
+        return kg_conditioning(a, fit) <= 1.0
+    if a['ep'] == 'predict_pd' and set(a['want']) - {'ice'}:
+        return pd_cancellation(a, fit) >= PD_CANCEL
+    return True
+
+
+def used_draw(a):
+    """what the runner's log says of a step drawn at run time: which draw was used, and the options a repeated draw may have replaced"""
+    if a.get('draw') is None:
+        return ''
+    if a['ep'] == 'acquire_kg':
+        return ' draw=%d noise=%s nodes=%s R=%d' % (a['draw'], a['noise'], a['nodes'], a['R'])
+    return ' draw=%d spread=%g' % (a['draw'], a.get('spread', 1.0))
+
+
+def _materialise(st, fit):
     D, S, M = fit.D, fit.S, fit.M
     rng = np.random.default_rng(st['seed'])
     ep, T, mode = st['ep'], st['T'], st['mode']
@@ -1099,9 +1374,9 @@ def materialise(st, fit):
             if st['op'] == 'fail':
                 a['y'] = a['y'].copy(); a['y'][T // 2] = np.nan
         return a
-    Xraw = raw_rows(rng, T, D)
+    Xraw = raw_rows(rng, T, D, st.get('spread', 1.0))
     a['Xraw'] = Xraw
-    if st.get('nan_row') or (st['op'] == 'fail' and ep == 'sample_argmax'):
+    if st.get('nan_row') or (st['op'] == 'fail' and ep in ('sample_argmax', 'predict_pd')):
         Xraw[T // 3, 0] = np.nan
     with np.errstate(all='ignore'):
         a['X'] = give(Xraw)
@@ -1115,6 +1390,25 @@ def materialise(st, fit):
         a['want_val'] = bool(st['noise'] or st.get('pair'))
     elif ep in ('sample_argmax', 'acquire'):
         a['w'] = mask(T)
+    elif ep in ('predict_gradcov', 'predict_pd'):
+        # weights with zeros among them and, on more than 8 rows, behind the last weighted row
+        a['w'] = mask(T)
+        if a['w'] is not None and T > 8:
+            a['w'][T - 3:] = 0.0
+            a['w'][0] = max(a['w'][0], 1.0)
+        if ep == 'predict_gradcov':
+            a['want'] = tuple(st['want']) if st.get('want') else T_GC.ALL if st['flag'] else ('dmu', 'dvar')
+            if st['op'] == 'fail':
+                a['w'] = np.zeros(T)                                               # weights that sum to 0: refused when asub is wanted
+        else:
+            a['want'] = tuple(st['want']) if st.get('want') else T_PD.ALL if st['flag'] else ('pd', 'sd')
+            dims = PD.dims_for(D) if st['pdims'] == 'all' else [int(st['u'] * D)]
+            cols = list(fit.xs.data['cols'])
+            a['dims'] = dims if mode == 'scaled' else [cols[d] for d in dims]     # raw mode names raw columns
+            fin = np.isfinite(a['X']).all(axis=1)
+            a['grid'] = PD.make_grid(a['X'][fin], a['dims'], st['G'], seed=st['seed'] % 1000)
+            # the auxiliary call's arguments: the dimensions reversed, a permuted proper subset of the grid (all of it at G = 1)
+            a['sub'] = np.arange(st['G'])[::-2]
     elif ep == 'acquire_kg':
         a['w'] = mask(T)
         a['Xr'] = give(raw_rows(rng, st['R'], D)) if st['R'] else None      # R = 0: the candidates are their own reference set
@@ -1184,6 +1478,10 @@ def call(eng, a):
         return eng.acquire(X, al, Li, a['kind'], w=a['w'], mode=mode, noise=a['noise'], minimize=a['minimize'], want=a['want'], **kw)
     if ep == 'acquire_kg':
         return eng.acquire_kg(X, al, Li, Xr=a['Xr'], z=a['z'], w=a['w'], mode=mode, noise=a['noise'], minimize=a['minimize'], want=T_KG.ALL)
+    if ep == 'predict_gradcov':
+        return eng.predict_gradcov(X, al, Li, w=a['w'], mode=mode, want=a['want'])
+    if ep == 'predict_pd':
+        return eng.predict_pd(X, al, Li, a['dims'], a['grid'], w=a['w'], mode=mode, want=a['want'])
     if ep == 'predict_cov':
         return dict(cov=eng.predict_cov(X, Li, Xb=a['Xb'], mode=mode, noise=a['noise'] and (a['Xb'] is None or a['op'] == 'fail')))
     if ep == 'condition':
@@ -1223,6 +1521,14 @@ def auxiliary(eng, a, got, fit):
         aux['cov'] = eng.predict_cov(X, Li, Xb=Xb, mode=mode)
         aux['mu_r'], aux['sd_r'] = (eng.predict if mode == 'scaled' else eng.predict_raw)(Xb, al, Li)
         aux['sd'] = eng.acquire(X, al, Li, 'ucb', beta=0.0, mode=mode, noise=a['noise'], want=('acq', 'sd'))['sd']
+    elif ep == 'predict_gradcov':
+        # promise 1: predict_grad of the same mode on the same context, which is thereby the direct successor of every gradcov call
+        aux['dmu'] = eng.predict_grad(X, al, Li, mode=mode, want_std=False)[2]
+    elif ep == 'predict_pd':
+        # promises 2, 3 and 7: the dimensions reversed, a permuted proper subset of the grid, the sums only.  A context whose products
+        # promise no bits across shapes (RefEngine.ROW_BITS) is compared to 1e-10 instead
+        aux['sub'] = eng.predict_pd(X, al, Li, a['dims'][::-1], a['grid'][::-1][:, a['sub']], w=a['w'], mode=mode, want=('pd', 'sd', 'cov'))
+        aux['bits'] = getattr(eng, 'ROW_BITS', True)
     elif ep in ('condition', 'forget') and 'alpha' in got:
         aux['probe'] = fit.fx(raw_rows(np.random.default_rng(a['seed'] + 1), 200, fit.D))
         aux['predict'] = eng.predict(aux['probe'], got['alpha'], got['Li'])
@@ -1378,6 +1684,54 @@ def records(a, got, aux, fit, dtype, prev):
             add('both sums are 0 at R = 1', 'exact', np.array([np.abs(got['kg']).max(), np.abs(got['kg_hi']).max()]), np.zeros(2), None)
         add('argmax idx', 'exact', got['idx'], int(KG.argmax(got['kg'], a['w'])), None)
         add('argmax val', 'exact', got['val'], float(got['kg'][got['idx']]), None)
+    elif ep == 'predict_gradcov':
+        want = a['want']
+        add('outputs are those asked for', 'exact', np.array([k in got for k in T_GC.ALL]), np.array([k in want for k in T_GC.ALL]), None)
+        r = ref.predict_gradcov(a['X'], al, Li, w=a['w'], mode=mode, want=want)
+        fin = np.isfinite(ref._rows(a['X'], mode)[0]).all(axis=1)                          # a NaN row stays in its own point's outputs
+        for k in ('dmu', 'dvar', 'dcov'):
+            if k in want:
+                add(k + ' finite pattern', 'exact', np.isfinite(got[k]), np.isfinite(r[k]), None)
+                add(k, 'relnorm', got[k][fin], r[k][fin], (T_GC.BOUNDS_DMU if k == 'dmu' else T_GC.BOUNDS)[dtype])
+        if 'asub' in want:
+            add('asub', 'relnorm', got['asub'], r['asub'], T_GC.BOUNDS[dtype])
+            add('asub is symmetric', 'exact', got['asub'], got['asub'].T, None)
+        if 'dmu' in want:
+            add('dmu is predict_grad\'s', 'exact', got['dmu'], aux['dmu'], None)
+        if 'dcov' in want:
+            add('dcov is symmetric', 'exact', got['dcov'], got['dcov'].transpose(0, 2, 1), None)
+            if 'dvar' in want:
+                add('dvar is the diagonal of dcov', 'exact', got['dvar'], np.diagonal(got['dcov'], axis1=1, axis2=2), None)
+        if 'dvar' in want:
+            add('dvar >= 0', 'exact', not np.any(got['dvar'] < 0), True, None)
+    elif ep == 'predict_pd':
+        want = a['want']
+        add('outputs are those asked for', 'exact', np.array([k in got for k in T_PD.ALL]), np.array([k in want for k in T_PD.ALL]), None)
+        sums = tuple(k for k in ('pd', 'sd', 'cov') if k in want)
+        if sums:
+            r = ref.predict_pd(a['X'], al, Li, a['dims'], a['grid'], w=a['w'], mode=mode, want=sums)
+            for k in sums:
+                add(k, 'relnorm', got[k], r[k], T_PD.BOUNDS[dtype])
+        if 'ice' in want:
+            # rows first, so that a step on row 0 alone is row-aligned with the larger one (conditioned_row0); a long call is compared
+            # on the rows around its chunk boundaries, as tests/test_gpu_predict_pd.py does
+            T = a['X'].shape[0]
+            sel = np.arange(T) if T <= 3000 else np.r_[0:4, 32766:32770, 65534:65538, T - 2:T]
+            r = ref.predict_pd(a['X'][sel], al, Li, a['dims'], a['grid'], mode=mode, want=('ice',))
+            add('ice', 'relnorm', got['ice'][:, sel].transpose(1, 0, 2), r['ice'].transpose(1, 0, 2), T_PD.BOUNDS_ICE[dtype])
+        if 'cov' in want:
+            add('cov is symmetric', 'exact', got['cov'], got['cov'].transpose(0, 2, 1), None)
+            if 'sd' in want:                                                               # tests/test_gpu_predict_pd.py: under BOUNDS
+                add('diag(cov) against sd^2', 'relnorm', np.diagonal(got['cov'], axis1=1, axis2=2), got['sd'] ** 2, T_PD.BOUNDS[dtype])
+        if 'sd' in want:
+            add('sd >= 0', 'exact', bool(np.all(got['sd'] >= 0)), True, None)
+        sub = a['sub']
+        for k in sums:
+            full = got[k][::-1][:, sub] if k != 'cov' else got[k][::-1][:, sub][:, :, sub]
+            if aux['bits']:
+                add('%s of the reversed dimensions and the grid\'s subset' % k, 'exact', aux['sub'][k], full, None)
+            else:
+                add('%s of the reversed dimensions and the grid\'s subset' % k, 'relnorm', aux['sub'][k], full, 1e-10)
     elif ep == 'predict_cov':
         add('cov', 'relnorm', got['cov'], ref.predict_cov(a['X'], Li, Xb=a['Xb'], mode=mode, noise=a['noise'] and a['Xb'] is None),
             T_COV.BOUNDS[dtype])
@@ -1529,6 +1883,18 @@ def failing_call(eng, a):
                 outs = [idx, val]
                 rc = eng.lib.scfgp_sample_argmax(eng.ctx, dptr(Xv), n, None, dptr(alv), dptr(Lv), a['nsamp'], a['seed'] % 1000, 0, 0,
                                                  idx.ctypes.data_as(_c_i64_p), dptr(val))
+            elif ep == 'predict_gradcov':
+                D = Xv.shape[1]
+                outs = [np.full((n, D), 3.0), np.full((n, D), 3.0), np.full((n, D, D), 3.0), np.full((D, D), 3.0)]
+                rc = eng.lib.scfgp_predict_gradcov(eng.ctx, dptr(Xv), n, dptr(np.ascontiguousarray(a['w'], np.float64)), dptr(alv), dptr(Lv), 0,
+                                                   *[dptr(o) for o in outs])
+            elif ep == 'predict_pd':
+                import ctypes
+                grid = np.ascontiguousarray(a['grid'], np.float64); nd, ng = grid.shape
+                dims = np.ascontiguousarray(a['dims'], np.int32)
+                outs = [np.full((nd, ng), 3.0), np.full((nd, ng), 3.0), np.full((nd, ng, ng), 3.0), np.full((nd, n, ng), 3.0)]
+                rc = eng.lib.scfgp_predict_pd(eng.ctx, dptr(Xv), n, None, dptr(alv), dptr(Lv), dims.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                              nd, dptr(grid), ng, 0, *[dptr(o) for o in outs])
             else:
                 outs = None
             if outs is not None:
@@ -1690,6 +2056,7 @@ class Runner(object):
                 a = _row0(self.kept[st['row0_of']][0], st['T'])
             else:
                 a = prepare(eng, materialise(st, f), f)
+                self.log[-1] += used_draw(a)
             got = call(eng, a)
             aux = auxiliary(eng, a, got, f)
             if i in self.row0_wanted:

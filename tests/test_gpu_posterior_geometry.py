@@ -1,5 +1,5 @@
 """GPU tier of the geometry sweep of the posterior entry points (tests/posterior_sequence.py: SWEEP_GEOMETRIES, sweep_schedule).  All
-seventeen posterior entry points run on padded buffers whose kernels "need no edge code"; what a call launches depends on a few integer
+nineteen posterior entry points run on padded buffers whose kernels "need no edge code"; what a call launches depends on a few integer
 classes of (D, S, M): the column plan of the apply products (64-wide tiles up to K = 256, 128-wide tiles and a 64-wide remainder above),
 the padding of K to Kp and the Kp / 64 partial slots, Jp, Dp, Sp and whether the rank-S projection is live.  Each geometry of the set
 sits in classes no other posterior test reaches (K = 8 and D = 1, M < S, three-tile small plans, K = 256 = Kp with J = Jp, K = 258 with
@@ -13,8 +13,9 @@ rows and then on row 0 of those rows alone, and is checked
   (d) in the f32 case, bit for bit against an f16x3 context that makes the same calls, where the header says the two modes agree bit
       for bit (PS.F16X3_EQUAL); its split products run for K > 256 only.
 
-Measured on the device (MI355X): 0.1 to 0.4 s per case, 21 tests in 8.9 s.  Largest error / bound of each entry point in f32 (every (c)
-and (d) record held exactly; each case prints its own line of these):
+Measured on the device (MI355X): 0.1 to 0.5 s per case, 21 tests in 9.7 s (8.9 s before predict_gradcov and predict_pd joined).  Largest
+error / bound of each of the seventeen older entry points in f32 (every (c) and (d) record held exactly; each case prints its own line
+of these):
 
     geometry   acquire acquire_kg condition forget loo predict predict_cov predict_grad predict_raw predict_y sample sample_argmax
                sample_grad sample_weights select select_iv select_qei
@@ -27,7 +28,24 @@ and (d) record held exactly; each case prints its own line of these):
     9-8-120    0.16 0.083 0.048 0.045 0.058 0.042 0.072 0.048 0.039 2.1e-07 0.2 0.23 0.027 0.00051 0.12 0.19 0.19
     40-6-123   0.26 0.46 0.11 0.044 0.13 0.051 0.071 0.055 0.05 1.9e-07 0.18 0.18 0.042 0.00054 0.13 0.088 0.18
     33-3-158   0.11 0.088 0.038 0.028 0.035 0.033 0.068 0.037 0.028 2e-07 0.11 0.11 0.044 0.00062 0.079 0.12 0.22
-    5-4-188    0.13 0.29 0.025 0.02 0.056 0.019 0.089 0.019 0.017 2e-07 0.24 0.46 0.05 0.00071 0.25 0.17 0.21"""
+    5-4-188    0.13 0.29 0.025 0.02 0.056 0.019 0.089 0.019 0.017 2e-07 0.24 0.46 0.05 0.00071 0.25 0.17 0.21
+
+predict_gradcov and predict_pd, which joined last (four groups at the end of the schedule, on the fit that condition and forget have
+moved): largest error / bound against the CPU closed forms under the bounds of their own GPU tests, per geometry and dtype, and the
+seconds of the case.  Every (c) record (dvar, dcov, ice of row 0 alone), every (d) record (all eight outputs of the f16x3 context) and
+every symmetry, diagonal, sign and subset record held exactly, at the three geometries with K > 256 as elsewhere:
+
+    geometry   f32: predict_gradcov predict_pd   f64: predict_gradcov predict_pd   seconds f64 / f32
+    1-2-2      0.019    0.04     4.4e-06  5.9e-06    0.2 / 0.1
+    7-12-3     0.036    0.17     1.1e-05  5.3e-05    0.1 / 0.2
+    70-5-60    0.015    0.094    2.6e-05  3.1e-05    0.3 / 0.4
+    15-15-60   0.02     0.077    1e-05    5.5e-06    0.3 / 0.3
+    16-16-70   0.035    0.14     1.3e-05  2.3e-05    0.3 / 0.3
+    6-5-91     0.014    0.041    8e-06    1.1e-05    0.2 / 0.3
+    9-8-120    0.016    0.08     8.5e-06  6.8e-06    0.3 / 0.3
+    40-6-123   0.033    0.11     1.3e-05  1.7e-05    0.5 / 0.5
+    33-3-158   0.0084   0.038    1.8e-05  1.3e-05    0.4 / 0.5
+    5-4-188    0.02     0.034    1.4e-05  8.9e-06    0.4 / 0.4"""
 import time
 
 import pytest
@@ -47,12 +65,15 @@ def _engine(D, S, M, dtype):
 
 
 def test_dims_of_every_geometry_of_the_set():
-    """the context's own geometry against the Python restatement the CPU tier's class coverage rests on"""
+    """the context's own geometry against the Python restatement the CPU tier's class coverage rests on, and its points per chunk of
+    predict_gradcov against the restatement of the header's formula"""
     for D, S, M in GEOS:
         ref = PS.RefEngine(D, S, M).dims()
         for dtype in PS.DTYPES + ('f16x3',):
             eng = _engine(D, S, M, dtype)
             d = eng.dims()
+            for want_cov in (True, False):
+                assert eng.gradcov_points_per_chunk(want_cov) == PS.gradcov_points_per_chunk(D, S, want_cov), ((D, S, M), want_cov)
             eng.close()
             assert {k: d[k] for k in ('K', 'Kp', 'Jp', 'Dp')} == {k: ref[k] for k in ('K', 'Kp', 'Jp', 'Dp')}, ((D, S, M), dtype, d, ref)
 

@@ -1,7 +1,9 @@
 """GPU tier of the posterior covariance of the input gradient (gradcov.hip: scfgp_predict_gradcov): parity with the numpy closed form
 (tests/gradcov_ref.py) over the geometry classes of q = min(D, S), multi-chunk calls with the chunk boundaries placed by
 HipEngine.gradcov_points_per_chunk, the bit-level promises of include/scfgp_hip.h, raw mode through every X scaler, every combination
-of outputs, the refusals, and the SCFGP facade (predict_gradcov, active_subspace)."""
+of outputs, the refusals, and the SCFGP facade (predict_gradcov, active_subspace).  Every geometry here has K <= 172: the 128-wide
+column plan of K > 256, K = 256 = Kp, the factors of a real fit and a context that other entry points share are covered by the geometry
+sweep and the stale-state sequences (tests/test_gpu_posterior_geometry.py, tests/test_gpu_posterior_sequence.py)."""
 import itertools
 
 import numpy as np

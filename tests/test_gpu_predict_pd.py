@@ -1,7 +1,9 @@
 """GPU tier of the partial-dependence and ICE curves (pd.hip: scfgp_predict_pd): parity with the numpy brute force over the expanded rows
 (tests/pd_ref.py) over the geometry classes, a three-chunk call, the bit-level promises of include/scfgp_hip.h, the documented bounds
 of G and ndim, self-consistency against predict / acquire / ice, raw mode through every X scaler, the refusals, the training state and
-the SCFGP facade (partial_dependence)."""
+the SCFGP facade (partial_dependence).  Every geometry of the parity tests has K <= 172: the 128-wide column plan of K > 256, K = 256 =
+Kp, the factors of a real fit and a context that other entry points share are covered by the geometry sweep and the stale-state
+sequences (tests/test_gpu_posterior_geometry.py, tests/test_gpu_posterior_sequence.py)."""
 import ctypes
 import itertools
 

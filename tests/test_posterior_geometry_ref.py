@@ -2,21 +2,91 @@
 covers every geometry class it is there for (the column plan of the apply products, the padding of K, J, D + 1 and S + 1, the rank-S
 projection, M < S), restated in Python so that an edit of the list cannot drop one; the sweep schedule of every geometry runs through the
 runner on the CPU references, with a second reference context in the f16x3 context's place; no check is vacuous (every bounded record
-fails when moved by ten times its bound, every exact one by one ulp); every one of the seventeen entry points had a bounded record moved at
-every geometry; and a correct fp32 evaluation of predict stays inside half the fp32 bound under the schedule's own parameters, rows and
-scalers, so that a miss on the GPU means the kernel."""
+fails when moved by ten times its bound, every exact one by one ulp); every one of the nineteen entry points had a bounded record moved at
+every geometry; the groups of the seventeen older entry points keep the seeds they had before predict_gradcov and predict_pd joined; no
+predict_pd step sums its features to a cancellation; and a correct fp32 evaluation of predict, predict_gradcov and predict_pd stays
+inside half the fp32 bound under the schedule's own parameters, rows and scalers, so that a miss on the GPU means the kernel."""
 import time
 
 import numpy as np
 import pytest
 
 from oracle import scfgp_oracle as O
+from tests import gradcov_ref as GC
 from tests import parity
+from tests import pd_ref as PD
 from tests import posterior_sequence as PS
 
 GEOS = PS.SWEEP_GEOMETRIES
 IDS = ['%d-%d-%d' % g for g in GEOS]
 MOVED = {}                  # geometry -> entry points of which an output was moved by ten times its bound
+NEW = ('predict_gradcov', 'predict_pd')
+# the seeds of the parameters, the rows of the fit, and the first and the last group of the seventeen older entry points, as the schedules
+# stood before the two new entry points were appended
+OLD_SEEDS = {
+    (1, 2, 2): (267044625, 1418682806, 1781960455, 291263497), (7, 12, 3): (2104014140, 366281942, 335817057, 2021640045),
+    (70, 5, 60): (1999072146, 972872473, 1549840235, 1322966090), (15, 15, 60): (1998373682, 558553731, 51004279, 1793372304),
+    (16, 16, 70): (2003618362, 186290001, 1974658586, 1772684625), (6, 5, 91): (792806809, 1976301653, 296080662, 740317324),
+    (9, 8, 120): (429022034, 1356161591, 1846834136, 1869176490), (40, 6, 123): (568823607, 115040132, 1571876481, 1673774771),
+    (33, 3, 158): (97341019, 366398862, 317038853, 1316310994), (5, 4, 188): (827559881, 871956715, 673099209, 550049996),
+}
+
+
+def _records(ep, plain, row0, mirror):
+    out = {(ep, k, kind) for k, kind in plain}
+    out |= {(ep, '(c) ' + k, kind) for k in row0 for kind in ('exact', 'relnorm')}         # RefEngine.ROW_BITS: the pattern, and 1e-10
+    return out | {(ep, '(d) ' + k, 'exact') for k in mirror}
+
+
+# every record the two new entry points must have had moved at every geometry: (entry point, label, kind)
+NEW_RECORDS = _records('predict_gradcov', [('outputs are those asked for', 'exact'), ('dmu finite pattern', 'exact'), ('dmu', 'relnorm'),
+                                           ('dvar finite pattern', 'exact'), ('dvar', 'relnorm'), ('dcov finite pattern', 'exact'),
+                                           ('dcov', 'relnorm'), ('asub', 'relnorm'), ('asub is symmetric', 'exact'),
+                                           ('dmu is predict_grad\'s', 'exact'), ('dcov is symmetric', 'exact'),
+                                           ('dvar is the diagonal of dcov', 'exact'), ('dvar >= 0', 'exact')],
+                       PS.ROW_ALONE['predict_gradcov'], PS.F16X3_EQUAL['predict_gradcov']) | \
+    _records('predict_pd', [('outputs are those asked for', 'exact'), ('pd', 'relnorm'), ('sd', 'relnorm'), ('cov', 'relnorm'), ('ice', 'relnorm'),
+                            ('cov is symmetric', 'exact'), ('diag(cov) against sd^2', 'relnorm'), ('sd >= 0', 'exact')] +
+             [('%s of the reversed dimensions and the grid\'s subset' % k, 'relnorm') for k in ('pd', 'sd', 'cov')],
+             PS.ROW_ALONE['predict_pd'], PS.F16X3_EQUAL['predict_pd'])
+
+
+def fp32_gradcov(a, fit):
+    """error / fp32 bound of a correct fp32 evaluation of a predict_gradcov step: the product Psi Li^T (and Psi alpha) as
+    parity.apply32_model forms it -- fp32 operands, fp32 result -- and everything after it in fp64, against the dense fp64 closed form"""
+    ref = PS._ref_engine(fit)
+    X, g, cols, width = ref._rows(a['X'], a['mode'])
+    T, D = X.shape
+    Q, P = GC.basis(fit.params, D, fit.S, fit.M)
+    Psi = GC.dphi(X, fit.params, fit.S, fit.M)[:, None, :] * np.concatenate((Q, Q), 0).T[None, :, :]        # T x q x K
+    q, K = Psi.shape[1:]
+    C = parity.apply32_model(Psi.reshape(T * q, K), np.tril(a['Li']).T).reshape(T, q, K)
+    m = parity.apply32_model(Psi.reshape(T * q, K), np.asarray(a['alpha']).reshape(-1, 1)).reshape(T, q) @ P.T
+    Sig = PS.kappa(fit.params) * (P @ (C @ C.transpose(0, 2, 1)) @ P.T)
+    if g is not None:
+        m, Sig = m * g, Sig * g[:, :, None] * g[:, None, :]
+    m0, S0 = GC.gradcov(X, a['alpha'], a['Li'], fit.params, fit.S, fit.M, g=g)
+    out = dict(dmu=PS.rel(m, m0) / PS.T_GC.BOUNDS_DMU['f32'], dvar=PS.rel(np.diagonal(Sig, axis1=1, axis2=2), np.diagonal(S0, axis1=1, axis2=2)),
+               dcov=PS.rel(Sig, S0), asub=PS.rel(GC.asub(m, Sig, a['w']), GC.asub(m0, S0, a['w'])))
+    for k in ('dvar', 'dcov', 'asub'):
+        out[k] /= PS.T_GC.BOUNDS['f32']
+    return {k: v for k, v in out.items() if k in a['want']}
+
+
+def fp32_pd(a, fit):
+    """the same of the sums of a predict_pd step: the mean feature rows Phibar in fp64 (the device sums them in fp64), then Phibar Li^T
+    and Phibar alpha as parity.apply32_model forms them, and everything after in fp64"""
+    ref = PS._ref_engine(fit)
+    X, dims, grid = ref.pd_scaled(a['X'], a['dims'], a['grid'], a['mode'])
+    pd0, sd0, cov0, _, Pb = PD.closed(X, a['w'], a['alpha'], a['Li'], fit.params, fit.S, fit.M, dims, grid, want_ice=False)
+    kap = PS.kappa(fit.params)
+    pd = np.empty_like(pd0); sd = np.empty_like(sd0); cov = np.empty_like(cov0)
+    for i in range(len(dims)):
+        C = parity.apply32_model(Pb[i], np.tril(a['Li']).T)
+        pd[i] = parity.apply32_model(Pb[i], np.asarray(a['alpha']).reshape(-1, 1)).ravel()
+        cov[i] = kap * (C @ C.T); sd[i] = np.sqrt(kap * np.sum(C * C, axis=1))
+    out = dict(pd=PS.rel(pd, pd0), sd=PS.rel(sd, sd0), cov=PS.rel(cov, cov0))
+    return {k: v / PS.T_PD.BOUNDS['f32'] for k, v in out.items() if k in a['want']}
 
 
 def test_the_set_covers_the_geometry_classes():
@@ -46,17 +116,25 @@ def test_sweep_schedules_hold_every_entry_point_in_every_mode():
     for g in GEOS:
         steps = PS.sweep_schedule(*g)
         info = PS.check_sweep(steps)
-        assert len(PS.SWEEP_ENTRY_POINTS) == 17 and not any(st['op'] in ('fail', 'eval', 'rows', 'train', 'option') for st in steps)
+        assert len(PS.SWEEP_ENTRY_POINTS) == 19 and len(set(PS.SWEEP_ENTRY_POINTS)) == 19 and not any(st['op'] in ('fail', 'eval', 'rows', 'train', 'option') for st in steps)
         post = [st for st in steps if st['op'] == 'post']
         assert {st['m'] for st in post} == {5} and {st['T'] for st in post} == {1, 37, 257, 300}
         PS.sweep_schedule.cache_clear()
         assert PS.sweep_schedule(*g) == steps                     # a function of the geometry alone
+        # the prefix of the seventeen older entry points is what it was: 85 steps, groups 2 .. 40, their seeds
+        lo, hi = PS.SWEEP_OLD_GROUPS
+        old = [st for st in steps if st['op'] != 'post' or st['group'] <= hi]
+        assert old == steps[:85] and {st['ep'] for st in old[4:]} == set(PS.SWEEP_ENTRY_POINTS) - set(NEW)
+        assert [st['group'] for st in steps[85:]] == [hi + 1, hi + 1, hi + 2, hi + 2, hi + 3, hi + 3, hi + 4, hi + 4]
+        assert (steps[1]['seed'], steps[2]['seed'], steps[4]['seed'], steps[84]['seed']) == OLD_SEEDS[g] and steps[4]['group'] == lo
+        assert steps[84]['group'] == hi and steps[84]['ep'] == 'predict' and set(NEW) == {st['ep'] for st in steps[85:]}
+        assert all(n <= hi for n in PS._SALT[g]) or {n for n in PS._SALT[g] if n > hi} <= set(range(hi + 1, hi + 5))
     print('steps per geometry: %d, posterior steps: %d' % (info['steps'], info['posterior']))
 
 
 @pytest.mark.parametrize('g', GEOS, ids=IDS)
 def test_dry_run_on_the_references_and_no_check_is_vacuous(g):
-    moved = {'bound': {}, 'exact': 0, 'row0': 0, 'mirror': 0, 'conditioned': 0}
+    moved = {'bound': {}, 'exact': 0, 'row0': 0, 'mirror': 0, 'conditioned': 0, 'pd sums': 0, 'new': set(), 'new row 0': set(), 'fp32': 0.0}
     refs = {}
     holder = {}
 
@@ -66,20 +144,36 @@ def test_dry_run_on_the_references_and_no_check_is_vacuous(g):
         if 'row0_of' in steps[i]:
             for label, ref in refs[i].items():
                 if label in refs[steps[i]['row0_of']]:
-                    assert PS.conditioned_row0(ref, refs[steps[i]['row0_of']][label]) is not False, (i, a['ep'], label)
+                    ok = PS.conditioned_row0(ref, refs[steps[i]['row0_of']][label])
+                    assert ok is not False, (i, a['ep'], label)
                     moved['conditioned'] += 1
+                    if a['ep'] in NEW and ok:
+                        moved['new row 0'].add((a['ep'], label))
             if a['ep'] == 'acquire_kg' and a['T'] == 257 and not (g[0] == 1 and a['R'] == 37):
                 assert PS.kg_conditioning(a, holder['run'].fit) <= 1.0, (i, PS.kg_conditioning(a, holder['run'].fit))
             if a['ep'] == 'acquire' and 'grad' in a['want']:
                 c = PS.acquire_grad_cancellation(a, holder['run'].fit)
                 assert c <= PS.GRAD_CANCEL, (i, a['kind'], c)
+        if a['ep'] == 'predict_pd' and set(a['want']) - {'ice'}:
+            c = PS.pd_cancellation(a, holder['run'].fit)
+            assert c >= PS.PD_CANCEL, (i, c)
+            moved['pd sums'] += 1
+        # a correct fp32 evaluation of every step of the two new entry points, the steps on row 0 alone included, stays inside half the
+        # fp32 bound: their salts are the first for which it does
+        if a['ep'] in NEW:
+            r32 = (fp32_gradcov if a['ep'] == 'predict_gradcov' else fp32_pd)(a, holder['run'].fit)
+            assert r32 and max(r32.values()) <= 0.5, (i, a['ep'], a['T'], r32)
+            moved['fp32'] = max(moved['fp32'], max(r32.values()))
         for rec in recs:
             PS.evaluate(rec)
             bad = PS.perturbed(rec)
             if bad is None:
+                assert a['ep'] not in NEW, (a['ep'], rec[0])           # every record of the new entry points has something to move
                 continue
             with pytest.raises(AssertionError):
                 PS.evaluate(bad)
+            if a['ep'] in NEW:
+                moved['new'].add((a['ep'], rec[0].split(' of row 0')[0].split(' of the f16x3')[0], rec[1]))
             if rec[0].startswith('(c)'):
                 moved['row0'] += 1
             elif rec[0].startswith('(d)'):
@@ -99,9 +193,14 @@ def test_dry_run_on_the_references_and_no_check_is_vacuous(g):
     print('%s: %d steps, %s, moved %s, %.1f s' % (g, len(steps), counts, moved, time.time() - t0))
     assert counts['twin'] == 0 and counts['records'] > 0 and counts['row0'] > 0 and counts['mirror'] > 0
     assert moved['exact'] > 0 and moved['row0'] > 0 and moved['mirror'] > 0 and moved['conditioned'] > 0
-    # every one of the seventeen entry points had a bounded record moved at this geometry
+    # every one of the nineteen entry points had a bounded record moved at this geometry
     assert set(moved['bound']) == set(PS.SWEEP_ENTRY_POINTS), sorted(set(PS.SWEEP_ENTRY_POINTS) - set(moved['bound']))
     assert len(run.min_pivot2) == 2 and min(run.min_pivot2) >= 0.25
+    # the new entry points: every record of PS.records, of (c) and of (d) was moved, and every row-aligned record of their steps on row 0
+    # alone met conditioned_row0 (asub, pd, sd and cov are sums over the rows and not row-aligned)
+    assert moved['pd sums'] == 4                                   # every predict_pd step of the sweep asks for a sum
+    assert moved['new'] >= NEW_RECORDS, sorted(NEW_RECORDS - moved['new'])
+    assert moved['new row 0'] == {('predict_gradcov', 'dmu'), ('predict_gradcov', 'dvar'), ('predict_gradcov', 'dcov'), ('predict_pd', 'ice')}
     MOVED[g] = set(moved['bound'])
 
 
@@ -136,3 +235,35 @@ def test_a_correct_fp32_predict_stays_inside_half_the_fp32_bound(g):
     r = parity.predict_ratio(mu, sd, mu0, sd0, 'f32')
     print('%s: a correct fp32 predict stands at %.2f of the fp32 bound' % (g, r))
     assert r <= 0.5, r
+
+
+@pytest.mark.parametrize('g', GEOS, ids=IDS)
+def test_a_correct_fp32_gradcov_and_pd_stay_inside_half_the_fp32_bound(g):
+    """the first predict_gradcov step and the first predict_pd step of the sweep schedule (257 rows, every output), on the fit as
+    condition and forget have left it: parity.apply32_model of Psi Li^T and of Phibar Li^T, everything after in fp64, against the fp64
+    closed forms under the bounds imported from the own GPU tests.  A condition on the choice of inputs, not a tolerance."""
+    D, S, M = g
+    steps = PS.sweep_schedule(*g)
+    fit = PS.Fit(D, S, M)
+    fit.xs = PS.x_scaler(steps[0]['algo'], D); fit.ys = PS.y_scaler(steps[3]['algo'])
+    fit.params = PS.new_params(np.random.default_rng(steps[1]['seed']), D, S, M)
+    rng = np.random.default_rng(steps[2]['seed'])
+    fit.Xraw = PS.raw_rows(rng, steps[2]['N'], D); fit.yraw = PS.raw_targets(rng, fit.Xraw)
+    # the rows condition and forget move, replayed on the CPU model of the fit
+    for st in steps:
+        if st['op'] == 'post' and st['ep'] in ('condition', 'forget'):
+            a = PS.materialise(st, fit)
+            if st['ep'] == 'condition':
+                fit.Xraw = np.vstack([fit.Xraw, a['Xraw']]); fit.yraw = np.vstack([fit.yraw, a['yraw']])
+            else:
+                keep = np.setdiff1d(np.arange(fit.Xraw.shape[0]), a['rows'])
+                fit.Xraw, fit.yraw = fit.Xraw[keep], fit.yraw[keep]
+            fit.touch()
+    assert fit.Xraw.shape[0] == PS.SWEEP_N
+    for ep, model in (('predict_gradcov', fp32_gradcov), ('predict_pd', fp32_pd)):
+        st = next(s for s in steps if s['op'] == 'post' and s['ep'] == ep)
+        a = PS.materialise(st, fit)
+        assert a['X'].shape[0] == 257 and st['flag'] and a['w'] is not None
+        r = model(a, fit)
+        print('%s: a correct fp32 %s stands at %s of the fp32 bound' % (g, ep, ' '.join('%s %.3f' % kv for kv in r.items())))
+        assert set(r) == set(a['want']) - {'ice'} and max(r.values()) <= 0.5, r
