@@ -141,7 +141,9 @@ int scfgp_predict_y(scfgp_ctx* ctx, const double* Xs_raw, int64_t T, const doubl
  *   mode 2  mode 1 and the y scaler, as scfgp_predict_y: mu, std are mu_y, std_y; dmu = bw'(mu) d mu,
  *           dstd = (bw'(mu + std) (d mu + d std) - bw'(mu - std) (d mu - d std)) / 2 (bw = the y scaler's backward transform)
  * dstd may be NULL: then only the mean gradient is formed (no V* = Phi* B product).  SCFGP_EARG for bad arguments, a missing scaler
- * (modes 1, 2) or parameters not set. */
+ * (modes 1, 2) or parameters not set.  Where a scaler's derivative is an infinite factor times a normal density that has underflowed to 0
+ * in fp64 (X mode 5 at x = min with an exponent below 1 and |z| > 38.6; y mode 5 at mu, mu +- std = 0 or 1) the product is formed as 0 * inf
+ * and the entry is NaN where the limit is infinite: non-finite either way. */
 int scfgp_predict_grad(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* alpha, const double* Li, int mode,
                        double* mu, double* std, double* dmu, double* dstd);
 /* ---- posterior sample functions (no reference counterpart: the reference reports the marginals only) ---------------------------
@@ -766,6 +768,9 @@ int scfgp_get_timings(scfgp_ctx* ctx, double* ms, const char** names, int n);
  * "p","q","vecs","Fall","Lall","Rall","Xt","Tt","scalars"); returns the number of bytes copied or <0.  "Lall" (Dp x round_up(Sp,64))
  * and "Rall" (Sp x Jp) are the factors of the rank-S projection, defined only where it runs (Sp < Dp).  "G" is exchange buffer 1 unpacked
  * (the summed Gram, Phi^T y, y^T y and the status word) at any stage; "W" is exchange buffer 2 as the adjoint stage left it.
+ * "Xt" holds the resident training rows only; "pXt" is the packed chunk of the last posterior call (scfgp_predict* and the other
+ * entry points that take test or pool rows): the rows of its last chunk after the X scaler, round_up(rows, 256) x Dp doubles with a
+ * column of ones at d = D and zeros elsewhere in the padding; an error before the first such call.
  * Compute mode SCFGP_F16X3 only (elsewhere an error with a message): "Phi16", "V16g", "qV16g" the Np x Kp plane-form arrays of
  * Phi, V and diag(q) V (4 bytes per element, per 16 columns 16 fp16 h's then 16 l's; without the padding behind them); "B16"
  * the K x K operand of the apply products in plane form (Kp x Kp x 4 bytes, row j = column j); "f16scale" its 4 floats

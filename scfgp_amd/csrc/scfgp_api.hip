@@ -182,6 +182,7 @@ struct scfgp_ctx {
     int ys_mode = 0; double* d_yscale = nullptr;                 // y scaler for scfgp_predict_y (5 doubles)
     // predict chunk buffers
     double *p_Xt = nullptr, *p_vpart = nullptr, *p_mupart = nullptr; void *p_Phi = nullptr;
+    int64_t p_rows = 0;                                          // padded rows of the chunk p_Xt holds (debug_read "pXt")
     // ... and those of scfgp_predict_grad, allocated by its first call: FT = Fall^T typed; with the std gradient C = Phi* Li^T, V = C Li
     // (PRED_ROWS x Kp each, typed) and the typed Li
     void *p_FT = nullptr, *p_C = nullptr, *p_V = nullptr, *p_Li = nullptr;
@@ -1409,6 +1410,12 @@ static Geom chunk_geom(const Geom& g0, int64_t rows) {
     g.N = rows; g.Np = round_up(rows, 256);
     return g;
 }
+// pack_data of one chunk of a posterior call into p_Xt; the chunk's padded row count is kept for debug_read("pXt")
+static void pack_chunk(scfgp_ctx* c, const Geom& g, const double* Xraw, const double* yraw, const int64_t* idx, double* y,
+                       int mode = 0, const double* sp = nullptr) {
+    c->p_rows = g.Np;
+    pack_data(g, Xraw, yraw, idx, c->p_Xt, y, c->st, mode, sp);
+}
 // The factor pass.  Li (K x K, host) -> raw -> L64 (Kp x Kp fp64) by `pad` (pad_square: identity padding; update_load_factor: the
 // lower triangle only, so that entries above the diagonal are never read) -> the typed Li^T into LiT and, Li_typed != NULL, the typed
 // Li.  alpha != NULL: zero-padded into avec.  finite != NULL: scfgp_condition's checks of what was loaded.  raw may be reused once the
@@ -1517,7 +1524,7 @@ static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double*
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, raw_mode ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, raw_mode ? c->xs_mode : 0, c->d_xscale);
         if (!grad && (rc = feed.release(i))) return rc;
         if ((rc = DISPATCH(c, predict_chunk, c, g, LiT, d_mu + t0, d_sd + t0))) return rc;
         if (grad) {
@@ -1678,7 +1685,7 @@ extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const dou
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
         if ((rc = ring.acquire(i))) return rc;
         if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, noise, ymode, slot(i)))) return rc;
@@ -1719,7 +1726,7 @@ static int sample_argmax_run(scfgp_ctx* c, const double* Xs, int64_t T, const do
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wraw;
         if ((rc = r.feed.acquire(i, &x, &wraw))) return rc;
-        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, r.wchunk.p, c->st, xraw ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, r.wchunk.p, xraw ? c->xs_mode : 0, c->d_xscale);
         if ((rc = r.feed.release(i))) return rc;
         const SampleArgmaxBufs b = {best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
         if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, Wt, nsamp, r.wchunk.p, minimize, jobs.row0(i), b))) return rc;
@@ -1832,7 +1839,7 @@ extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const do
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wraw;
         if ((rc = feed.acquire(i, &x, &wraw))) return rc;
-        pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, w ? d_w : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if (!grad && (rc = feed.release(i))) return rc;
         const AcquireBufs b = {d_mu + t0, d_sd + t0, d_acq + t0, d_au, d_as, best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
         if ((rc = DISPATCH(c, acquire_chunk, c, g, LiT, spec, w ? d_w : nullptr, t0, b))) return rc;
@@ -1930,7 +1937,7 @@ extern "C" int scfgp_acquire_kg(scfgp_ctx* c, const double* Xc, int64_t T, const
         const double *x, *wraw;
         if ((rc = feed.acquire(job, &x, &wraw))) return rc;
         const bool cand = !jobs.lead(job);
-        pack_data(g, x, cand && w ? wraw : nullptr, nullptr, c->p_Xt, cand && w ? d_w : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, cand && w ? wraw : nullptr, nullptr, cand && w ? d_w : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(job))) return rc;
         const int64_t i = jobs.chunk(job), t0 = i * PRED_ROWS;
         const KgBufs b = {d_d, d_zf, d_sd, d_stm, d_sts, d_stb, cand ? d_kg + t0 : nullptr, cand ? d_hi + t0 : nullptr,
@@ -2014,7 +2021,7 @@ extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, cons
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *sraw;
         if ((rc = feed.acquire(i, &x, &sraw))) return rc;
-        pack_data(g, x, sidx ? sraw : nullptr, nullptr, c->p_Xt, schunk.p, c->st, xmode, c->d_xscale);
+        pack_chunk(c, g, x, sidx ? sraw : nullptr, nullptr, schunk.p, xmode, c->d_xscale);
         if ((rc = ring.acquire(i))) return rc;
         if ((rc = DISPATCH(c, sample_grad_chunk, c, g, wt.p, schunk.p, jobs.row0(i), nsamp, slot_val(i), slot_grad(i)))) return rc;
         // the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is released after them), the y
@@ -2090,7 +2097,7 @@ extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, con
         const Geom g = chunk_geom(g0, jobs.rows(job));
         const double* x;
         if ((rc = feed.acquire(job, &x))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(job))) return rc;
         if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, jobs.lead(job) ? c->p_V : c->p_C))) return rc;
         if (job + 1 < njobs && (rc = feed.upload(job + 1, jobs))) return rc;
@@ -2183,7 +2190,7 @@ static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const dou
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *yi;
         if ((rc = feed.acquire(i, &x, &yi))) return rc;
-        pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
         double* out = i == 0 ? c->u_acc : c->u_part;
         if ((rc = wide ? Impl<double>::update_chunk(c, g, update_splits(c, g.Np, true), ops, out)
@@ -2311,7 +2318,7 @@ extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, in
             const Geom g = chunk_geom(g0, jobs.rows(i));
             const double *x, *yi;
             if ((rc = feed.acquire(nchunks + i, &x, &yi))) return rc;
-            pack_data(g, x, yi, nullptr, c->p_Xt, c->u_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+            pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
             if ((rc = feed.release(nchunks + i))) return rc;
             if ((rc = ring.acquire(i))) return rc;
             double* o = slot(i);
@@ -2405,11 +2412,11 @@ extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t
         const int64_t t0 = jobs.row0(i);
         const Geom g = chunk_geom(g0, jobs.rows(i));
         if (resident) {
-            pack_data(g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->p_Xt, c->l_y, c->st);
+            pack_chunk(c, g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->l_y);
         } else {
             const double *xi, *yi;
             if ((rc = feed.acquire(i, &xi, &yi))) return rc;
-            pack_data(g, xi, yi, nullptr, c->p_Xt, c->l_y, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+            pack_chunk(c, g, xi, yi, nullptr, c->l_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
             if ((rc = feed.release(i))) return rc;
         }
         if ((rc = ring.acquire(i))) return rc;
@@ -2514,7 +2521,7 @@ extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, 
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double *x, *wi;
         if ((rc = feed.acquire(i, &x, &wi))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
         if ((rc = ring.acquire(i))) return rc;
         // the raw rows and the weights stay in the feed's half until the block kernel has read them
         if ((rc = DISPATCH(c, gradcov_chunk, c, g, LiT, qt.p, x, xmode, gfac.p, feed_w ? wi : nullptr, slot_dmu(i), dvar ? slot_dvar(i) : nullptr,
@@ -2631,7 +2638,7 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
             const Geom g = chunk_geom(g0, jobs.rows(i));
             const double *x, *wraw;
             if ((rc = feed.acquire(i, &x, &wraw))) return rc;
-            pack_data(g, x, w ? wraw : nullptr, nullptr, c->p_Xt, wchunk.p, c->st, xmode, c->d_xscale);
+            pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, wchunk.p, xmode, c->d_xscale);
             if ((rc = feed.release(i))) return rc;
             for (int a0 = 0; a0 < ndim; a0 += ngs)
                 if ((rc = DISPATCH(c, pd_sums_chunk, c, g, wchunk.p, dv + a0, std::min(ngs, ndim - a0), rec.p, acc + a0 * Jp2))) return rc;
@@ -2710,7 +2717,7 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
             const Geom g = chunk_geom(g0, jobs.rows(i));
             const double* x;
             if ((rc = feed.acquire(j0 + i, &x))) return rc;
-            pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, xmode, c->d_xscale);
+            pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
             if ((rc = feed.release(j0 + i))) return rc;
             for (int a = 0; a < ndim; ++a, ++k) {
                 if ((rc = ring.acquire(k))) return rc;
@@ -2799,7 +2806,7 @@ extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const dou
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
         if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, (char*)Cbuf.p + ts * (size_t)jobs.row0(i) * Kp))) return rc;
         if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
@@ -2927,7 +2934,7 @@ extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const 
         const bool in_q = job < nref || !Xr, weighted = in_q && wr;
         const double *x, *om;
         if ((rc = feed.acquire(job, &x, &om))) return rc;
-        pack_data(g, x, weighted ? om : nullptr, nullptr, c->p_Xt, weighted ? c->u_y : nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, weighted ? om : nullptr, nullptr, weighted ? c->u_y : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(job))) return rc;
         void* Cj = job < nref ? c->p_C : (void*)((char*)Cbuf.p + ts * (size_t)((job - nref) * PRED_ROWS) * Kp);
         if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, Cj))) return rc;
@@ -3033,7 +3040,7 @@ extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const
         const Geom g = chunk_geom(g0, jobs.rows(i));
         const double* x;
         if ((rc = feed.acquire(i, &x))) return rc;
-        pack_data(g, x, nullptr, nullptr, c->p_Xt, nullptr, c->st, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
         if ((rc = feed.release(i))) return rc;
         if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, 0, -1, Fbuf + jobs.row0(i) * nsamp))) return rc;
         if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
@@ -3425,6 +3432,10 @@ extern "C" int64_t scfgp_debug_read(scfgp_ctx* c, const char* name, void* host, 
     else if (s == "Lall") { src = c->d_Lall; bytes = 8 * (int64_t)g.Dp * round_up(g.Sp, 64); }   // factors of the rank-S form; written
     else if (s == "Rall") { src = c->d_Rall; bytes = 8 * (int64_t)g.Sp * g.Jp; }                  // only where it is used (Sp < Dp)
     else if (s == "Xt") { src = c->d_Xt; bytes = 8 * g.Np * g.Dp; }
+    else if (s == "pXt") {                                       // the packed, scaled rows of the last chunk of the last posterior call
+        if (!c->p_Xt || !c->p_rows) { c->err = "debug_read: pXt exists only after a posterior call"; return SCFGP_EARG; }
+        src = c->p_Xt; bytes = 8 * c->p_rows * g.Dp;
+    }
     else if (s == "scalars") { src = c->d_scalars; bytes = 8 * 32; }
     else if (s == "C") {                                         // factor form: C = Phi Li^T of the last pass 2 at level 2
         if (!c->d_C || c->c_cap < g.Np || !c->last_cform) { c->err = "debug_read: C exists only after a pass 2 in the factor form (level 2)"; return SCFGP_EARG; }

@@ -9,6 +9,8 @@ chosen to minimise squared sample skewness (SLSQP on lambda = softplus(t), t in
 [-5,5]; SCFGP/Scaler.py:58-70) and then standardise ('auto-normal') or map through
 the normal CDF ('auto-inv-normal').  Constant columns are dropped (:40-41).
 """
+import math
+
 import numpy as np
 from scipy.optimize import minimize
 from scipy.stats import norm, skew
@@ -22,6 +24,19 @@ def _boxcox(x, lm):
 
 def _inv_boxcox(x, lm):
     return np.sign(x * lm + 1) * np.abs(x * lm + 1) ** (1. / lm)
+
+
+def _norm_cdf(z):
+    # scipy's cdf is 0 from z = -37.65 down (its erfc gives up where exp(-z^2 / 2) leaves the normal range).  The true value stays
+    # representable, as a subnormal number, down to z = -38.6, and the device's erfc returns it; those few elements are computed
+    # with libm's erfc, which returns it too.
+    z = np.asarray(z, dtype=np.float64)
+    c = np.asarray(norm.cdf(z))
+    tail = (c == 0) & (z > -39)
+    if np.any(tail):
+        c = c.copy()
+        c[tail] = [0.5 * math.erfc(-v * 0.70710678118654752440) for v in z[tail].tolist()]
+    return c
 
 
 class Scaler(object):
@@ -73,11 +88,11 @@ class Scaler(object):
         if self.algo == "normal":
             return (tX - d["mu"]) / d["std"]
         if self.algo == "inv-normal":
-            return norm.cdf((tX - d["mu"]) / d["std"])
+            return _norm_cdf((tX - d["mu"]) / d["std"])
         tX = _boxcox((tX - d["min"]) / (d["max"] - d["min"]), d["boxcox"][None, :])
         if self.algo == "auto-normal":
             return (tX - d["mu"]) / d["std"]
-        return norm.cdf(tX, d["mu"], d["std"])
+        return _norm_cdf((tX - d["mu"]) / d["std"])
 
     def backward_transform(self, X):
         d = self.data

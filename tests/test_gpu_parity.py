@@ -623,7 +623,11 @@ def test_predict_y_back_transform_and_metrics_on_the_device(xalgo, yalgo, T):
     assert mu_y.shape == (T, 1) and sd_y.shape == (T, 1)
     assert np.array_equal(np.isnan(mu_y), np.isnan(mu_h)) and np.array_equal(np.isnan(sd_y), np.isnan(sd_h))
     ok = ~(np.isnan(mu_h) | np.isnan(sd_h))
-    assert ok.mean() > 0.1                                   # inv-normal targets: mu +- std outside (0, 1) is NaN on both sides
+    # inv-normal targets: mu +- std outside (0, 1) is NaN on both sides.  The rows that stay are those the host tail keeps when it is
+    # fed the CPU oracle's mu_f, std_f on these seeds (no band edge within 3e-5 of 0 or 1, so the device's last bits cannot move one)
+    kept = {('auto-inv-normal', 'auto-normal', 333): 333, ('min-max', 'min-max', 500): 500, ('normal', 'normal', 40000): 40000,
+            ('inv-normal', 'inv-normal', 257): 134, ('auto-normal', 'auto-inv-normal', 1000): 313}
+    assert ok.sum() >= kept[(xalgo, yalgo, T)], (int(ok.sum()), xalgo, yalgo, T)
     assert np.allclose(mu_y[ok], mu_h[ok], rtol=1e-9, atol=1e-12) and np.allclose(sd_y[ok], sd_h[ok], rtol=1e-8, atol=1e-12)
     for k in ref:
         assert (np.isnan(ref[k]) and np.isnan(met[k])) or abs(met[k] - ref[k]) <= 1e-8 * max(1.0, abs(ref[k])), (k, met[k], ref[k])
