@@ -25,11 +25,28 @@ def num_params(D, S, M):
     return 3 + D * S + M * S + S + M
 
 
-def _scatter(g, cols, width):
-    """(T, len(cols)) gradients -> (T, width), zero in the columns not listed"""
-    out = np.zeros((g.shape[0], width))
-    out[:, cols] = g
+def _scatter(g, cols, width, square=False):
+    """(.., len(cols)) gradients -> (.., width), zero in the columns not listed; square: (.., len(cols), len(cols)) matrices ->
+    (.., width, width), rows and columns alike"""
+    out = np.zeros(g.shape[:-1] + (width,))
+    out[..., cols] = g
+    if square:
+        g, out = out, np.zeros(g.shape[:-2] + (width, width))
+        out[..., cols, :] = g
     return out
+
+
+def _i64(a):
+    return None if a is None else a.ctypes.data_as(_lib._c_i64_p)
+
+
+def _seed(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _count(n, lo, hi):
+    """n, or 0 outside lo..hi: the library refuses such a count before it writes, so the outputs sized by it stay empty"""
+    return n if lo <= n <= hi else 0
 
 
 class PeerFailed(RuntimeError):
@@ -170,10 +187,7 @@ class HipEngine(object):
         """pred_func (SCFGP/SCFGP.py:138-148): returns mu (T,1), std (T,)."""
         self._check_xy(Xs, None, self.D)
         Xs = np.ascontiguousarray(Xs)
-        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if alpha.size != self.K or Li.shape != (self.K, self.K):
-            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
+        alpha, Li = self._factors(alpha, Li)
         T = Xs.shape[0]
         mu = np.empty((T, 1)); sd = np.empty(T)
         self._check(self.lib.scfgp_predict(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), dptr(mu), dptr(sd)), 'predict')
@@ -240,6 +254,82 @@ class HipEngine(object):
                                              dptr(met) if ys is not None else None), 'predict_y')
         return mu, sd, (dict(zip(self.METRICS, met.tolist())) if ys is not None else None)
 
+    # -- arguments of the posterior and pool entry points -------------------------------------------------
+    def _mode(self, who, table, mode, rows=True):
+        """(the library's number of `mode`, the columns the registered X scaler kept -- None where rows go in as they are); rows=False:
+        the call brings no rows, so no scaler is asked for"""
+        if mode not in table:
+            raise ValueError('%s: mode must be one of %s' % (who, sorted(table)))
+        m = table[mode]
+        cols = getattr(self, '_xcols', None) if m and rows else None
+        if m and rows and cols is None:
+            raise ValueError('%s: mode %r needs a registered X scaler (set_x_scaler)' % (who, mode))
+        return m, cols
+
+    def _raw_cols(self, who, raw):
+        """_mode for the entry points with a `raw` flag"""
+        cols = getattr(self, '_xcols', None) if raw else None
+        if raw and cols is None:
+            raise ValueError('%s: raw rows need a registered X scaler (set_x_scaler)' % who)
+        return cols
+
+    def _rows(self, X, name, cols=None):
+        """X as the library reads it: contiguous (n, D) float64, the columns `cols` of it; a copy only where one is needed"""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise TypeError('%s must be a 2-d float64 array' % name)
+        if cols is not None:
+            X = X[:, cols]
+        X = np.ascontiguousarray(X)
+        if X.shape[1] != self.D:
+            raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
+        return X
+
+    @staticmethod
+    def _weights(v, n, name):
+        """n weights (or targets) as a flat contiguous float64 array; None stays None"""
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        if v.size != n:
+            raise ValueError('%s has %d entries for %d rows' % (name, v.size, n))
+        return v
+
+    def _Li(self, Li):
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if Li.shape != (self.K, self.K):
+            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        return Li
+
+    def _factors(self, alpha, Li):
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+        Li = np.ascontiguousarray(Li, dtype=np.float64)
+        if alpha.size != self.K or Li.shape != (self.K, self.K):
+            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
+        return alpha, Li
+
+    @staticmethod
+    def _wanted(who, want, allowed, some=False):
+        """`want` as a tuple of names out of `allowed`; some: at least one (each entry point keeps its wording)"""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if some:
+            if not want or any(k not in allowed for k in want):
+                raise ValueError('%s: want must name some of %s' % (who, allowed))
+        else:
+            for k in want:
+                if k not in allowed:
+                    raise ValueError('%s: want holds %r; allowed: %s' % (who, k, allowed))
+        return want
+
+    def _check_undelivered(self, rc, who):
+        """_check for the entry points that deliver nothing when the result is not finite: -4 is an error whatever self.nonfinite says
+        (unlike an evaluation's NaN cost, which comes with its outputs).  predict, predict_raw, predict_y, predict_grad,
+        predict_gradcov, sample_weights, sample and predict_cov go through the plain _check instead, so under nonfinite = 'return'
+        they hand back what the library wrote; tests/test_engine_marshal.py pins which method does which."""
+        if rc == -4:
+            raise FloatingPointError('%s: %s' % (who, self.last_error()))
+        self._check(rc, who)
+
     PREDICT_GRAD_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
 
     def predict_grad(self, Xs, alpha, Li, mode='scaled', want_std=True):
@@ -247,31 +337,16 @@ class HipEngine(object):
         takes it; 'raw': unscaled Xs through the registered X scaler, as predict_raw; 'y': that and the y scaler, as predict_y.
         Returns mu (T,1), std (T,), dmu (T,D), dstd (T,D) (None without want_std); mu and std are those of the matching predict call, bit
         for bit.  In the 'raw' / 'y' modes dmu, dstd are (T, D_raw): the constant columns the X scaler dropped get zero gradients."""
-        if mode not in self.PREDICT_GRAD_MODES:
-            raise ValueError('predict_grad: mode must be one of %s' % sorted(self.PREDICT_GRAD_MODES))
-        m = self.PREDICT_GRAD_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('predict_grad: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        D_in = Xs.shape[1]
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
-        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if alpha.size != self.K or Li.shape != (self.K, self.K):
-            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
-        T = Xs.shape[0]
+        m, cols = self._mode('predict_grad', self.PREDICT_GRAD_MODES, mode)
+        X = self._rows(Xs, 'Xs', cols)
+        alpha, Li = self._factors(alpha, Li)
+        T = X.shape[0]
         mu = np.empty((T, 1)); sd = np.empty(T)
         dmu = np.empty((T, self.D)); dsd = np.empty((T, self.D)) if want_std else None
-        self._check(self.lib.scfgp_predict_grad(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), m, dptr(mu), dptr(sd), dptr(dmu), dptr(dsd)),
+        self._check(self.lib.scfgp_predict_grad(self.ctx, dptr(X), T, dptr(alpha), dptr(Li), m, dptr(mu), dptr(sd), dptr(dmu), dptr(dsd)),
                     'predict_grad')
         if cols is not None:
+            D_in = np.shape(Xs)[1]
             dmu, dsd = _scatter(dmu, cols, D_in), (None if dsd is None else _scatter(dsd, cols, D_in))
         return mu, sd, dmu, dsd
 
@@ -295,43 +370,19 @@ class HipEngine(object):
         call's rows (w: T weights >= 0, None: all 1).  mode 'scaled': Xs as predict takes it; 'raw': unscaled Xs through the registered
         X scaler, outputs in the D_raw raw columns with zeros for the columns the scaler dropped, as predict_grad.  Needs min(D, S) <=
         64."""
-        if mode not in self.GRADCOV_MODES:
-            raise ValueError('predict_gradcov: mode must be one of %s' % sorted(self.GRADCOV_MODES))
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(k not in self.GRADCOV_OUTPUTS for k in want):
-            raise ValueError('predict_gradcov: want must name some of %s' % (self.GRADCOV_OUTPUTS,))
-        m = self.GRADCOV_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('predict_gradcov: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        D_in = Xs.shape[1]
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        m, cols = self._mode('predict_gradcov', self.GRADCOV_MODES, mode)
+        want = self._wanted('predict_gradcov', want, self.GRADCOV_OUTPUTS, some=True)
+        X = self._rows(Xs, 'Xs', cols)
         alpha, Li = self._factors(alpha, Li)
-        T, D = Xs.shape[0], self.D
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        T, D = X.shape[0], self.D
+        w = self._weights(w, T, 'w')
         shapes = {'dmu': (T, D), 'dvar': (T, D), 'dcov': (T, D, D), 'asub': (D, D)}
         out = {k: np.empty(shapes[k]) for k in self.GRADCOV_OUTPUTS if k in want}
-        self._check(self.lib.scfgp_predict_gradcov(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), m,
+        self._check(self.lib.scfgp_predict_gradcov(self.ctx, dptr(X), T, dptr(w), dptr(alpha), dptr(Li), m,
                                                    *[dptr(out.get(k)) for k in self.GRADCOV_OUTPUTS]), 'predict_gradcov')
         if cols is not None:
             for k in out:
-                a = np.zeros(out[k].shape[:-1] + (D_in,))
-                a[..., cols] = out[k]
-                if k in ('dcov', 'asub'):                      # rows of the matrices too
-                    b = np.zeros(a.shape[:-2] + (D_in, D_in))
-                    b[..., cols, :] = a
-                    a = b
-                out[k] = a
+                out[k] = _scatter(out[k], cols, np.shape(Xs)[1], square=k in ('dcov', 'asub'))
         return out
 
     PD_MODES = {'scaled': 0, 'raw': 1}
@@ -344,88 +395,50 @@ class HipEngine(object):
         curves; all in scaled y units.  w: T weights >= 0 (None: all 1); rows of weight 0 count for 'ice' only.  mode 'scaled': Xs and the
         grid as predict takes them; 'raw': unscaled Xs through the registered X scaler, `dims` naming raw columns (none that the scaler
         dropped) and the grid in raw units of its column.  1 <= G <= 1024."""
-        if mode not in self.PD_MODES:
-            raise ValueError('predict_pd: mode must be one of %s' % sorted(self.PD_MODES))
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(k not in self.PD_OUTPUTS for k in want):
-            raise ValueError('predict_pd: want must name some of %s' % (self.PD_OUTPUTS,))
-        m = self.PD_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('predict_pd: mode %r needs a registered X scaler (set_x_scaler)' % mode)
+        m, cols = self._mode('predict_pd', self.PD_MODES, mode)
+        want = self._wanted('predict_pd', want, self.PD_OUTPUTS, some=True)
+        Xs = self._rows(Xs, 'Xs', cols)
         dims = np.asarray(dims, dtype=np.int64).reshape(-1)
         if cols is not None:
             where = {int(cc): i for i, cc in enumerate(cols)}
             if any(int(d) not in where for d in dims):
                 raise ValueError('predict_pd: dims names a column that the X scaler dropped or that does not exist')
             dims = np.array([where[int(d)] for d in dims], dtype=np.int64)
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
         grid = np.ascontiguousarray(grid, dtype=np.float64)
         if grid.ndim != 2 or grid.shape[0] != dims.size:
             raise ValueError('grid must be (ndim, G) with one row per entry of dims')
         alpha, Li = self._factors(alpha, Li)
         T, nd, G = Xs.shape[0], int(dims.size), int(grid.shape[1])
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        w = self._weights(w, T, 'w')
         dims32 = np.ascontiguousarray(dims, dtype=np.int32)
         shapes = {'pd': (nd, G), 'sd': (nd, G), 'cov': (nd, G, G), 'ice': (nd, T, G)}
         out = {k: np.empty(shapes[k]) for k in self.PD_OUTPUTS if k in want}
         rc = self.lib.scfgp_predict_pd(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), dims32.ctypes.data_as(C.POINTER(C.c_int)), nd,
                                        dptr(grid), G, m, *[dptr(out.get(k)) for k in self.PD_OUTPUTS])
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('predict_pd: %s' % self.last_error())
-        self._check(rc, 'predict_pd')
+        self._check_undelivered(rc, 'predict_pd')
         return out
 
     SAMPLE_MODES = {'scaled': 0, 'raw': 1, 'y': 2}
-
-    def _factors(self, alpha, Li):
-        alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if alpha.size != self.K or Li.shape != (self.K, self.K):
-            raise ValueError('alpha/Li have the wrong shape for K=%d' % self.K)
-        return alpha, Li
 
     def sample_weights(self, alpha, Li, nsamp, seed=0):
         """Weights of nsamp posterior sample functions (include/scfgp_hip.h: scfgp_sample_weights): W (K, nsamp) = alpha 1^T +
         sqrt(kappa) Li^T Z with Z drawn from `seed` by the library's counter-based generator; column s is the same for any nsamp."""
         alpha, Li = self._factors(alpha, Li)
         W = np.empty((self.K, int(nsamp)))
-        self._check(self.lib.scfgp_sample_weights(self.ctx, dptr(alpha), dptr(Li), int(nsamp), int(seed) & (2 ** 64 - 1), dptr(W)),
-                    'sample_weights')
+        self._check(self.lib.scfgp_sample_weights(self.ctx, dptr(alpha), dptr(Li), int(nsamp), _seed(seed), dptr(W)), 'sample_weights')
         return W
 
     def sample(self, Xs, alpha, Li, nsamp, seed=0, mode='scaled', noise=False):
         """nsamp posterior sample functions evaluated at the rows of Xs (include/scfgp_hip.h: scfgp_sample): (T, nsamp), column s =
         phi(x)^T w_s (+ sqrt(kappa) eps with noise).  mode 'scaled': Xs as predict takes it; 'raw': unscaled Xs through the registered
         X scaler, as predict_raw; 'y': that and the y scaler's backward transform of every sample, as predict_y."""
-        if mode not in self.SAMPLE_MODES:
-            raise ValueError('sample: mode must be one of %s' % sorted(self.SAMPLE_MODES))
-        m = self.SAMPLE_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('sample: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        m, cols = self._mode('sample', self.SAMPLE_MODES, mode)
+        Xs = self._rows(Xs, 'Xs', cols)
         alpha, Li = self._factors(alpha, Li)
         T = Xs.shape[0]
         out = np.empty((T, max(int(nsamp), 0)))
-        self._check(self.lib.scfgp_sample(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), int(nsamp), int(seed) & (2 ** 64 - 1), m,
-                                          int(bool(noise)), dptr(out)), 'sample')
+        self._check(self.lib.scfgp_sample(self.ctx, dptr(Xs), T, dptr(alpha), dptr(Li), int(nsamp), _seed(seed), m, int(bool(noise)),
+                                          dptr(out)), 'sample')
         return out
 
     def sample_argmax(self, Xs, alpha, Li, nsamp, seed=0, w=None, mode='scaled', minimize=False):
@@ -433,34 +446,17 @@ class HipEngine(object):
         idx[s] the lowest eligible row at which sample function s of `sample` (same seed, no noise) is largest (minimize: smallest)
         and val[s] its value there, bit for bit what `sample` returns.  w (T,): row t is eligible iff w[t] > 0 (None: every row).
         mode as in `sample`; with 'y' the row is chosen in scaled units and val is in raw y units."""
-        if mode not in self.SAMPLE_MODES:
-            raise ValueError('sample_argmax: mode must be one of %s' % sorted(self.SAMPLE_MODES))
-        m = self.SAMPLE_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('sample_argmax: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        m, cols = self._mode('sample_argmax', self.SAMPLE_MODES, mode)
+        Xs = self._rows(Xs, 'Xs', cols)
         T = Xs.shape[0]
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        w = self._weights(w, T, 'w')
         alpha, Li = self._factors(alpha, Li)
         nsamp = int(nsamp)
-        n = nsamp if 0 < nsamp <= 1024 else 0                   # out of range: the library refuses before it writes
+        n = _count(nsamp, 1, 1024)
         idx = np.empty(n, dtype=np.int64); val = np.empty(n)
-        rc = self.lib.scfgp_sample_argmax(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), nsamp, int(seed) & (2 ** 64 - 1), m,
-                                          int(bool(minimize)), idx.ctypes.data_as(_lib._c_i64_p), dptr(val))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('sample_argmax: %s' % self.last_error())
-        self._check(rc, 'sample_argmax')
+        rc = self.lib.scfgp_sample_argmax(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), nsamp, _seed(seed), m, int(bool(minimize)),
+                                          _i64(idx), dptr(val))
+        self._check_undelivered(rc, 'sample_argmax')
         return idx, val
 
     ACQUIRE_KINDS = {'ucb': 0, 'pi': 1, 'ei': 2, 'logei': 3, 'mes': 4}
@@ -477,30 +473,12 @@ class HipEngine(object):
         scaler dropped a constant column).  Returns a dict with the keys asked for ('argmax' gives 'idx' and 'val')."""
         if kind not in self.ACQUIRE_KINDS:
             raise ValueError('acquire: kind must be one of %s' % sorted(self.ACQUIRE_KINDS))
-        if mode not in self.ACQUIRE_MODES:
-            raise ValueError('acquire: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for k in want:
-            if k not in self.ACQUIRE_WANT:
-                raise ValueError('acquire: want holds %r; allowed: %s' % (k, self.ACQUIRE_WANT))
-        k, m = self.ACQUIRE_KINDS[kind], self.ACQUIRE_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('acquire: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        D_in = Xs.shape[1]
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
-        T = Xs.shape[0]
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        m, cols = self._mode('acquire', self.ACQUIRE_MODES, mode)
+        want = self._wanted('acquire', want, self.ACQUIRE_WANT)
+        k = self.ACQUIRE_KINDS[kind]
+        X = self._rows(Xs, 'Xs', cols)
+        T = X.shape[0]
+        w = self._weights(w, T, 'w')
         alpha, Li = self._factors(alpha, Li)
         if k == 0:
             if beta is None:
@@ -521,12 +499,10 @@ class HipEngine(object):
         mu = np.empty(T) if 'mu' in want else None
         sd = np.empty(T) if 'sd' in want else None
         grad = np.empty((T, self.D)) if 'grad' in want else None
-        rc = self.lib.scfgp_acquire(self.ctx, dptr(Xs), T, dptr(w), dptr(alpha), dptr(Li), k, dptr(par), 0 if par is None else par.size,
+        rc = self.lib.scfgp_acquire(self.ctx, dptr(X), T, dptr(w), dptr(alpha), dptr(Li), k, dptr(par), 0 if par is None else par.size,
                                     dptr(fstar), 0 if fstar is None else fstar.size, m, int(bool(noise)), int(bool(minimize)), dptr(acq),
-                                    None if idx is None else idx.ctypes.data_as(_lib._c_i64_p), dptr(val), dptr(mu), dptr(sd), dptr(grad))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('acquire: %s' % self.last_error())
-        self._check(rc, 'acquire')
+                                    _i64(idx), dptr(val), dptr(mu), dptr(sd), dptr(grad))
+        self._check_undelivered(rc, 'acquire')
         if acq is not None:
             out['acq'] = acq
         if idx is not None:
@@ -536,22 +512,11 @@ class HipEngine(object):
         if sd is not None:
             out['sd'] = sd
         if grad is not None:
-            out['grad'] = _scatter(grad, cols, D_in) if cols is not None else grad
+            out['grad'] = _scatter(grad, cols, np.shape(Xs)[1]) if cols is not None else grad
         return out
 
     KG_WANT = ('kg', 'kg_hi', 'idx', 'val', 'm', 's')
     KG_DEFAULT_NODES = np.linspace(-5.0, 5.0, 31)
-
-    def _kg_rows(self, X, cols, name):
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 2:
-            raise TypeError('%s must be a 2-d float64 array' % name)
-        if cols is not None:
-            X = X[:, cols]
-        X = np.ascontiguousarray(X)
-        if X.shape[1] != self.D:
-            raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
-        return X
 
     def acquire_kg(self, Xc, alpha, Li, Xr=None, z=None, w=None, mode='scaled', noise=True, minimize=False, want=('kg', 'idx', 'val')):
         """Knowledge gradient of the candidates Xc (T, D) over the reference rows Xr (R <= 32768 rows; None: the candidates themselves,
@@ -560,30 +525,19 @@ class HipEngine(object):
         row t is eligible iff w[t] > 0.  mode 'scaled' or 'raw' (Xc and Xr through the registered X scaler).  want: any of 'kg' (T,: the
         lower bound), 'kg_hi' (T,: the upper bound), 'idx' (the lowest eligible row with the largest kg), 'val' (its kg; needs 'idx'),
         'm', 's' ((T, J) each: the node table).  Returns a dict with the keys asked for."""
-        if mode not in self.ACQUIRE_MODES:
-            raise ValueError('acquire_kg: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
-        want = (want,) if isinstance(want, str) else tuple(want)
-        for k in want:
-            if k not in self.KG_WANT:
-                raise ValueError('acquire_kg: want holds %r; allowed: %s' % (k, self.KG_WANT))
-        md = self.ACQUIRE_MODES[mode]
-        cols = getattr(self, '_xcols', None) if md else None
-        if md and cols is None:
-            raise ValueError('acquire_kg: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        Xc = self._kg_rows(Xc, cols, 'Xc')
+        md, cols = self._mode('acquire_kg', self.ACQUIRE_MODES, mode)
+        want = self._wanted('acquire_kg', want, self.KG_WANT)
+        Xc = self._rows(Xc, 'Xc', cols)
         T = Xc.shape[0]
         R = 0
         if Xr is not None:
-            Xr = self._kg_rows(Xr, cols, 'Xr')
+            Xr = self._rows(Xr, 'Xr', cols)
             R = Xr.shape[0]
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        w = self._weights(w, T, 'w')
         z = np.ascontiguousarray(self.KG_DEFAULT_NODES if z is None else z, dtype=np.float64).reshape(-1)
         J = z.size
         alpha, Li = self._factors(alpha, Li)
-        nj = J if 3 <= J <= 32 else 0                           # out of range: the library refuses before it writes
+        nj = _count(J, 3, 32)
         kg = np.empty(T) if 'kg' in want else None
         hi = np.empty(T) if 'kg_hi' in want else None
         idx = np.empty(1, dtype=np.int64) if 'idx' in want else None
@@ -591,11 +545,8 @@ class HipEngine(object):
         m = np.empty((T, nj)) if 'm' in want else None
         s = np.empty((T, nj)) if 's' in want else None
         rc = self.lib.scfgp_acquire_kg(self.ctx, dptr(Xc), T, dptr(w), dptr(Xr), R, dptr(alpha), dptr(Li), dptr(z), J, md, int(bool(noise)),
-                                       int(bool(minimize)), dptr(kg), dptr(hi), None if idx is None else idx.ctypes.data_as(_lib._c_i64_p),
-                                       dptr(val), dptr(m), dptr(s))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('acquire_kg: %s' % self.last_error())
-        self._check(rc, 'acquire_kg')
+                                       int(bool(minimize)), dptr(kg), dptr(hi), _i64(idx), dptr(val), dptr(m), dptr(s))
+        self._check_undelivered(rc, 'acquire_kg')
         out = {}
         for k, a in (('kg', kg), ('kg_hi', hi), ('m', m), ('s', s)):
             if a is not None:
@@ -613,38 +564,22 @@ class HipEngine(object):
         predict_grad: 'raw' chains grad through the X scaler and returns (T, D_raw) with zero columns where the scaler dropped a
         constant column; 'y' also maps val through the y scaler's backward transform and grad through its derivative.  val is None
         without want_val."""
-        if mode not in self.SAMPLE_MODES:
-            raise ValueError('sample_grad: mode must be one of %s' % sorted(self.SAMPLE_MODES))
-        m = self.SAMPLE_MODES[mode]
-        Xs = np.asarray(Xs, dtype=np.float64)
-        if Xs.ndim != 2:
-            raise TypeError('Xs must be a 2-d float64 array')
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('sample_grad: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        D_in = Xs.shape[1]
-        if cols is not None:
-            Xs = Xs[:, cols]
-        Xs = np.ascontiguousarray(Xs)
-        if Xs.shape[1] != self.D:
-            raise ValueError('Xs has %d columns, expected %d' % (Xs.shape[1], self.D))
+        m, cols = self._mode('sample_grad', self.SAMPLE_MODES, mode)
+        X = self._rows(Xs, 'Xs', cols)
         W = np.ascontiguousarray(W, dtype=np.float64)
         if W.ndim != 2 or W.shape[0] != self.K:
             raise ValueError('W must be (K, nsamp) with K=%d' % self.K)
-        T, nsamp = Xs.shape[0], W.shape[1]
+        T, nsamp = X.shape[0], W.shape[1]
         if sidx is not None:
             sidx = np.ascontiguousarray(sidx, dtype=np.int64).reshape(-1)
             if sidx.size != T:
                 raise ValueError('sidx has %d entries for %d rows' % (sidx.size, T))
         val = np.empty(T) if want_val else None
         grad = np.empty((T, self.D))
-        rc = self.lib.scfgp_sample_grad(self.ctx, dptr(Xs), T, dptr(W), nsamp, None if sidx is None else sidx.ctypes.data_as(_lib._c_i64_p),
-                                        m, dptr(val), dptr(grad))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('sample_grad: %s' % self.last_error())
-        self._check(rc, 'sample_grad')
+        rc = self.lib.scfgp_sample_grad(self.ctx, dptr(X), T, dptr(W), nsamp, _i64(sidx), m, dptr(val), dptr(grad))
+        self._check_undelivered(rc, 'sample_grad')
         if cols is not None:
-            grad = _scatter(grad, cols, D_in)
+            grad = _scatter(grad, cols, np.shape(Xs)[1])
         return val, grad
 
     PREDICT_COV_MODES = {'scaled': 0, 'raw': 1}
@@ -654,32 +589,14 @@ class HipEngine(object):
         (Ta, Tb) float64, cov[i][j] = kappa <Li phi(a_i), Li phi(b_j)>, in the units of the scaled target.  Xb=None is the symmetric
         form (Ta, Ta), symmetric bit for bit; noise=True (symmetric form only) adds kappa to its diagonal.  mode 'scaled': inputs as
         predict takes them; 'raw': unscaled inputs through the registered X scaler, as predict_raw."""
-        if mode not in self.PREDICT_COV_MODES:
-            raise ValueError('predict_cov: mode must be one of %s' % sorted(self.PREDICT_COV_MODES))
-        m = self.PREDICT_COV_MODES[mode]
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('predict_cov: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-
-        def rows(X, name):
-            X = np.asarray(X, dtype=np.float64)
-            if X.ndim != 2:
-                raise TypeError('%s must be a 2-d float64 array' % name)
-            if cols is not None:
-                X = X[:, cols]
-            X = np.ascontiguousarray(X)
-            if X.shape[1] != self.D:
-                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
-            return X
-        Xa = rows(Xa, 'Xa')
-        Xb = None if Xb is None else rows(Xb, 'Xb')
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if Li.shape != (self.K, self.K):
-            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        m, cols = self._mode('predict_cov', self.PREDICT_COV_MODES, mode)
+        Xa = self._rows(Xa, 'Xa', cols)
+        Xb = None if Xb is None else self._rows(Xb, 'Xb', cols)
+        Li = self._Li(Li)
         Ta, Tb = Xa.shape[0], (Xa.shape[0] if Xb is None else Xb.shape[0])
         if Xb is not None and Tb == 0:
             raise ValueError('predict_cov: Xb has no rows')           # an empty array has no pointer to tell it from Xb=None
-        cov = np.empty((Ta, Tb) if 0 < Tb <= 32768 else (0, 0))       # out of range: the library refuses before it writes
+        cov = np.empty((Ta, Tb) if _count(Tb, 1, 32768) else (0, 0))
         self._check(self.lib.scfgp_predict_cov(self.ctx, dptr(Xa), Ta, dptr(Xb), Tb, dptr(Li), m, int(bool(noise)), dptr(cov)),
                     'predict_cov')
         return cov
@@ -828,31 +745,15 @@ class HipEngine(object):
         return dict(zip(self.CONDITION, out.tolist()))
 
     def _condition(self, Xn, yn, alpha, Li, mode):
-        if mode not in self.CONDITION_MODES:
-            raise ValueError('condition: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        m, cols = self._mode('condition', self.CONDITION_MODES, mode)
         if Xn is None or yn is None or alpha is None or Li is None:
             raise ValueError('condition: Xn, yn, alpha and Li are all needed')
-        m = self.CONDITION_MODES[mode]
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('condition: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        Xn = np.asarray(Xn, dtype=np.float64)
-        if Xn.ndim != 2:
-            raise TypeError('Xn must be a 2-d float64 array')
-        if cols is not None:
-            Xn = Xn[:, cols]
-        Xn = np.ascontiguousarray(Xn)
-        if Xn.shape[1] != self.D:
-            raise ValueError('Xn has %d columns, expected %d' % (Xn.shape[1], self.D))
-        yn = np.ascontiguousarray(yn, dtype=np.float64).reshape(-1)
-        if yn.size != Xn.shape[0]:
-            raise ValueError('yn has %d entries for %d rows' % (yn.size, Xn.shape[0]))
+        Xn = self._rows(Xn, 'Xn', cols)
+        yn = self._weights(yn, Xn.shape[0], 'yn')
         alpha, Li = self._factors(alpha, Li)
         alpha_out = np.empty((self.K, 1)); Li_out = np.empty((self.K, self.K))
         rc = self.lib.scfgp_condition(self.ctx, dptr(Xn), dptr(yn), Xn.shape[0], dptr(alpha), dptr(Li), m, dptr(alpha_out), dptr(Li_out))
-        if rc == -4:                # nothing was delivered (unlike an evaluation's NaN cost): an error whatever self.nonfinite says
-            raise FloatingPointError('condition: %s' % self.last_error())
-        self._check(rc, 'condition')
+        self._check_undelivered(rc, 'condition')
         return alpha_out, Li_out
 
     FORGET_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'log_joint', 'min_pivot2', 'blocks')
@@ -863,28 +764,14 @@ class HipEngine(object):
         stats dict), the held-out predictions of the removed rows under that fit -- bit for bit predict(X, alpha', Li') -- and
         FORGET_STATS with e = y - mu; with factors=False Li' never leaves the device.  Both: (alpha', Li', mu, std, stats).  mode
         'scaled': X as predict takes it; 'raw': unscaled X through the registered X scaler.  y (n,) or (n,1) is the SCALED target."""
-        if mode not in self.CONDITION_MODES:
-            raise ValueError('forget: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        m, cols = self._mode('forget', self.CONDITION_MODES, mode)
         if X is None or y is None or alpha is None or Li is None:
             raise ValueError('forget: X, y, alpha and Li are all needed')
         if not factors and not predict:
             raise ValueError('forget: nothing asked for (factors and predict are both False)')
-        m = self.CONDITION_MODES[mode]
-        cols = getattr(self, '_xcols', None) if m else None
-        if m and cols is None:
-            raise ValueError('forget: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 2:
-            raise TypeError('X must be a 2-d float64 array')
-        if cols is not None:
-            X = X[:, cols]
-        X = np.ascontiguousarray(X)
-        if X.shape[1] != self.D:
-            raise ValueError('X has %d columns, expected %d' % (X.shape[1], self.D))
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        if y.size != X.shape[0]:
-            raise ValueError('y has %d entries for %d rows' % (y.size, X.shape[0]))
+        X = self._rows(X, 'X', cols)
         n = X.shape[0]
+        y = self._weights(y, n, 'y')
         alpha, Li = self._factors(alpha, Li)
         alpha_out = np.empty((self.K, 1)) if factors else None
         Li_out = np.empty((self.K, self.K)) if factors else None
@@ -893,9 +780,7 @@ class HipEngine(object):
         stats = np.zeros(8) if predict else None
         rc = self.lib.scfgp_forget(self.ctx, dptr(X), dptr(y), n, dptr(alpha), dptr(Li), m, dptr(alpha_out), dptr(Li_out), dptr(mu), dptr(sd),
                                    dptr(stats))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('forget: %s' % self.last_error())
-        self._check(rc, 'forget')
+        self._check_undelivered(rc, 'forget')
         out = (alpha_out, Li_out) if factors else ()
         if predict:
             st = dict(zip(self.FORGET_STATS, stats.tolist()))
@@ -911,40 +796,24 @@ class HipEngine(object):
         the `block` consecutive rows of its block ([j block, (j+1) block); block 1: leave-one-out); lev is the leverage h_i.  X=None and
         y=None: the rows made resident by set_data.  mode 'scaled': X as predict takes it; 'raw': unscaled X through the registered X
         scaler.  y (n,) or (n,1) is the SCALED target in either mode.  stats: LOO_STATS, sums over the call's rows with e = y - mu."""
-        if mode not in self.CONDITION_MODES:
-            raise ValueError('loo: mode must be one of %s' % sorted(self.CONDITION_MODES))
+        m, cols = self._mode('loo', self.CONDITION_MODES, mode, rows=X is not None)
         if alpha is None or Li is None:
             raise ValueError('loo: alpha and Li are needed')
         if (X is None) != (y is None):
             raise ValueError('loo: X and y go together (both None: the resident rows)')
-        m = self.CONDITION_MODES[mode]
         alpha, Li = self._factors(alpha, Li)
         if X is None:
             d = (C.c_int64 * 8)()
             self._check(self.lib.scfgp_get_dims(self.ctx, d, 8), 'get_dims')
             n = int(d[7])                                   # the rows made resident by set_data (0: the library refuses)
         else:
-            cols = getattr(self, '_xcols', None) if m else None
-            if m and cols is None:
-                raise ValueError('loo: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-            X = np.asarray(X, dtype=np.float64)
-            if X.ndim != 2:
-                raise TypeError('X must be a 2-d float64 array')
-            if cols is not None:
-                X = X[:, cols]
-            X = np.ascontiguousarray(X)
-            if X.shape[1] != self.D:
-                raise ValueError('X has %d columns, expected %d' % (X.shape[1], self.D))
-            y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-            if y.size != X.shape[0]:
-                raise ValueError('y has %d entries for %d rows' % (y.size, X.shape[0]))
+            X = self._rows(X, 'X', cols)
             n = X.shape[0]
+            y = self._weights(y, n, 'y')
         mu = np.empty((n, 1)); sd = np.empty(n); lev = np.empty(n); stats = np.zeros(8)
         rc = self.lib.scfgp_loo(self.ctx, dptr(X), dptr(y), n, dptr(alpha), dptr(Li), m, int(block), dptr(mu), dptr(sd), dptr(lev),
                                 dptr(stats))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('loo: %s' % self.last_error())
-        self._check(rc, 'loo')
+        self._check_undelivered(rc, 'loo')
         out = dict(zip(self.LOO_STATS, stats.tolist()))
         out['n'] = int(out['n']); out['blocks'] = int(out['blocks'])
         return mu, sd, lev, out
@@ -956,34 +825,16 @@ class HipEngine(object):
         std_after: what predict reports as std at every pool row once the picks have been observed (condition), whatever their
         targets.  w (T,): non-negative weights of the criterion, 0 excludes a row.  raw: unscaled Xc through the registered X scaler,
         as predict_raw.  Only Li is needed; condition on pending points first, with any targets."""
-        cols = getattr(self, '_xcols', None) if raw else None
-        if raw and cols is None:
-            raise ValueError('select: raw rows need a registered X scaler (set_x_scaler)')
-        Xc = np.asarray(Xc, dtype=np.float64)
-        if Xc.ndim != 2:
-            raise TypeError('Xc must be a 2-d float64 array')
-        if cols is not None:
-            Xc = Xc[:, cols]
-        Xc = np.ascontiguousarray(Xc)
-        if Xc.shape[1] != self.D:
-            raise ValueError('Xc has %d columns, expected %d' % (Xc.shape[1], self.D))
+        Xc = self._rows(Xc, 'Xc', self._raw_cols('select', raw))
         T = Xc.shape[0]
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if Li.shape != (self.K, self.K):
-            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        w = self._weights(w, T, 'w')
+        Li = self._Li(Li)
         m = int(m)
-        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
+        n = _count(m, 1, 4096)
         idx = np.empty(n, dtype=np.int64); var = np.empty(n); gain = np.empty(n)
         sd = np.empty(T) if return_std else None
-        rc = self.lib.scfgp_select(self.ctx, dptr(Xc), T, dptr(w), dptr(Li), m, int(bool(raw)), idx.ctypes.data_as(_lib._c_i64_p),
-                                   dptr(var), dptr(gain), dptr(sd))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('select: %s' % self.last_error())
-        self._check(rc, 'select')
+        rc = self.lib.scfgp_select(self.ctx, dptr(Xc), T, dptr(w), dptr(Li), m, int(bool(raw)), _i64(idx), dptr(var), dptr(gain), dptr(sd))
+        self._check_undelivered(rc, 'select')
         return (idx, var, gain, sd) if return_std else (idx, var, gain)
 
     def select_iv(self, Xc, Li, m, Xr=None, w=None, wr=None, raw=False, return_std=False):
@@ -993,45 +844,20 @@ class HipEngine(object):
         when it was picked, ivar = (integrated variance before the picks, after them), all in scaled-y units, noise excluded.  Xr
         None: the pool is its own reference (wr then has T entries).  w (T,): non-negative weights of the criterion, 0 excludes a row;
         wr: non-negative weights of the reference rows.  raw: unscaled Xc and Xr through the registered X scaler."""
-        cols = getattr(self, '_xcols', None) if raw else None
-        if raw and cols is None:
-            raise ValueError('select_iv: raw rows need a registered X scaler (set_x_scaler)')
-
-        def rows_of(X, name):
-            X = np.asarray(X, dtype=np.float64)
-            if X.ndim != 2:
-                raise TypeError('%s must be a 2-d float64 array' % name)
-            if cols is not None:
-                X = X[:, cols]
-            X = np.ascontiguousarray(X)
-            if X.shape[1] != self.D:
-                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
-            return X
-
-        def weights_of(v, n, name):
-            if v is None:
-                return None
-            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-            if v.size != n:
-                raise ValueError('%s has %d entries for %d rows' % (name, v.size, n))
-            return v
-        Xc = rows_of(Xc, 'Xc')
+        cols = self._raw_cols('select_iv', raw)
+        Xc = self._rows(Xc, 'Xc', cols)
         T = Xc.shape[0]
-        Xr = None if Xr is None else rows_of(Xr, 'Xr')
+        Xr = None if Xr is None else self._rows(Xr, 'Xr', cols)
         R = T if Xr is None else Xr.shape[0]
-        w = weights_of(w, T, 'w'); wr = weights_of(wr, R, 'wr')
-        Li = np.ascontiguousarray(Li, dtype=np.float64)
-        if Li.shape != (self.K, self.K):
-            raise ValueError('Li has the wrong shape for K=%d' % self.K)
+        w = self._weights(w, T, 'w'); wr = self._weights(wr, R, 'wr')
+        Li = self._Li(Li)
         m = int(m)
-        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
+        n = _count(m, 1, 4096)
         idx = np.empty(n, dtype=np.int64); red = np.empty(n); var = np.empty(n); ivar = np.empty(2)
         sd = np.empty(T) if return_std else None
-        rc = self.lib.scfgp_select_iv(self.ctx, dptr(Xc), T, dptr(w), dptr(Xr), R, dptr(wr), dptr(Li), m, int(bool(raw)),
-                                      idx.ctypes.data_as(_lib._c_i64_p), dptr(red), dptr(var), dptr(ivar), dptr(sd))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('select_iv: %s' % self.last_error())
-        self._check(rc, 'select_iv')
+        rc = self.lib.scfgp_select_iv(self.ctx, dptr(Xc), T, dptr(w), dptr(Xr), R, dptr(wr), dptr(Li), m, int(bool(raw)), _i64(idx),
+                                      dptr(red), dptr(var), dptr(ivar), dptr(sd))
+        self._check_undelivered(rc, 'select_iv')
         return (idx, red, var, ivar, sd) if return_std else (idx, red, var, ivar)
 
     def select_qei(self, Xc, alpha, Li, m, nsamp, best, xi=0.0, seed=0, w=None, pending=None, mode='scaled', minimize=False,
@@ -1043,43 +869,21 @@ class HipEngine(object):
         pending (np, D): rows chosen earlier and not yet observed, in the pool's mode; w (T,): row t is eligible iff w[t] > 0.  qei =
         (q-EI of the pending rows alone, q-EI of pending rows plus picks); score0: the one-point Monte-Carlo EI of every row given the
         pending rows; mstate: the per-sample running maximum after the last pick.  mode 'scaled' or 'raw'."""
-        if mode not in self.ACQUIRE_MODES:
-            raise ValueError('select_qei: mode must be one of %s' % sorted(self.ACQUIRE_MODES))
-        md = self.ACQUIRE_MODES[mode]
-        cols = getattr(self, '_xcols', None) if md else None
-        if md and cols is None:
-            raise ValueError('select_qei: mode %r needs a registered X scaler (set_x_scaler)' % mode)
-
-        def rows_of(X, name):
-            X = np.asarray(X, dtype=np.float64)
-            if X.ndim != 2:
-                raise TypeError('%s must be a 2-d float64 array' % name)
-            if cols is not None:
-                X = X[:, cols]
-            X = np.ascontiguousarray(X)
-            if X.shape[1] != self.D:
-                raise ValueError('%s has %d columns, expected %d' % (name, X.shape[1], self.D))
-            return X
-        Xc = rows_of(Xc, 'Xc')
+        md, cols = self._mode('select_qei', self.ACQUIRE_MODES, mode)
+        Xc = self._rows(Xc, 'Xc', cols)
         T = Xc.shape[0]
-        Xp = None if pending is None or len(pending) == 0 else rows_of(pending, 'pending')
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
-            if w.size != T:
-                raise ValueError('w has %d entries for %d rows' % (w.size, T))
+        Xp = None if pending is None or len(pending) == 0 else self._rows(pending, 'pending', cols)
+        w = self._weights(w, T, 'w')
         alpha, Li = self._factors(alpha, Li)
         m, nsamp = int(m), int(nsamp)
-        n = m if 0 < m <= 4096 else 0                           # out of range: the library refuses before it writes
-        ns = nsamp if 0 < nsamp <= 1024 else 0
+        n = _count(m, 1, 4096)
         idx = np.empty(n, dtype=np.int64); gain = np.empty(n); qei = np.empty(2)
         score0 = np.empty(T) if return_score0 else None
-        mstate = np.empty(ns) if return_state else None
+        mstate = np.empty(_count(nsamp, 1, 1024)) if return_state else None
         rc = self.lib.scfgp_select_qei(self.ctx, dptr(Xc), T, dptr(w), dptr(Xp), 0 if Xp is None else Xp.shape[0], dptr(alpha), dptr(Li),
-                                       nsamp, int(seed) & (2 ** 64 - 1), float(best), float(xi), m, md, int(bool(minimize)),
-                                       idx.ctypes.data_as(_lib._c_i64_p), dptr(gain), dptr(score0), dptr(mstate), dptr(qei))
-        if rc == -4:                # nothing was delivered: an error whatever self.nonfinite says
-            raise FloatingPointError('select_qei: %s' % self.last_error())
-        self._check(rc, 'select_qei')
+                                       nsamp, _seed(seed), float(best), float(xi), m, md, int(bool(minimize)), _i64(idx), dptr(gain),
+                                       dptr(score0), dptr(mstate), dptr(qei))
+        self._check_undelivered(rc, 'select_qei')
         out = (idx, gain, qei)
         if return_score0:
             out += (score0,)

@@ -261,9 +261,7 @@ class SCFGP(object):
         """Predictions and their gradients in the inputs, in raw X and raw y units: mu_y (T,1), std_y (T,1), dmu_y (T,D), dstd_y (T,D)
         with D the raw column count (zero columns where the X scaler dropped a constant column).  mu_y, std_y are those of
         predict(Xs) with device_scaler=True, bit for bit."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('predict_grad needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('predict_grad')
         mu_y, std_y, dmu_y, dstd_y = owner.pred_grad_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li)
         return mu_y, std_y[:, None], dmu_y, dstd_y
 
@@ -273,9 +271,7 @@ class SCFGP(object):
         standard deviations; D the raw column count (zeros where the X scaler dropped a constant column).  There are no raw-y units:
         through a non-affine y scaler the gradient is not Gaussian, the argument of predict_cov (include/scfgp_hip.h:
         scfgp_predict_gradcov)."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('predict_gradcov needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('predict_gradcov')
         out = owner.pred_gradcov_raw(Xs, self.X_scaler, self.alpha, self.Li, want=('dmu', 'dvar') + (('dcov',) if full else ()))
         res = (out['dmu'], np.sqrt(out['dvar']))
         return res + (out['dcov'],) if full else res
@@ -285,9 +281,7 @@ class SCFGP(object):
         eigenvectors (D,D) in columns, asub (D,D)) of asub = E[grad f grad f^T] averaged over the rows -- the posterior mean of the
         gradient's outer product, sum_t w_t (m_t m_t^T + Sigma_t) / sum_t w_t, formed on the device without a (T,D,D) array; the
         eigendecomposition of the D x D matrix runs on the host.  Raw X units, scaled target units."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('active_subspace needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('active_subspace')
         asub = owner.pred_gradcov_raw(Xs, self.X_scaler, self.alpha, self.Li, w=w, want=('asub',))['asub']
         lam, vec = np.linalg.eigh(asub)
         return lam[::-1].copy(), vec[:, ::-1].copy(), asub
@@ -302,9 +296,7 @@ class SCFGP(object):
         (ndim, G).  weights: T row weights >= 0.  pd, sd, cov and ice are in the SCALED target's units: the y scaler's backward transform
         is not affine, so a PD curve in raw y units is not Gaussian -- the argument of predict_cov and acquire (include/scfgp_hip.h:
         scfgp_predict_pd)."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('partial_dependence needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('partial_dependence')
         X = np.asarray(X, dtype=np.float64)
         kept = [int(cc) for cc in self.X_scaler.data['cols']]
         dims = kept if dims is None else [int(d) for d in np.atleast_1d(dims)]
@@ -327,9 +319,7 @@ class SCFGP(object):
         """nsamples posterior sample functions of the fitted model at the raw rows Xs, in raw y units: (T, nsamples).  Column s is
         phi(x)^T w_s with w_s ~ N(alpha, kappa A^-1) (plus observation noise with noise=True), mapped through the y scaler's backward
         transform; the same seed gives the same functions on any rows (include/scfgp_hip.h: scfgp_sample)."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('sample needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('sample')
         return owner.sample_y(Xs, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, noise=noise)
 
     def sample_argmax(self, X_pool, nsamples, seed=0, weights=None, minimize=False):
@@ -339,9 +329,7 @@ class SCFGP(object):
         (include/scfgp_hip.h: scfgp_sample_argmax).  weights (T,): row t is eligible iff weights[t] > 0.  The row is chosen in scaled
         y units; ties go to the lowest index.  val is a draw of the maximum f* (max-value entropy search), and the share of samples
         that name a row estimates its probability of being the best."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('sample_argmax needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('sample_argmax')
         return owner.sample_argmax_y(X_pool, self.X_scaler, self.y_scaler, self.alpha, self.Li, nsamples, seed=seed, weights=weights,
                                      minimize=minimize)
 
@@ -383,9 +371,7 @@ class SCFGP(object):
         gtol max(1, |value|) within max_iter iterations).  In scaled units no value is worse than at its start row.  Nothing of the
         model is touched."""
         from .ascent import ascend
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('sample_maximize needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('sample_maximize')
         X_pool = np.asarray(X_pool, dtype=np.float64)
         nsamples = int(nsamples)
         idx, _ = self.sample_argmax(X_pool, nsamples, seed=seed, weights=weights, minimize=minimize)
@@ -420,7 +406,7 @@ class SCFGP(object):
                     break
         return np.array(picked, dtype=np.int64)
 
-    def _acquire_owner(self, who):
+    def _owner(self, who):
         owner = getattr(self.pred_func, '__self__', None)
         if not isinstance(owner, CompiledFuncs):
             raise TypeError('%s needs the library\'s pred_func (build_hip_models / fit); got %r' % (who, self.pred_func))
@@ -436,7 +422,7 @@ class SCFGP(object):
         in raw y has no closed form.  grad is d acq / d x with x in raw X units.  The acquisition is always maximised;
         minimize says that small targets are good.  noise: use the predictive std sigma* instead of the latent sigma_f.  Returns the
         dict of engine.acquire (want: 'acq', 'argmax' -> 'idx', 'val', 'mu', 'sd', 'grad')."""
-        owner = self._acquire_owner('acquire')
+        owner = self._owner('acquire')
         kw = dict(w=weights, noise=noise, minimize=minimize, want=want)
         if kind == 'ucb':
             kw['beta'] = beta
@@ -453,14 +439,14 @@ class SCFGP(object):
         (None: linspace(-5, 5, 31)).  noise: the observation is noisy (the normal case).  minimize: small targets are good.  Returns a
         dict: 'kg' (T,) a lower and 'kg_hi' (T,) an upper bound of the exact value -- their gap certifies the nodes -- and 'idx',
         'val': the lowest eligible row (weights > 0) with the largest kg, and that kg."""
-        owner = self._acquire_owner('kg')
+        owner = self._owner('kg')
         return owner.acquire_kg_raw(X_pool, self.X_scaler, self.alpha, self.Li, Xr_raw=X_ref, z=nodes, w=weights, noise=noise,
                                     minimize=minimize, want=('kg', 'kg_hi', 'idx', 'val'))
 
     def mes(self, X_pool, nsamples, seed=0, weights=None, minimize=False):
         """Max-value entropy search over the raw pool: one sample_argmax call for nsamples draws of the maximum f* in scaled y units,
         then acquire('mes') on the same pool.  Returns acquire's dict with 'fstar' added."""
-        owner = self._acquire_owner('mes')
+        owner = self._owner('mes')
         _, fstar = owner.sample_argmax_raw(X_pool, self.X_scaler, self.alpha, self.Li, int(nsamples), seed=seed, weights=weights,
                                            minimize=minimize)
         out = self.acquire(X_pool, 'mes', fstar=fstar, weights=weights, minimize=minimize)
@@ -475,7 +461,7 @@ class SCFGP(object):
         points inside the bounds, val (n,) the acquisition values there (scaled units), idx_start (n,) the pool rows the ascents started
         from (descending value), converged (n,) bool; n = min(starts, distinct eligible rows).  No value is below its start row's."""
         from .ascent import ascend
-        owner = self._acquire_owner('acquire_maximize')
+        owner = self._owner('acquire_maximize')
         X_pool = np.asarray(X_pool, dtype=np.float64)
         kw = dict(noise=noise, minimize=minimize)
         if kind == 'ucb':
@@ -501,9 +487,7 @@ class SCFGP(object):
         CDF), so no covariance in raw y units follows from the model.  For joint statistics of raw y draw functions with `sample`.
         noise=True (Xs2=None only) adds the observation noise kappa to the diagonal; the diagonal then equals the squared scaled
         std that pred_func reports (include/scfgp_hip.h: scfgp_predict_cov)."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('predict_cov needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('predict_cov')
         return owner.pred_cov_raw(Xs, self.X_scaler, self.Li, Xb_raw=Xs2, noise=noise)
 
     def condition(self, X, y):
@@ -512,9 +496,7 @@ class SCFGP(object):
         that needs no old rows (include/scfgp_hip.h: scfgp_condition) -- so it works on a model restored by load() that never saw
         set_data.  The scalers are the fitted ones: they are not refitted.  self.X / self.y are NOT touched: a later optimize() or
         set_data() recomputes the factors from the training set it holds, without the absorbed rows.  Returns self."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('condition needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('condition')
         ys = np.asarray(self.y_scaler.forward_transform(np.asarray(y, dtype=np.float64).reshape(-1, 1)), dtype=np.float64)
         self.alpha, self.Li = owner.condition_raw(X, ys, self.X_scaler, self.alpha, self.Li)
         return self
@@ -526,9 +508,7 @@ class SCFGP(object):
         the two alternate.  Units, scalers and what is left alone are as in condition: the scalers are not refitted and self.X /
         self.y are NOT touched.  Rows that were not in the fit raise the library's 'not positive definite' error (or, if few, go
         unnoticed: the library cannot check membership).  Returns self."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('forget needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('forget')
         ys = np.asarray(self.y_scaler.forward_transform(np.asarray(y, dtype=np.float64).reshape(-1, 1)), dtype=np.float64)
         self.alpha, self.Li = owner.forget_raw(X, ys, self.X_scaler, self.alpha, self.Li)
         return self
@@ -544,9 +524,7 @@ class SCFGP(object):
         metrics['CV_LPD'] is the mean log predictive density of the scaled targets and 'CV_LOG_JOINT' the sum of the folds' joint log
         densities; fold_stats is the list of the folds' stats (engine.FORGET_STATS, scaled units) with 'fold' (its id) added, in
         ascending id order.  Neither self.evals nor self.alpha / self.Li are touched."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('cv needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('cv')
         if (X is None) != (y is None):
             raise ValueError('cv: X and y go together (both None: the training set)')
         if X is None:
@@ -601,9 +579,7 @@ class SCFGP(object):
         exactly as predict does it; metrics holds predict's six numbers (MAE, NMAE, MSE, NMSE, MNLP, SCORE) of the held-out
         predictions against y, and 'LOO_LPD', the mean log predictive density of the scaled targets.  Neither self.evals nor
         self.alpha / self.Li are touched."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('loo needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('loo')
         if (X is None) != (y is None):
             raise ValueError('loo: X and y go together (both None: the training set)')
         if X is None:
@@ -635,9 +611,7 @@ class SCFGP(object):
         (noise excluded); gain[j] its information gain in nats.  weights (T,) >= 0 scale the criterion, 0 excludes a row.  Points that
         are pending (chosen but not yet observed) are handled by condition(X_pending, any y) on a copy of the model first: the
         choice depends on Li alone.  The library's message is raised on error.  Nothing of the model is touched."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('select needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('select')
         idx, var, gain = owner.select_raw(X_pool, self.X_scaler, self.Li, m, weights=weights)
         return idx, np.sqrt(var), gain
 
@@ -649,9 +623,7 @@ class SCFGP(object):
         (include/scfgp_hip.h: scfgp_select_iv).  red[j] is the reduction pick j achieved and ivar the summed variance before and
         after the m picks, in squared scaled-y units (noise excluded).  weights (T,) >= 0 scale the criterion, 0 excludes a row.
         Pending points: condition(X_pending, any y) on a copy of the model first.  Nothing of the model is touched."""
-        owner = getattr(self.pred_func, '__self__', None)
-        if not isinstance(owner, CompiledFuncs):
-            raise TypeError('select_iv needs the library\'s pred_func (build_hip_models / fit); got %r' % (self.pred_func,))
+        owner = self._owner('select_iv')
         idx, red, _, ivar = owner.select_iv_raw(X_pool, self.X_scaler, self.Li, m, Xr_raw=X_ref, weights=weights, ref_weights=ref_weights)
         return idx, red, ivar
 
@@ -676,7 +648,7 @@ class SCFGP(object):
                 running = remove_rows(running, X_done)                   # the unfinished ones stay pending
 
         Nothing of the model is touched."""
-        owner = self._acquire_owner('select_qei')
+        owner = self._owner('select_qei')
         idx, gain, _ = owner.select_qei_raw(X_pool, self.X_scaler, self.alpha, self.Li, m, int(nsamples), self._acquire_best(best, minimize),
                                             xi=xi, seed=seed, w=weights, pending=pending, minimize=minimize)
         return idx, gain
