@@ -79,7 +79,18 @@ const char* scfgp_last_error(const scfgp_ctx* ctx);
 /* ---- implicit state: the shared parameter vector -------------------------------------
  * The reference binds hyper-parameters with givens=[(params, self.params)]
  * (SCFGP/SCFGP.py:134-137,147-148): they are state of the compiled functions, not
- * arguments.  Layout [a,b,c,l_f(D*S),r_f(M*S),l_p(S),p(M)] (SCFGP/SCFGP.py:72,74-90). */
+ * arguments.  Layout [a,b,c,l_f(D*S),r_f(M*S),l_p(S),p(M)] (SCFGP/SCFGP.py:72,74-90).
+ *
+ * Range of the three scalars.  s = e^b sqrt(2/M), lam = e^{2a} + 1e-6, kappa = softplus(c) (formed as log1p(e^c), or c + log1p(e^-c)
+ * for c > 0), e^{-2a} and sigmoid(c) are formed in fp64 in every mode, each to a few ulp, over a in [-8, 3], b in [-6, 6] and
+ * c in [-36, 36]; over that range results are held to the mode's precision times what the point's conditioning costs any float64
+ * evaluation: alpha and Li carry cond(A) u, and cond(A) grows like e^{2b} / lam; the cost's term e^{-2a} (y^T y - g^T alpha) cancels
+ * at small a, in the reference's formula too (tests/test_gpu_hyper_range.py holds every output to the float64 oracle's own error
+ * against an mpmath evaluation at the same point).  Outside it: c beyond +-36 stays finite and monotone (kappa -> c above,
+ * kappa -> e^c > 0 below, down to c = -700); a and b are limited by the overflow of e^{2a}, e^{-2a} and e^b alone.
+ * A row of l_f whose entries are all equal (always, with S = 1) or such a row of F = l_f r_f^T has standard deviation 0: when every
+ * row of one of the two is so, the penalty's -log(sum of stds) is +infinity, as in the reference, and the evaluation returns that
+ * cost with SCFGP_ENONFINITE; a single such row among others leaves the cost finite and that row's penalty gradient 0/0 = NaN. */
 int scfgp_set_params(scfgp_ctx* ctx, const double* params, int P);
 int scfgp_get_params(scfgp_ctx* ctx, double* params, int P);
 

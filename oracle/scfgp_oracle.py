@@ -87,7 +87,7 @@ def forward(X, y, params, S, M, gauss_hermite=True):
     a, b, c, l_F, r_F, F, l_FC, FC = unpack_params(params, D, S, M)
     sig2_n = np.exp(2 * a)
     Phi = feature_map(X, params, D, S, M)
-    noise = np.log(1 + np.exp(c))                                   # :103
+    noise = np.log1p(np.exp(c))                                     # :103, log(1 + e^c) without its cancellation
     A = Phi.T @ Phi + (sig2_n + EPSILON) * np.eye(Phi.shape[1])      # :104-105
     L = np.linalg.cholesky(A)                                        # :106 (lower)
     Li = np.linalg.inv(L)                                            # :107 general inverse
@@ -119,7 +119,7 @@ def predict(Xs, alpha, Li, params, S, M):
     D = Xs.shape[1]
     c = params[2]
     Phis = feature_map(Xs, params, D, S, M)
-    noise = np.log(1 + np.exp(c))
+    noise = np.log1p(np.exp(c))
     mu = Phis @ np.asarray(alpha).reshape(-1, 1)
     std = (noise * (1 + ((Phis @ np.asarray(Li).T) ** 2).sum(1))) ** 0.5
     return mu, std

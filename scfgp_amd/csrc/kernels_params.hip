@@ -12,7 +12,8 @@ __global__ void scal_kernel(const double* __restrict__ params, int M, Scal* sc) 
     sc->s = exp(b) * sqrt(2.0 / M);
     sc->e2a = exp(2.0 * a);
     sc->lam = sc->e2a + 1e-6;
-    sc->kappa = log(1.0 + exp(c));
+    // softplus without the cancellation of log(1 + e^c): e^c below ulp(1) survives in log1p, and e^c cannot overflow for c > 0
+    sc->kappa = c > 0 ? c + log1p(exp(-c)) : log1p(exp(c));
     sc->em2a = exp(-2.0 * a);
     sc->sigc = 1.0 / (1.0 + exp(-c));
 }

@@ -256,7 +256,6 @@ struct scfgp_ctx {
     double* ut() { return d_vecs + 3 * g.Kp; }
     double* alpha_pred() { return d_vecs + 4 * g.Kp; }
     size_t tsize() const { return dtype == SCFGP_F32 ? 4 : 8; }
-    double h_scale() const { return std::exp(h_params[1]) * std::sqrt(2.0 / g.M); }      // s = e^b sqrt(2/M) from the host copy
     KStage kstage() {
         KStage k; k.K = g.K; k.Kp = g.Kp; k.A = d_x1; k.Li = d_Li; k.B = d_B; k.T1 = d_T1; k.T2 = d_T2;
         k.g = d_x1 + (int64_t)g.Kp * g.Kp; k.beta = beta(); k.alpha = alpha(); k.h = d_x2 + (int64_t)g.Kp * g.Kp;
