@@ -380,6 +380,42 @@ int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double
 int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                     double* alpha_out, double* Li_out);
 
+/* ---- absorbing derivative observations into a fitted posterior (no reference counterpart: the reference refits, on values only) -----
+ * The gradient of the model is linear in its weights, grad f(x) = J(x)^T w, so an observed partial derivative is a linear observation of w
+ * like an observed value, and it enters the posterior through scfgp_condition's update with another row.  Notation as there.  n points Xn
+ * (n x D); dims (nd entries in 0..D-1, distinct, in any order; NULL: all D inputs in order, and then nd must be D) names the inputs whose
+ * partial derivative was observed; Gn (n x nd): Gn[t][j] = d f / d x_dims[j] at point t, observed with noise of variance kappa / rho[t][j];
+ * rho (n x nd; NULL: all 1): the precision of every observation relative to the value noise, >= 0 and finite, 0 = "not observed"; yn (n;
+ * NULL: none): the values observed at the same points, with noise kappa -- one call then absorbs (f, grad f) as one run of a simulator
+ * with an adjoint returns them.  Every point contributes a block of nb = nd + (yn ? 1 : 0) consecutive rows to Phi_n:
+ *     the value row      phi_t                                                                       target  yn[t]
+ *     derivative row j   psi_tj = sqrt(rho[t][j]) g_t[d] (-phi_s o F_all[d, :] | phi_c o F_all[d, :])       target  sqrt(rho[t][j]) Gn[t][j]
+ * with d = dims[j], phi = (phi_c | phi_s) = s (cos z | sin z) the features of point t and F_all the x-part of the phase projection
+ * (d z / d x).  From these rows C, r, S = I + C^T C = M M^T, Li' = M^-1 Li and alpha' = alpha + Li^T gamma are exactly scfgp_condition's,
+ * so (alpha', Li') are the factors of A' = A + Phi_n^T Phi_n and everything that takes (alpha, Li) keeps working.  A value update followed
+ * by a derivative update equals the joint update, in either order.
+ * mode 0: scaled rows, Gn the derivative of the SCALED target in the SCALED input (g_t = 1); 1: column-selected raw rows through the
+ * registered X scaler, Gn the derivative of the scaled target in the RAW input: the row carries the scaler's derivative g_t[d] at the raw
+ * input, the factor scfgp_predict_grad and scfgp_predict_gradcov chain their outputs with.  There is no raw-y mode, as in scfgp_condition.
+ * Promises: Li_out is exactly zero above the diagonal; alpha_out (K) and Li_out (K x K) may alias alpha and Li and are written only on
+ * success; the training state of the context survives; SCFGP_F16X3 contexts agree with SCFGP_F32 ones bit for bit; an entry with rho = 0
+ * contributes exact zeros, and the outputs do not depend, bit for bit, on what Gn holds there as long as it is finite (rho of all ones
+ * has rho == NULL's bits); n >= 1 without limit: the points go through in chunks of floor(32768 / nb) whole points whose C^T C and C^T r
+ * are summed in fp64, so device memory does not grow with n.  The first pass (features, rows, C, C^T C, C^T r) and the K x K stage are fp64
+ * in every context, as in scfgp_forget and on its buffers: a derivative row is |F_all[d, :]| sqrt(rho / J) times as long as a value row, the
+ * rounding errors of fp32 products grow with the square of that, and a precise observation (rho = 100) at K = 2112 put the predictions 200
+ * fp32 bounds off; SCFGP_F32 and SCFGP_F16X3 contexts run the fp64 kernels of precision level 1 for it.  D is not limited: dims selects
+ * rows of F_all.
+ * SCFGP_EARG (with a scfgp_last_error text "condition_grad: ...", before any device work) for a NULL Xn, Gn, alpha, Li or output; n < 1;
+ * nd < 1, nd > D or nb > 32768; dims == NULL with nd != D; a dims entry out of range or repeated (the text names its position); a bad mode;
+ * a missing X scaler in mode 1 or parameters not set; a negative rho, reported by its first (row, column) even where it stands behind a
+ * non-finite one; every rho zero with no yn.  SCFGP_ENONFINITE for non-finite rows, observations, rho or factors; SCFGP_ENOTPD if the
+ * Cholesky of S fails: the outputs are untouched in all three cases.  Out of scope: the downdate (taking derivative observations back out;
+ * scfgp_forget removes values only), derivatives along arbitrary directions, a communicator / row-sharded form, and factors kept resident
+ * on the device between calls. */
+int scfgp_condition_grad(scfgp_ctx* ctx, const double* Xn, int64_t n, const int32_t* dims, int nd, const double* Gn, const double* rho,
+                         const double* yn, const double* alpha, const double* Li, int mode, double* alpha_out, double* Li_out);
+
 /* ---- removing observations from a fitted posterior (no reference counterpart: the reference refits on the remaining rows) ------------
  * The mirror image of scfgp_condition: n rows (Xo, yo) that ARE in the fit leave it through a K x K downdate that needs only alpha, Li,
  * the parameters and the rows being removed.  Notation as there; Phi_o the features of the removed rows at the SAME hyper-parameters:

@@ -52,6 +52,8 @@ SIGNATURES = {
                                    C.c_int, C.c_int, C.c_int, C.c_int, _c_double_p, _c_double_p, _c_i64_p, _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_predict_cov': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, _c_double_p, C.c_int64, _c_double_p, C.c_int, C.c_int, _c_double_p]),
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
+    'scfgp_condition_grad': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, C.POINTER(C.c_int32), C.c_int, _c_double_p, _c_double_p, _c_double_p,
+                                       _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_forget': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p,
                                _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_loo': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p,

@@ -1,5 +1,5 @@
 // Host-side helpers of the posterior and pool entry points (scfgp_api.hip): plain C++17, no HIP, so that a stand-alone program can
-// check them (tests/host/api_host_check.cpp).
+// check them (tests/host/api_host_check.cpp; scfgp_condition_grad's part: tests/host/condgrad_host_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -38,4 +38,40 @@ struct RowJobs {
     int64_t rows(int64_t job) const { return lead(job) ? n0 : std::min(CH, n - row0(job)); }
     const double* x(int64_t job, int D) const { return lead(job) ? X0 : X + row0(job) * D; }
     const double* targets(int64_t job) const { return lead(job) || !y ? nullptr : y + row0(job); }
+    // The target block of a job: up to three arrays behind the rows, segment 0 = y (1 double per row), segments 1 and 2 = y1, y2 (w1, w2
+    // doubles per row; NULL: absent).  In the feed's half the segments that are present follow one another, each CH rows long, so a
+    // segment's place does not depend on the job: seg_off(k) doubles behind the start of the block, target_width() * CH in all.
+    const double* y1 = nullptr; int64_t w1 = 0;
+    const double* y2 = nullptr; int64_t w2 = 0;
+    static constexpr int SEGS = 3;
+    const double* seg_base(int k) const { return k == 0 ? y : k == 1 ? y1 : y2; }
+    int64_t seg_width(int k) const { return !seg_base(k) ? 0 : k == 0 ? 1 : k == 1 ? w1 : w2; }
+    int64_t seg_off(int k) const { int64_t o = 0; for (int i = 0; i < k; ++i) o += seg_width(i) * CH; return o; }
+    int64_t target_width() const { return seg_width(0) + seg_width(1) + seg_width(2); }
+    const double* seg(int64_t job, int k) const { return lead(job) || !seg_base(k) ? nullptr : seg_base(k) + row0(job) * seg_width(k); }
 };
+
+// scfgp_condition_grad: a point brings a block of nb = nd + (values ? 1 : 0) observation rows, and a chunk holds whole points.
+struct GradBlocks {
+    int nd; bool values, weights;                                 // derivative columns; yn given; rho given
+    int64_t nb() const { return nd + (values ? 1 : 0); }
+    int64_t points(int64_t chunk_rows) const { return chunk_rows / nb(); }       // per chunk of chunk_rows observation rows (0: none fit)
+    int64_t target_width() const { return (values ? 1 : 0) + (int64_t)nd * (weights ? 2 : 1); }
+    // the schedule: n points in chunks of points(chunk_rows), targets [yn | Gn | rho] behind them
+    RowJobs jobs(const double* X, const double* yn, const double* Gn, const double* rho, int64_t n, int64_t chunk_rows) const {
+        RowJobs j = {X, values ? yn : nullptr, n, points(chunk_rows)};
+        j.y1 = Gn; j.w1 = nd;
+        j.y2 = weights ? rho : nullptr; j.w2 = weights ? nd : 0;
+        return j;
+    }
+};
+
+// dims (nd entries): the position of the first entry that is out of 0..D-1 or repeats an earlier one, -1: none.  seen: D bytes of scratch
+inline int first_bad_dim(const int32_t* dims, int nd, int D, char* seen) {
+    std::fill(seen, seen + D, 0);
+    for (int j = 0; j < nd; ++j) {
+        if (dims[j] < 0 || dims[j] >= D || seen[dims[j]]) return j;
+        seen[dims[j]] = 1;
+    }
+    return -1;
+}

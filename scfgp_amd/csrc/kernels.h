@@ -404,6 +404,17 @@ void gradcov_blocks(const Geom& gr, const Geom& g, const T* C, const double* par
 // acc (D x D, lower triangle) += rec[0..n) in point order, one lane per entry
 void gradcov_reduce(const double* rec, int64_t n, int D, double* acc, hipStream_t st);
 
+// ---- condgrad.hip: derivative observations as rows of the posterior update (scfgp_condition_grad) ------------------------------------
+// what a chunk of g.N points observes: dims (nd device ints, NULL: 0..nd-1), gfac (g.N x D: the X scaler's derivative factors, NULL: 1), y
+// (g.N values, NULL: none), G (g.N x nd derivatives), rho (g.N x nd precisions relative to the value noise, NULL: 1)
+struct GradObs { const int* dims; int nd; const double *gfac, *y, *G, *rho; };
+// Psi (gr.Np x Kp) and tg (gr.Np): a point's nb = nd + (y ? 1 : 0) observation rows and their targets at rows t nb + i -- the value row
+// phi_t with target y_t, then sqrt(rho) gfac[d] (-Phi_s[t] o Fall[d] | Phi_c[t] o Fall[d]) with target sqrt(rho) G for d = dims[j], formed in
+// fp64 and rounded once; an entry with rho = 0 gives exact zeros; the padding columns and the rows from g.N nb on are zero.  gr: the
+// chunk's geometry in observation rows
+template <typename T>
+void gradobs_rows(const Geom& gr, const Geom& g, const T* Phi, const double* Fall, const GradObs& a, T* Psi, double* tg, hipStream_t st);
+
 // ---- pd.hip: partial dependence and ICE curves over a pool (scfgp_predict_pd) ----------------------------------------------------------
 // rows that a dimension's G grid points take in the stacked operand Phibar: a multiple of 128, so that predcov finds its padded rows
 inline int pd_grid_rows(int G) { return (int)round_up(G, 128); }

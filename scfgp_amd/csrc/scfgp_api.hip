@@ -784,8 +784,9 @@ template <typename T> struct Impl {
     // chunk's geometry with the update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows
     // (never the fp16 split: an f16x3 context runs fp32 mode's kernels here).  The typed operands come with the call (UpdateOperands):
     // scfgp_forget runs the fp64 arm on buffers of its own in an fp32 context.
-    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const UpdateOperands& o, double* out) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.Phi, c->st);
+    // have_rows: o.Phi and u_y already hold the chunk's rows and targets (scfgp_condition_grad: gradobs_chunk)
+    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const UpdateOperands& o, double* out, bool have_rows = false) {
+        if (!have_rows) SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.Phi, c->st);
         SK::apply_c(g, (const T*)o.Phi, (const T*)o.LiT, (const T*)o.Li, (T*)o.C, c->p_vpart, c->u_vec, c->u_vec, c->p_mupart, c->st, 0);
         SK::rowresidual(g, c->p_mupart, c->u_y, c->u_r, c->st);
         const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
@@ -793,6 +794,15 @@ template <typename T> struct Impl {
         SK::gram(g, (const T*)o.C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
         reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
         reduce_side(sidepart, rs.nsplit, g.Kp, g.gfull * g.tile + g.gstrip * 64, out + c->n_pk, c->st);
+        HIPCHK(c, hipGetLastError());
+        return SCFGP_OK;
+    }
+    // scfgp_condition_grad (condgrad.hip): Phi of the chunk's g.N packed points into o.C (which the product that follows overwrites), then
+    // their gr.N observation rows into o.Phi and the rows' targets into u_y, where update_chunk (have_rows) finds them
+    static int gradobs_chunk(scfgp_ctx* c, const Geom& g, const Geom& gr, const UpdateOperands& o, const GradObs& a) {
+        { ProfScope ps(c, "gradobs_featuremap");
+          SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.C, c->st); }
+        { ProfScope ps(c, "gradobs_rows"); gradobs_rows<T>(gr, g, (const T*)o.C, c->d_Fall, a, (T*)o.Phi, c->u_y, c->st); }
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
@@ -1317,7 +1327,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 
 // ----------------------------------------------------------------------------------------------
 // the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_predict_pd, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
+// scfgp_condition, scfgp_condition_grad, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_predict_pd, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
 // ----------------------------------------------------------------------------------------------
 // Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
 // the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
@@ -1338,7 +1348,7 @@ static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
 // Not through these helpers, and why:
 //   scfgp_loo with resident rows      the rows are read where they lie on the device: its loop skips the uploads and the feed
 //   scfgp_select_iv                   two schedules in a row (the reference chunks, then the pool): a one-line lambda picks a job's
-//   scfgp_condition, scfgp_forget     load_factor's long form (update_gather): other buffers, and the finite check of what was loaded
+//   scfgp_condition, _condition_grad, scfgp_forget    load_factor's long form (update_gather): other buffers, and the finite check
 //   scfgp_predict_grad, _raw, _y      scaler checks under their own names and texts, apart from predict_impl's parameter check
 //   scfgp_select, _select_iv, _qei    bare int flags, fetched twice under two different synchronisations: a helper would not be shorter
 // scfgp_forget's second phase and scfgp_predict_pd's second pass use RowJobs through `base`: their feed goes on counting.
@@ -1369,8 +1379,21 @@ struct RowFeed {
         HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
         return SCFGP_OK;
     }
-    // a job of a schedule, as the feed's job base + job
-    int upload(int64_t job, const RowJobs& j, int64_t base = 0) { return upload(base + job, j.x(job, c->g.D), j.targets(job), j.rows(job)); }
+    // a job of a schedule, as the feed's job base + job.  A schedule with further target arrays (RowJobs::y1, y2: scfgp_condition_grad)
+    // stages every segment at its place in the block behind the rows; its stride is PRED_ROWS * D + CH * target_width() doubles
+    int upload(int64_t job, const RowJobs& j, int64_t base = 0) {
+        if (!j.y1 && !j.y2) return upload(base + job, j.x(job, c->g.D), j.targets(job), j.rows(job));
+        const int h = (int)((base + job) & 1);
+        const int64_t rows = j.rows(job);
+        if (base + job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[2 + h], 0));
+        HIPCHK(c, hipMemcpyAsync(raw + h * stride, j.x(job, c->g.D), sizeof(double) * rows * c->g.D, hipMemcpyHostToDevice, c->copy_st));
+        for (int k = 0; k < RowJobs::SEGS; ++k)
+            if (const double* src = j.seg(job, k))
+                HIPCHK(c, hipMemcpyAsync(raw + h * stride + PRED_ROWS * c->g.D + j.seg_off(k), src, sizeof(double) * rows * j.seg_width(k),
+                                         hipMemcpyHostToDevice, c->copy_st));
+        HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
+        return SCFGP_OK;
+    }
     int acquire(int64_t job, const double** x, const double** y = nullptr) {
         const int h = (int)(job & 1);
         HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[h], 0));
@@ -2158,42 +2181,48 @@ static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
 // C^T C and C^T r to a running fp64 sum in u_acc and, rr != NULL, its r^T r to rr[0].  u_flag[0..3] are cleared first; u_flag[1] tells
 // of non-finite rows, targets or factors.  `feed` is opened here and stays open for the caller.  wide != NULL (fp32 contexts only): the
 // pass runs the fp64 kernels on these operands.
-static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const double* y, int64_t n, const double* alpha, const double* Li,
-                         int mode, double* rr, const UpdateOperands* wide = nullptr) {
+//
+// How a chunk's rows and targets are produced is the caller's: produce(i, g, x, targets, ops, &have_rows) packs job i (g: its geometry
+// in points; x, targets: its place in the feed), releases the feed's half when the raw rows have been read, and either leaves the
+// feature map to update_chunk (the packed rows ARE the update's rows, targets in u_y) or writes the rows of the update itself into
+// ops.Phi and u_y (have_rows; rpp of them per point: scfgp_condition_grad).
+template <typename Produce>
+static int update_gather(scfgp_ctx* c, RowFeed& feed, const RowJobs& jobs, int64_t rpp, const double* alpha, const double* Li, double* rr,
+                         const UpdateOperands* wide, Produce produce) {
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp;
-    const int64_t nchunks = (n + PRED_ROWS - 1) / PRED_ROWS;
+    const int64_t nchunks = jobs.count(), n = jobs.n * rpp, CHR = jobs.CH * rpp;      // the update's rows: in all, per full chunk
     int rc;
     if ((rc = ensure_pred_chunk(c))) return rc;
     if ((rc = ensure_pred_factor(c))) return rc;
     {   // slabs of the widest split among the call's chunk shapes (full chunks and the ragged last one)
         const int nts = Kp / g0.tile, ntiles = nts * (nts + 1) / 2;
         size_t need = 0;
-        for (int64_t np : {round_up(std::min<int64_t>(n, PRED_ROWS), 256), round_up(n - (nchunks - 1) * PRED_ROWS, 256)})
+        for (int64_t np : {round_up(std::min<int64_t>(n, CHR), 256), round_up(n - (nchunks - 1) * CHR, 256)})
             need = std::max(need, sizeof(double) * (size_t)update_splits(c, np, wide).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
         if ((rc = ensure_update(c, need))) return rc;
     }
     const UpdateOperands own = {c->p_Phi, c->p_C, c->u_LiT, c->p_Li};
     const UpdateOperands& ops = wide ? *wide : own;
     // Li in host layout (in, then out) / two chunks of [X | y]
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
+    if ((rc = feed.open(c, PRED_ROWS * g0.D + jobs.CH * std::max<int64_t>(1, jobs.target_width()), (int64_t)g0.K * g0.K))) return rc;
     HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
     if (rr) HIPCHK(c, hipMemsetAsync(rr, 0, sizeof(double), c->st));
     if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->u_Li, wide ? nullptr : ops.LiT, wide ? nullptr : ops.Li, alpha, c->u_vec,
                           c->u_flag))) return rc;
     if (wide) Impl<double>::type_factor(c, c->u_Li, ops.LiT, ops.Li);
     HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    const RowJobs jobs = {X, y, n, PRED_ROWS};
     if ((rc = feed.upload(0, jobs))) return rc;
     for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
+        const Geom gp = chunk_geom(g0, jobs.rows(i));
         const double *x, *yi;
         if ((rc = feed.acquire(i, &x, &yi))) return rc;
-        pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
+        bool have_rows = false;
+        if ((rc = produce(i, gp, x, yi, ops, &have_rows))) return rc;
+        const Geom g = have_rows ? chunk_geom(g0, jobs.rows(i) * rpp) : gp;
         double* out = i == 0 ? c->u_acc : c->u_part;
-        if ((rc = wide ? Impl<double>::update_chunk(c, g, update_splits(c, g.Np, true), ops, out)
-                       : DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), ops, out))) return rc;
+        if ((rc = wide ? Impl<double>::update_chunk(c, g, update_splits(c, g.Np, true), ops, out, have_rows)
+                       : DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), ops, out, have_rows))) return rc;
         if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
         if (rr) update_sumsq(c->u_r, g.N, rr, c->st);
         if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
@@ -2201,6 +2230,16 @@ static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const dou
     // non-finite rows or targets have reached C^T C or C^T r by now
     update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
     return SCFGP_OK;
+}
+// scfgp_condition, scfgp_forget: the n rows (X, y) in chunks of PRED_ROWS are the update's rows
+static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const double* y, int64_t n, const double* alpha, const double* Li,
+                         int mode, double* rr, const UpdateOperands* wide = nullptr) {
+    const RowJobs jobs = {X, y, n, PRED_ROWS};
+    return update_gather(c, feed, jobs, 1, alpha, Li, rr, wide,
+                         [&](int64_t i, const Geom& g, const double* x, const double* yi, const UpdateOperands&, bool*) {
+                             pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
+                             return feed.release(i);
+                         });
 }
 static KUpdate update_buffers(scfgp_ctx* c) {
     const int64_t Kp = c->g.Kp;
@@ -2211,19 +2250,11 @@ static KUpdate update_buffers(scfgp_ctx* c) {
 }
 
 // One K x K stage turns the first pass's sum into the new factors, which leave through the feed's buffer.  The outputs are fetched only
-// when the stage succeeded.
-extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
-                               double* alpha_out, double* Li_out) {
-    if (!c) return SCFGP_EARG;
-    if (!Xn || !yn || !alpha || !Li || !alpha_out || !Li_out || mode < 0 || mode > 1) { c->err = "condition: bad arguments"; return SCFGP_EARG; }
-    if (n < 1) { c->err = "condition: n must be at least 1"; return SCFGP_EARG; }
-    int rc;
-    if ((rc = need_model({c, "condition"}, mode == 1))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+// when the stage succeeded.  who, what: the entry point and its name for the targets in the error texts
+static int update_finish(scfgp_ctx* c, RowFeed& feed, const char* who, const char* what, double* alpha_out, double* Li_out) {
     const Geom& g0 = c->g;
     const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    RowFeed feed;
-    if ((rc = update_gather(c, feed, Xn, yn, n, alpha, Li, mode, nullptr))) return rc;
+    const Fail fail = {c, who};
     const KUpdate k = update_buffers(c);
     kstage_update(k, c->st);
     update_check_finite(c->u_S, K2, c->u_flag, c->st);
@@ -2233,12 +2264,92 @@ extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn,
     int flags[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flags[1]) { c->err = "condition: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
-    if (flags[0]) { c->err = "condition: I + C^T C is not positive definite"; return SCFGP_ENOTPD; }
+    if (flags[1]) return fail.nonfinite(std::string("non-finite rows, ") + what + " or factors");
+    if (flags[0]) return fail.set("I + C^T C is not positive definite", SCFGP_ENOTPD);
     HIPCHK(c, hipMemcpyAsync(Li_out, feed.raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     return SCFGP_OK;
+}
+extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
+                               double* alpha_out, double* Li_out) {
+    if (!c) return SCFGP_EARG;
+    if (!Xn || !yn || !alpha || !Li || !alpha_out || !Li_out || mode < 0 || mode > 1) { c->err = "condition: bad arguments"; return SCFGP_EARG; }
+    if (n < 1) { c->err = "condition: n must be at least 1"; return SCFGP_EARG; }
+    int rc;
+    if ((rc = need_model({c, "condition"}, mode == 1))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    RowFeed feed;
+    if ((rc = update_gather(c, feed, Xn, yn, n, alpha, Li, mode, nullptr))) return rc;
+    return update_finish(c, feed, "condition", "targets", alpha_out, Li_out);
+}
+
+// ----------------------------------------------------------------------------------------------
+// absorbing derivative observations into a fitted posterior (condgrad.hip; derivation and promises in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+// scfgp_condition's path with another producer of a chunk's rows: a chunk holds whole points, np = PRED_ROWS / nb of them (GradBlocks,
+// api_host.h), whose features are expanded into nb observation rows each (Impl::gradobs_chunk).  A job uploads [X | yn | Gn | rho] of its
+// points; the raw rows stay in the feed's half until the scaler's factors g_t have been formed from them (mode 1) and the targets
+// until the row kernel has read them.  In fp32 contexts the first pass is the fp64 one on scfgp_forget's buffers, as there: a derivative
+// row is |F_all[d, :]| sqrt(rho / J) times as long as a value row, the rounding errors of the fp32 products grow with its square, and
+// the predictions feel them (DESIGN 4.20 has the measured ratios).
+static int ensure_forget(scfgp_ctx* c);
+extern "C" int scfgp_condition_grad(scfgp_ctx* c, const double* Xn, int64_t n, const int32_t* dims, int nd, const double* Gn, const double* rho,
+                                    const double* yn, const double* alpha, const double* Li, int mode, double* alpha_out, double* Li_out) {
+    if (!c) return SCFGP_EARG;
+    const Fail fail = {c, "condition_grad"};
+    if (!Xn || !Gn || !alpha || !Li || !alpha_out || !Li_out) return fail.arg("bad arguments");
+    if (n < 1) return fail.arg("n must be at least 1");
+    const Geom& g0 = c->g;
+    const int D = g0.D;
+    if (nd < 1 || nd > D) return fail.arg("nd must lie in 1..D");
+    const GradBlocks gb = {nd, yn != nullptr, rho != nullptr};
+    if (gb.nb() > PRED_ROWS) return fail.arg("the rows of a point (nd, and one for its value) must not exceed 32768");
+    if (!dims && nd != D) return fail.arg("dims == NULL needs nd == D");
+    if (dims) {
+        std::vector<char> seen(D);
+        const int j = first_bad_dim(dims, nd, D, seen.data());
+        if (j >= 0) return fail.arg("dims[" + std::to_string(j) + "] is out of range or repeated");
+    }
+    if (mode < 0 || mode > 1) return fail.arg("bad mode");
+    int rc;
+    if ((rc = need_model(fail, mode == 1))) return rc;
+    if (rho) {
+        const WeightScan ws = scan_weights(rho, n * nd);
+        auto at = [&](int64_t e) { return "rho[" + std::to_string(e / nd) + ", " + std::to_string(e % nd) + "]"; };
+        if (ws.first_negative >= 0) return fail.arg(at(ws.first_negative) + " is negative");
+        if (ws.first_nonfinite >= 0) return fail.nonfinite(at(ws.first_nonfinite) + " is not finite");
+        if (!yn && ws.positive == 0) return fail.arg("every rho is zero and no values are given");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/condition_grad_time.py)
+    const int xmode = mode == 1 ? c->xs_mode : 0;
+    const RowJobs jobs = gb.jobs(Xn, yn, Gn, rho, n, PRED_ROWS);
+    DevTmp d_dims, gfac;                                          // dims | g_t of a chunk's points
+    if (dims) {
+        if ((rc = dmalloc(c, &d_dims.p, sizeof(int) * nd))) return rc;
+        HIPCHK(c, hipMemcpyAsync(d_dims.p, dims, sizeof(int) * nd, hipMemcpyHostToDevice, c->st));
+    }
+    if (xmode && (rc = dmalloc(c, &gfac.p, sizeof(double) * std::min(n, jobs.CH) * D))) return rc;
+    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
+    if (c->dtype == SCFGP_F32 && (rc = ensure_forget(c))) return rc;
+    const UpdateOperands wide = {c->f_w, c->f_w + PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp + K2};
+    RowFeed feed;
+    auto produce = [&](int64_t i, const Geom& g, const double* x, const double* tg, const UpdateOperands& ops, bool* have_rows) -> int {
+        pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
+        if (xmode) {
+            gradcov_ones(gfac.p, g.N * D, c->st);
+            xgrad_chunk(x, g.N, D, xmode, c->d_xscale, gfac.p, nullptr, c->st);
+        }
+        const GradObs obs = {(const int*)d_dims.p, nd, xmode ? gfac.p : nullptr, yn ? tg + jobs.seg_off(0) : nullptr, tg + jobs.seg_off(1),
+                             rho ? tg + jobs.seg_off(2) : nullptr};
+        const Geom gr = chunk_geom(g0, g.N * gb.nb());
+        if (int r = Impl<double>::gradobs_chunk(c, g, gr, ops, obs)) return r;      // fp64 operands in every context
+        *have_rows = true;
+        return feed.release(i);
+    };
+    if ((rc = update_gather(c, feed, jobs, gb.nb(), alpha, Li, nullptr, c->dtype == SCFGP_F32 ? &wide : nullptr, produce))) return rc;
+    return update_finish(c, feed, "condition_grad", "observations", alpha_out, Li_out);
 }
 
 // ----------------------------------------------------------------------------------------------

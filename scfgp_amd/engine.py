@@ -756,6 +756,53 @@ class HipEngine(object):
         self._check_undelivered(rc, 'condition')
         return alpha_out, Li_out
 
+    def condition_grad(self, X, G, alpha, Li, dims=None, rho=None, y=None, raw=False):
+        """Absorb observed partial derivatives into the fitted posterior (alpha, Li) (include/scfgp_hip.h: scfgp_condition_grad) and
+        return (alpha' (K,1), Li' (K,K)).  G (n, nd): G[t, j] = d f / d x_dims[j] at row t of X, in SCALED target units; dims: the
+        observed inputs (distinct, any order; None: all of them, in order); rho (n, nd) >= 0: every observation's precision relative to
+        the value noise (None: 1; 0: not observed); y (n,) or (n,1): the SCALED values observed at the same points (None: none).
+        raw=False: X as predict takes it, derivatives in the scaled inputs.  raw=True: unscaled X through the registered X scaler,
+        derivatives in the RAW inputs, dims naming raw columns and -- dims=None -- G, rho with one column per raw column; what refers
+        to a constant column that the scaler dropped is ignored, since the model does not depend on it."""
+        cols = self._raw_cols('condition_grad', raw)
+        if X is None or G is None or alpha is None or Li is None:
+            raise ValueError('condition_grad: X, G, alpha and Li are all needed')
+        D_in = np.shape(X)[1] if np.ndim(X) == 2 else self.D
+        X = self._rows(X, 'X', cols)
+        n = X.shape[0]
+        G = np.asarray(G, dtype=np.float64)
+        rho = None if rho is None else np.asarray(rho, dtype=np.float64)
+        if dims is None:
+            dims = np.arange(D_in)
+        dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+        if G.ndim != 2 or G.shape != (n, dims.size) or (rho is not None and rho.shape != G.shape):
+            raise ValueError('condition_grad: G (and rho) must be (%d, %d): one column per observed input' % (n, dims.size))
+        if cols is not None:
+            if dims.size and (dims.min() < 0 or dims.max() >= D_in):
+                raise ValueError('condition_grad: dims names a column that does not exist')
+            where = {int(cc): i for i, cc in enumerate(cols)}
+            keep = [j for j, d in enumerate(dims) if int(d) in where]
+            dims = np.array([where[int(dims[j])] for j in keep], dtype=np.int64)
+            G = G[:, keep]
+            rho = None if rho is None else rho[:, keep]
+        if dims.size == 0:
+            raise ValueError('condition_grad: no observed input is left')
+        G = np.ascontiguousarray(G)
+        rho = None if rho is None else np.ascontiguousarray(rho)
+        y = self._weights(y, n, 'y')
+        alpha, Li = self._factors(alpha, Li)
+        nd = int(dims.size)
+        dims32 = None if nd == self.D and np.array_equal(dims, np.arange(nd)) else np.ascontiguousarray(dims, dtype=np.int32)
+        alpha_out = np.empty((self.K, 1)); Li_out = np.empty((self.K, self.K))
+        rc = self.lib.scfgp_condition_grad(self.ctx, dptr(X), n, None if dims32 is None else dims32.ctypes.data_as(C.POINTER(C.c_int32)), nd,
+                                           dptr(G), dptr(rho), dptr(y), dptr(alpha), dptr(Li), 1 if raw else 0, dptr(alpha_out), dptr(Li_out))
+        self._check_undelivered(rc, 'condition_grad')
+        return alpha_out, Li_out
+
+    def condition_grad_points_per_chunk(self, nd, values):
+        """Points per chunk of condition_grad (the formula of include/scfgp_hip.h): whole blocks of nb = nd + (1 with values) rows"""
+        return 32768 // (int(nd) + (1 if values else 0))
+
     FORGET_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'log_joint', 'min_pivot2', 'blocks')
 
     def forget(self, X, y, alpha, Li, factors=True, predict=False, mode='scaled'):

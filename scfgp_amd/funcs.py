@@ -355,6 +355,14 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.condition(X_raw, y_scaled, alpha, Li, mode='raw')
 
+    def condition_grad_raw(self, X_raw, G, x_scaler, alpha, Li, dims=None, rho=None, y_scaled=None):
+        """The factors (alpha', Li') of the posterior (alpha, Li) after the derivative observations G (scaled target per RAW input; dims,
+        rho as engine.condition_grad takes them with raw=True) and, given y_scaled, the values at the same rows are absorbed into it, at
+        the shared parameter vector: raw rows through the X scaler on the device."""
+        self._sync_params()
+        self._sync_scalers(x_scaler, None)
+        return self.engine.condition_grad(X_raw, G, alpha, Li, dims=dims, rho=rho, y=y_scaled, raw=True)
+
     def forget_raw(self, X_raw, y_scaled, x_scaler, alpha, Li, factors=True, predict=False):
         """engine.forget of the rows (X_raw, y_scaled), which must be rows of the fit (alpha, Li), at the shared parameter vector: raw
         rows through the X scaler on the device, targets already scaled."""

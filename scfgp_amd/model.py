@@ -501,6 +501,30 @@ class SCFGP(object):
         self.alpha, self.Li = owner.condition_raw(X, ys, self.X_scaler, self.alpha, self.Li)
         return self
 
+    def condition_grad(self, X, dY, y=None, rho=None, dims=None):
+        """Absorb observed partial derivatives into the fitted posterior, as condition absorbs values (include/scfgp_hip.h:
+        scfgp_condition_grad).  X: raw inputs (n,D); dY: the derivatives of the RAW target in the raw inputs, (n,D) or -- with dims, the
+        raw columns that were observed -- (n, len(dims)); rho: every observation's precision relative to the value noise, shaped like
+        dY (None: 1; 0: not observed); y: the raw targets (n,1) observed at the same points, absorbed as values in the same call (None:
+        derivatives only).  A derivative in a constant column that the X scaler dropped is ignored: the model does not depend on it.
+        The chain rule through the y scaler needs its forward derivative at the observed y, so a scaler that is not affine ('min-max'
+        and 'normal' are) needs y.  Scalers, self.X / self.y and the restored-checkpoint case are as in condition.  Returns self."""
+        owner = self._owner('condition_grad')
+        dY = np.asarray(dY, dtype=np.float64)
+        if dY.ndim != 2:
+            raise ValueError('condition_grad: dY must be (n, D) or (n, len(dims))')
+        if y is None:
+            if not self.y_scaler.affine:
+                raise ValueError("condition_grad: the y scaler %r is not affine, so its derivative depends on the observed y: pass y"
+                                 % self.y_scaler.algo)
+            ys, dfy = None, self.y_scaler.forward_derivative(np.zeros((1, len(self.y_scaler.data['cols']))))
+        else:
+            y = np.asarray(y, dtype=np.float64).reshape(-1, 1)
+            ys = np.asarray(self.y_scaler.forward_transform(y), dtype=np.float64)
+            dfy = self.y_scaler.forward_derivative(y)
+        self.alpha, self.Li = owner.condition_grad_raw(X, dY * dfy, self.X_scaler, self.alpha, self.Li, dims=dims, rho=rho, y_scaled=ys)
+        return self
+
     def forget(self, X, y):
         """Remove the observations (X, y), raw inputs (n,D) and raw targets (n,1) that ARE rows of the fit, from the fitted posterior:
         self.alpha and self.Li become those of the fit on the remaining rows, at the current hyper-parameters, through a K x K

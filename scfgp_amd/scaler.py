@@ -94,6 +94,28 @@ class Scaler(object):
             return (tX - d["mu"]) / d["std"]
         return _norm_cdf((tX - d["mu"]) / d["std"])
 
+    def forward_derivative(self, X):
+        """d forward_transform / d x, element-wise at the kept columns of the raw rows X (n x len(cols))"""
+        d = self.data
+        tX = np.asarray(X, dtype=np.float64)[:, d["cols"]]
+        if self.algo == "min-max":
+            return np.broadcast_to(1. / (d["max"] - d["min"]), tX.shape).copy()
+        if self.algo == "normal":
+            return np.broadcast_to(1. / d["std"], tX.shape).copy()
+        if self.algo == "inv-normal":
+            return norm.pdf((tX - d["mu"]) / d["std"]) / d["std"]
+        t = (tX - d["min"]) / (d["max"] - d["min"])
+        lm = d["boxcox"][None, :]
+        dz = np.abs(t) ** (lm - 1) / ((d["max"] - d["min"]) * d["std"])
+        if self.algo == "auto-normal":
+            return dz
+        return norm.pdf((_boxcox(t, lm) - d["mu"]) / d["std"]) * dz
+
+    @property
+    def affine(self):
+        """whether forward_transform is affine in every column, so that its derivative does not depend on where it is taken"""
+        return self.algo in ("min-max", "normal")
+
     def backward_transform(self, X):
         d = self.data
         assert len(d["cols"]) == X.shape[1], "Backward Transform Error"
