@@ -572,6 +572,43 @@ int scfgp_predict_pd(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* 
                      const int* dims, int ndim, const double* grid, int G, int mode,
                      double* pd, double* pd_sd, double* pd_cov, double* ice);
 
+/* ---- closed-form Sobol indices under a product measure (no reference counterpart) ----------------------------------------------------
+ * The variance-based answer to "which inputs matter": the variance V of a sample function under a stated input distribution, the
+ * main-effect variances Vmain[d] = Var(E[f | x_d]) and the total-effect variances Vtot[d] = E[Var(f | x_-d)]; S_d = Vmain[d] / V and
+ * T_d = Vtot[d] / V are the first-order and total Sobol indices.  A phase is linear in x, so with phi(x) = s [cos z | sin z], z_j = sum_e
+ * x_e Om[e][j] + b_j (Om: rows 0..D-1 of F_all, b: its row D; J = S + M) and a_j = s (w_j - i w_{J+j}) a sample function is f(x) = Re sum_j
+ * a_j e^{i z_j(x)}, and under a product measure mu = prod_d mu_d over the SCALED inputs with characteristic functions psi_d(om) = E e^{i om x}
+ *     kind 0, uniform on [p0, p1]:   psi(om) = e^{i om (p0 + p1) / 2} sinc(om (p1 - p0) / 2)     (p0 == p1: a point mass)
+ *     kind 1, normal(p0, p1^2):       psi(om) = e^{i om p0 - (om p1)^2 / 2}                         (exactly 0 from |om| p1 of about 39 on)
+ * every moment factorises over the inputs: no pool, no row sweep, no Monte-Carlo error.  With psi1[d][j] = psi_d(Om[d][j]), E_j = e^{i b_j}
+ * prod_d psi1[d][j], E_j^{-d} the same product without factor d and, for a pair (j, k) and a sign (conjugation (+-) follows the sign),
+ *     P+-_all       = e^{i(b_j +- b_k)} prod_e psi_e(Om[e][j] +- Om[e][k])
+ *     P+-_main(d)   = E_j^{-d} (E_k^{-d})^(+-) psi_d(Om[d][j] +- Om[d][k])
+ *     P+-_closed(d) = e^{i(b_j +- b_k)} psi1[d][j] (psi1[d][k])^(+-) prod_{e != d} psi_e(Om[e][j] +- Om[e][k])
+ * the centred coefficients are C+-_u = P+-_u - E_j E_k^(+-), the centred form is Q_u(w) = 1/2 Re sum_{j,k} [a_j a_k C+_u + a_j conj(a_k)
+ * C-_u], and f0 = Re sum_j a_j E_j, V = Q_all, Vmain[d] = Q_main(d), Vtot[d] = V - Q_closed(d), phibar = s (Re E | Im E) = E_mu phi(x) in
+ * alpha's layout (f0 = phibar^T w; Bayesian quadrature: int f dmu ~ N(phibar^T alpha, kappa |Li phibar|^2)).  The difference is taken per
+ * coefficient, never as w^T M w - f0^2, so f0^2 >> V does not cancel; a leave-one-out product is a prefix times a suffix, never a
+ * quotient, so a factor that is exactly 0 is harmless.
+ * kind (D entries, NULL: all uniform), p0, p1 (D each); W (K x nw, row-major: what scfgp_sample_weights returns, or any K-vectors; nw = 1
+ * with W = alpha gives the posterior mean), 1 <= nw <= 1024; f0, V (nw each), Vmain, Vtot (nw x D, row-major), phibar (K).  Any output
+ * may be NULL, at least one must be given; a NULL Vtot skips the closed-set work, a NULL Vmain the main-effect work, f0 and phibar alone
+ * run no pair work at all; W may be NULL (and nw is then ignored) when only phibar is asked for.  The variances are returned, not the
+ * ratios: V may be 0.  Everything is fp64 in every context (the K x K stage convention, as in scfgp_forget) and uses the context's current
+ * parameters only: no alpha, no Li, no rows, no scaler; the training state of the context survives.  D is not limited: the pair kernel
+ * takes the inputs in groups of 16 (option test_sobol_group can only lower that) and re-evaluates psi outside the group.
+ * Promises, bit for bit: (1) the same outputs on every run; (2) column w of every output depends on W[:, w] and the parameters only, not
+ * on nw or on the other columns: a call with fewer columns returns a prefix; (3) every output is the same whichever other outputs are
+ * asked for; (4) contexts of all three compute modes agree (F_all and the scalars are formed by the same fp64 kernels in each); (5) the
+ * group size does not change any output.
+ * SCFGP_EARG (with a scfgp_last_error text "sobol: ...", before any device work, in this order) for a NULL p0 or p1; no output asked for;
+ * W == NULL while f0, V, Vmain or Vtot is wanted; nw out of range (when W is used); a kind outside {0, 1}; p1 < p0 on a uniform input or
+ * p1 < 0 on a normal one (the text names the first such input); parameters not set.  SCFGP_ENONFINITE for a non-finite p0, p1 or W.  The
+ * outputs are untouched in both cases.  Out of scope: second-order and higher interaction indices, empirical marginals, dependent inputs,
+ * raw-y units, a row-sharded form (there are no rows) and weights kept on the device between calls. */
+int scfgp_sobol(scfgp_ctx* ctx, const int32_t* kind, const double* p0, const double* p1, const double* W, int nw,
+                double* f0, double* V, double* Vmain, double* Vtot, double* phibar);
+
 /* ---- greedy maximum-information choice of m rows from a pool (no reference counterpart) ----------------------------------------------
  * Which rows should be observed next?  The posterior of a Fourier-feature model is a Bayesian linear model in K weights, and the
  * posterior variance after an observation does not depend on the observed value, so the exact greedy batch needs neither targets nor

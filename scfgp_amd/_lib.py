@@ -54,6 +54,8 @@ SIGNATURES = {
     'scfgp_condition': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
     'scfgp_condition_grad': (C.c_int, [C.c_void_p, _c_double_p, C.c_int64, C.POINTER(C.c_int32), C.c_int, _c_double_p, _c_double_p, _c_double_p,
                                        _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p]),
+    'scfgp_sobol': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), _c_double_p, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p,
+                              _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_forget': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, _c_double_p, _c_double_p,
                                _c_double_p, _c_double_p, _c_double_p]),
     'scfgp_loo': (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p,

@@ -1,9 +1,11 @@
 // Host-side helpers of the posterior and pool entry points (scfgp_api.hip): plain C++17, no HIP, so that a stand-alone program can
-// check them (tests/host/api_host_check.cpp; scfgp_condition_grad's part: tests/host/condgrad_host_check.cpp).
+// check them (tests/host/api_host_check.cpp; scfgp_condition_grad's part: tests/host/condgrad_host_check.cpp; scfgp_sobol's:
+// tests/host/sobol_host_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 // One pass over a weight vector, in index order.  It decides nothing: every caller keeps its own messages and its own order of tests.
 struct WeightScan {
@@ -74,4 +76,53 @@ inline int first_bad_dim(const int32_t* dims, int nd, int D, char* seen) {
         seen[dims[j]] = 1;
     }
     return -1;
+}
+
+// ---- scfgp_sobol: the measure (kind NULL: all uniform; p0, p1: D entries each) and the schedule of the pair kernel -------------------
+inline int sobol_first_bad_kind(const int32_t* kind, int D) {         // first kind outside {0, 1}, -1: none
+    if (kind) for (int d = 0; d < D; ++d) if (kind[d] != 0 && kind[d] != 1) return d;
+    return -1;
+}
+// first input with p1 < p0 (uniform) or p1 < 0 (normal), -1: none; a NaN compares false and is left to sobol_first_nonfinite
+inline int sobol_first_bad_range(const int32_t* kind, const double* p0, const double* p1, int D) {
+    for (int d = 0; d < D; ++d) if (kind && kind[d] == 1 ? p1[d] < 0.0 : p1[d] < p0[d]) return d;
+    return -1;
+}
+inline int sobol_first_nonfinite(const double* p0, const double* p1, int D) {
+    for (int d = 0; d < D; ++d) if (!std::isfinite(p0[d]) || !std::isfinite(p1[d])) return d;
+    return -1;
+}
+// meas (3 x D) as the kernels take it: kind | centre or mean | half width or standard deviation.  The halves are taken before the sum
+// and the difference, so bounds near DBL_MAX do not overflow.
+inline void sobol_measure(const int32_t* kind, const double* p0, const double* p1, int D, double* meas) {
+    for (int d = 0; d < D; ++d) {
+        const bool normal = kind && kind[d] == 1;
+        meas[d] = normal ? 1.0 : 0.0;
+        meas[D + d] = normal ? p0[d] : 0.5 * p0[d] + 0.5 * p1[d];
+        meas[2 * D + d] = normal ? p1[d] : 0.5 * p1[d] - 0.5 * p0[d];
+    }
+}
+// The work units of the pair kernel: the blocks (jb, kb), jb <= kb < nb, of the upper triangle in row-major order, a row cut into runs
+// of at most kseg blocks; a unit is (jb, kb0, kb1).  A column's sum visits the units in this order, so the schedule may depend on the
+// geometry only, never on the number of columns: kseg is the smallest of 16, 32, 64, ... at which the records of one block of `cols`
+// columns (units x nsets x cols doubles) fit `budget` bytes, or one unit per row where none does.
+inline int64_t sobol_unit_count(int nb, int kseg) {
+    int64_t n = 0;
+    for (int jb = 0; jb < nb; ++jb) n += (nb - jb + kseg - 1) / kseg;
+    return n;
+}
+inline int sobol_kseg(int nb, int64_t nsets, int cols, int64_t budget) {
+    int kseg = 16;
+    while (kseg < nb && sobol_unit_count(nb, kseg) * nsets * cols * 8 > budget) kseg *= 2;
+    return kseg;
+}
+inline void sobol_units(int nb, int kseg, std::vector<int>& units) {
+    units.clear();
+    for (int jb = 0; jb < nb; ++jb)
+        for (int kb = jb; kb < nb; kb += kseg) { units.push_back(jb); units.push_back(kb); units.push_back(std::min(kb + kseg, nb)); }
+}
+// columns per pass: as many blocks of `cols` as fit the budget, at least one
+inline int sobol_pass_cols(int64_t nunits, int64_t nsets, int cols, int64_t budget) {
+    const int64_t blocks = budget / (nunits * nsets * cols * 8);
+    return (int)(std::max<int64_t>(1, std::min<int64_t>(blocks, 1 << 10)) * cols);
 }

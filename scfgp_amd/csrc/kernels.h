@@ -415,6 +415,27 @@ struct GradObs { const int* dims; int nd; const double *gfac, *y, *G, *rho; };
 template <typename T>
 void gradobs_rows(const Geom& gr, const Geom& g, const T* Phi, const double* Fall, const GradObs& a, T* Psi, double* tg, hipStream_t st);
 
+// ---- sobol.hip: closed-form Sobol indices under a product measure (scfgp_sobol) -------------------------------------------------------
+constexpr int SOBOL_T = 8;                      // edge of a tile of pairs (j, k)
+constexpr int SOBOL_COLS = 32;                  // weight columns per workgroup of the pair kernel
+constexpr int SOBOL_GROUP = 16;                 // inputs per workgroup of the pair kernel, at most
+// meas (3 x D): kind (0 uniform, 1 normal) | centre or mean | half width or standard deviation.  Jt = round_up(J, SOBOL_T).  psi1[d][j] =
+// psi_d(Fall[d][j]) and Ed[d][j] = E_j without its factor d (D x Jt complex each), E_j = E_mu e^{i z_j}, Eb_j = e^{i b_j} (Jt complex
+// each; entries j >= J are not written), phibar (K, or NULL) = s (Re E | Im E)
+void sobol_tables(const Geom& g, const double* Fall, const Scal* sc, const double* meas, int Jt, double* psi1, double* Ed, double* E,
+                  double* Eb, double* phibar, hipStream_t st);
+// W (K x nw, row-major) -> A (Jt x nw complex) = s (W[j] - i W[J + j]), zero rows from J on; f0 (nw, or NULL) = Re sum_j A_j E_j
+void sobol_weights(const Geom& g, const double* W, const Scal* sc, const double* E, int Jt, int nw, double* A, double* f0, hipStream_t st);
+// The centred quadratic forms of columns w0 .. w0 + ncols of A.  units (3 ints each: block of j, first and one-past-last block of k, blocks
+// of SOBOL_T); G <= SOBOL_GROUP inputs per workgroup; flags: 1 = the whole set, 2 = main effects, 4 = closed sets.  rec (nunits x (1 + 2 D)
+// x ncols): per unit the partial sums of set 0 = all, 1 + d = main effect of d, 1 + D + d = closed set of d; what flags leave out is
+// neither computed nor written
+void sobol_pairs(const Geom& g, const double* Fall, const double* meas, const double* psi1, const double* Ed, const double* E,
+                 const double* Eb, const double* A, const int* units, int nunits, int Jt, int nw, int w0, int ncols, int G, int flags,
+                 double* rec, hipStream_t st);
+// sums ((1 + 2 D) x nw): columns w0 .. w0 + ncols of the sets that flags name = the records added in unit order
+void sobol_reduce(const double* rec, int nunits, int D, int ncols, int nw, int w0, int flags, double* sums, hipStream_t st);
+
 // ---- pd.hip: partial dependence and ICE curves over a pool (scfgp_predict_pd) ----------------------------------------------------------
 // rows that a dimension's G grid points take in the stacked operand Phibar: a multiple of 128, so that predcov finds its padded rows
 inline int pd_grid_rows(int G) { return (int)round_up(G, 128); }

@@ -129,7 +129,7 @@ struct scfgp_ctx {
     // Ranks decide together (common.h: XS_*).  `unsettled`: a precision level was raised (or refused) since the last sum over
     // ranks, so the next exchange 1 carries every rank's attainable level and scfgp_factor commits to the lowest before pass 2
     // runs; cap(): the highest level this rank can run at.  test_*: fault injection for the tests (scfgp_set_option).
-    bool unsettled = false; int test_deny_level = 0, test_fail_stage = 0, test_pd_group = 0;
+    bool unsettled = false; int test_deny_level = 0, test_fail_stage = 0, test_pd_group = 0, test_sobol_group = 0;
     int cap() const { return esc_denied > 0 ? esc_denied - 1 : 2; }
     double* x3_xu() { return d_x3 + (int64_t)Dpp * g.Jp + 8; }
     hipEvent_t ev_fence = nullptr;                                          // scfgp_stream_fence
@@ -2848,6 +2848,87 @@ extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const
 }
 
 // ----------------------------------------------------------------------------------------------
+// closed-form Sobol indices under a product measure (sobol.hip; derivation in include/scfgp_hip.h)
+// ----------------------------------------------------------------------------------------------
+static constexpr int SOBOL_MAX_NW = SAMPLE_MAX;
+static constexpr int64_t SOBOL_RECORD_BYTES = GRADCOV_SLOT_BYTES;  // the workgroups' records of one pass over a block of columns
+// No rows, no factors, no scaler: the tables from Fall / Scal, then the columns of W in passes whose records fit SOBOL_RECORD_BYTES.  The
+// schedule of the pair kernel (api_host.h) depends on J and D only, so a column has one summation order whatever nw is.
+extern "C" int scfgp_sobol(scfgp_ctx* c, const int32_t* kind, const double* p0, const double* p1, const double* W, int nw, double* f0,
+                           double* V, double* Vmain, double* Vtot, double* phibar) {
+    if (!c) return SCFGP_EARG;
+    const Fail f = {c, "sobol"};
+    const Geom& g = c->g;
+    const int D = g.D, J = g.J, K = g.K;
+    const bool cols = f0 || V || Vmain || Vtot;
+    if (!p0 || !p1) return f.arg("p0 and p1 are needed");
+    if (!cols && !phibar) return f.arg("no output asked for");
+    if (cols && !W) return f.arg("W is needed for f0, V, Vmain and Vtot");
+    if (cols && (nw < 1 || nw > SOBOL_MAX_NW)) return f.arg("nw must lie in 1..1024");
+    if (int d = sobol_first_bad_kind(kind, D); d >= 0) return f.arg("kind[" + std::to_string(d) + "] must be 0 (uniform) or 1 (normal)");
+    if (int d = sobol_first_bad_range(kind, p0, p1, D); d >= 0)
+        return f.arg("input " + std::to_string(d) + (kind && kind[d] == 1 ? ": p1 (the standard deviation) is negative" : ": p1 < p0 on a uniform input"));
+    if (int rc = need_model(f, false)) return rc;
+    if (int d = sobol_first_nonfinite(p0, p1, D); d >= 0) return f.nonfinite("non-finite measure at input " + std::to_string(d));
+    if (cols)
+        for (int64_t i = 0; i < (int64_t)K * nw; ++i)
+            if (!std::isfinite(W[i])) return f.nonfinite("non-finite W");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!cols) nw = 0;
+
+    const int Jt = (int)round_up(J, SOBOL_T), nb = Jt / SOBOL_T, nsets = 1 + 2 * D;
+    const int flags = (V || Vtot ? 1 : 0) | (Vmain ? 2 : 0) | (Vtot ? 4 : 0);
+    std::vector<int> units;
+    int pass = 0;
+    if (flags) {
+        sobol_units(nb, sobol_kseg(nb, nsets, SOBOL_COLS, SOBOL_RECORD_BYTES), units);
+        pass = std::min<int>((int)round_up(nw, SOBOL_COLS), sobol_pass_cols((int64_t)units.size() / 3, nsets, SOBOL_COLS, SOBOL_RECORD_BYTES));
+    }
+    const int64_t nunits = (int64_t)units.size() / 3;
+    int G = std::min(D, SOBOL_GROUP);
+    if (c->test_sobol_group > 0) G = std::min(G, c->test_sobol_group);
+    // one allocation: meas | psi1 | Ed | E | Eb | phibar | W | A | f0 | sums | units | rec
+    const int64_t n_meas = 3 * D, n_tab = 2 * (int64_t)D * Jt, n_e = 2 * Jt, n_w = (int64_t)K * nw, n_a = 2 * (int64_t)Jt * nw,
+                  n_sums = (int64_t)nsets * nw, n_units = (3 * nunits + 1) / 2, n_rec = nunits * nsets * pass;
+    DevTmp buf;
+    if (int rc = dmalloc(c, &buf.p, sizeof(double) * (n_meas + 2 * n_tab + 2 * n_e + K + n_w + n_a + nw + n_sums + n_units + n_rec))) return rc;
+    double* d_meas = buf.p; double* d_psi1 = d_meas + n_meas; double* d_Ed = d_psi1 + n_tab; double* d_E = d_Ed + n_tab;
+    double* d_Eb = d_E + n_e; double* d_phibar = d_Eb + n_e; double* d_W = d_phibar + K; double* d_A = d_W + n_w; double* d_f0 = d_A + n_a;
+    double* d_sums = d_f0 + nw; int* d_units = (int*)(d_sums + n_sums); double* d_rec = d_sums + n_sums + n_units;
+
+    std::vector<double> h(std::max<int64_t>(n_meas, K + nw + n_sums));
+    sobol_measure(kind, p0, p1, D, h.data());
+    HIPCHK(c, hipMemcpyAsync(d_meas, h.data(), sizeof(double) * n_meas, hipMemcpyHostToDevice, c->st));
+    if (cols) HIPCHK(c, hipMemcpyAsync(d_W, W, sizeof(double) * n_w, hipMemcpyHostToDevice, c->st));
+    if (nunits) HIPCHK(c, hipMemcpyAsync(d_units, units.data(), sizeof(int) * 3 * nunits, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));                      // h is reused for the results
+    { ProfScope ps(c, "sobol_tables"); sobol_tables(g, c->d_Fall, c->d_sc, d_meas, Jt, d_psi1, d_Ed, d_E, d_Eb, d_phibar, c->st); }
+    if (cols) { ProfScope ps(c, "sobol_weights"); sobol_weights(g, d_W, c->d_sc, d_E, Jt, nw, d_A, d_f0, c->st); }
+    for (int w0 = 0; flags && w0 < nw; w0 += pass) {
+        const int ncols = std::min(pass, nw - w0);
+        { ProfScope ps(c, "sobol_pairs");
+          sobol_pairs(g, c->d_Fall, d_meas, d_psi1, d_Ed, d_E, d_Eb, d_A, d_units, (int)nunits, Jt, nw, w0, ncols, G, flags, d_rec, c->st); }
+        { ProfScope ps(c, "sobol_reduce"); sobol_reduce(d_rec, (int)nunits, D, ncols, nw, w0, flags, d_sums, c->st); }
+    }
+    HIPCHK(c, hipGetLastError());
+    // phibar | f0 | sums are adjacent on the device only up to W and A in between: three copies
+    double* h_phibar = h.data(); double* h_f0 = h_phibar + K; double* h_sums = h_f0 + nw;
+    HIPCHK(c, hipMemcpyAsync(h_phibar, d_phibar, sizeof(double) * K, hipMemcpyDeviceToHost, c->st));
+    if (cols) HIPCHK(c, hipMemcpyAsync(h_f0, d_f0, sizeof(double) * nw, hipMemcpyDeviceToHost, c->st));
+    if (flags) HIPCHK(c, hipMemcpyAsync(h_sums, d_sums, sizeof(double) * n_sums, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    if (phibar) memcpy(phibar, h_phibar, sizeof(double) * K);
+    if (f0) memcpy(f0, h_f0, sizeof(double) * nw);
+    if (V) memcpy(V, h_sums, sizeof(double) * nw);
+    for (int w = 0; w < nw; ++w)
+        for (int d = 0; d < D; ++d) {
+            if (Vmain) Vmain[(int64_t)w * D + d] = h_sums[(int64_t)(1 + d) * nw + w];
+            if (Vtot) Vtot[(int64_t)w * D + d] = h_sums[w] - h_sums[(int64_t)(1 + D + d) * nw + w];
+        }
+    return SCFGP_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // greedy maximum-information choice of m rows from a pool (select.hip; derivation in include/scfgp_hip.h)
 // ----------------------------------------------------------------------------------------------
 static constexpr int SELECT_MAX_M = 4096;
@@ -3488,6 +3569,7 @@ extern "C" int scfgp_set_option(scfgp_ctx* c, const char* name, int64_t value) {
     else if (s == "roctx") c->roctx_on = value != 0;
     else if (s == "test_deny_level") { c->test_deny_level = (int)value; return SCFGP_OK; }       // tests: levels >= value are refused as if out of memory
     else if (s == "test_pd_group") { c->test_pd_group = (int)value; return SCFGP_OK; }         // tests: scfgp_predict_pd takes at most `value` dimensions per group
+    else if (s == "test_sobol_group") { c->test_sobol_group = (int)value; return SCFGP_OK; }   // tests: scfgp_sobol takes at most `value` inputs per workgroup
     else if (s == "test_fail_stage") { c->test_fail_stage = (int)value; return SCFGP_OK; }       // tests: the next sweep `value` (1..3) fails
     else { c->err = "unknown option " + s; return SCFGP_EARG; }
     // kernels not run so far, buffers not allocated so far: the next scfgp_train starts with an eager iteration again

@@ -803,6 +803,41 @@ class HipEngine(object):
         """Points per chunk of condition_grad (the formula of include/scfgp_hip.h): whole blocks of nb = nd + (1 with values) rows"""
         return 32768 // (int(nd) + (1 if values else 0))
 
+    SOBOL_OUTPUTS = ('f0', 'V', 'Vmain', 'Vtot', 'phibar')
+
+    def sobol(self, kind, p0, p1, W=None, want=('f0', 'V', 'Vmain', 'Vtot')):
+        """Closed-form Sobol variances of the sample functions W under a product measure over the SCALED inputs (include/scfgp_hip.h:
+        scfgp_sobol).  kind (D,) ints: 0 = uniform on [p0, p1], 1 = normal(p0, p1^2) (None: all uniform); W (K, nw) as sample_weights
+        returns it, or (K,) / (K, 1) such as alpha for the posterior mean.  Returns a dict of the outputs named in want: 'f0' (nw,)
+        the mean of f, 'V' (nw,) its variance, 'Vmain', 'Vtot' (nw, D) the main-effect and total-effect variances, 'phibar' (K,) the
+        mean feature vector.  The Sobol indices are Vmain / V and Vtot / V; V may be 0."""
+        want = tuple(want)
+        bad = [k for k in want if k not in self.SOBOL_OUTPUTS]
+        if bad:
+            raise ValueError('sobol: unknown output %r (one of %s)' % (bad[0], ', '.join(self.SOBOL_OUTPUTS)))
+        p0 = np.ascontiguousarray(p0, dtype=np.float64).reshape(-1)
+        p1 = np.ascontiguousarray(p1, dtype=np.float64).reshape(-1)
+        if p0.size != self.D or p1.size != self.D:
+            raise ValueError('sobol: p0 and p1 must have D=%d entries' % self.D)
+        k32 = None
+        if kind is not None:
+            k32 = np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+            if k32.size != self.D:
+                raise ValueError('sobol: kind must have D=%d entries' % self.D)
+        nw = 0
+        if W is not None:
+            W = np.asarray(W, dtype=np.float64)
+            W = np.ascontiguousarray(W.reshape(-1, 1) if W.ndim == 1 else W)
+            if W.ndim != 2 or W.shape[0] != self.K:
+                raise ValueError('sobol: W must be (K, nw) with K=%d' % self.K)
+            nw = W.shape[1]
+        shapes = {'f0': (nw,), 'V': (nw,), 'Vmain': (nw, self.D), 'Vtot': (nw, self.D), 'phibar': (self.K,)}
+        out = {k: np.empty(shapes[k]) for k in want}
+        rc = self.lib.scfgp_sobol(self.ctx, None if k32 is None else k32.ctypes.data_as(C.POINTER(C.c_int32)), dptr(p0), dptr(p1), dptr(W), nw,
+                                  *[dptr(out.get(k)) for k in self.SOBOL_OUTPUTS])
+        self._check_undelivered(rc, 'sobol')
+        return out
+
     FORGET_STATS = ('n', 'sum_e2', 'sum_abs_e', 'sum_log_marginal', 'log_joint', 'min_pivot2', 'blocks')
 
     def forget(self, X, y, alpha, Li, factors=True, predict=False, mode='scaled'):

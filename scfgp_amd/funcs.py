@@ -342,6 +342,37 @@ class CompiledFuncs(object):
         self._sync_scalers(x_scaler, None)
         return self.engine.predict_pd(Xs_raw, alpha, Li, dims, grid, w=w, mode='raw', want=want)
 
+    def sobol_raw(self, kind, p0, p1, x_scaler, W=None, want=('f0', 'V', 'Vmain', 'Vtot'), scaled=False):
+        """Closed-form Sobol variances (engine.sobol) of the sample functions W under a product measure stated per RAW column: kind
+        (D_raw,) 0 = uniform on [p0, p1], 1 = normal(p0, p1^2) (None: all uniform), in raw X units.  An affine X scaler ('min-max',
+        'normal') maps such an input to one of the same kind -- bounds and mean through the transform, the standard deviation through its
+        slope -- on the columns it kept; any other scaler does not, and the call raises a ValueError unless scaled=True states that the
+        measure is already in scaled units.  What refers to a constant column that the scaler dropped is ignored.  Vmain and Vtot come
+        back (nw, D_raw) with zeros at the dropped columns, as predict_grad's gradients do."""
+        from .engine import _scatter
+        self._sync_params()
+        cols = [int(cc) for cc in x_scaler.data['cols']]
+        p0 = np.asarray(p0, dtype=np.float64).reshape(-1); p1 = np.asarray(p1, dtype=np.float64).reshape(-1)
+        D_raw = p0.size
+        kind = np.zeros(D_raw, dtype=np.int32) if kind is None else np.asarray(kind, dtype=np.int32).reshape(-1)
+        if p1.size != D_raw or kind.size != D_raw or (cols and max(cols) >= D_raw):
+            raise ValueError('sobol: kind, p0 and p1 need one entry per raw column')
+        k, q0, q1 = kind[cols], p0[cols], p1[cols]
+        if not scaled:
+            if not x_scaler.affine:
+                raise ValueError("sobol: the X scaler %r is not affine, so a uniform or normal raw input is neither after it: state the "
+                                 "measure in scaled units (scaled=True)" % x_scaler.algo)
+            z = np.zeros((1, D_raw))
+            off = np.asarray(x_scaler.forward_transform(z), dtype=np.float64)[0]             # x~ = off + slope x, slope > 0
+            slope = np.asarray(x_scaler.forward_derivative(z), dtype=np.float64)[0]
+            q0 = off + slope * q0
+            q1 = np.where(k == 1, slope * q1, off + slope * q1)
+        out = self.engine.sobol(k, q0, q1, W, want=want)
+        for key in ('Vmain', 'Vtot'):
+            if key in out:
+                out[key] = _scatter(out[key], cols, D_raw)
+        return out
+
     def pred_cov_raw(self, Xa_raw, x_scaler, Li, Xb_raw=None, noise=False):
         """Joint posterior covariance of the scaled target between the raw rows Xa_raw and Xb_raw (None: among Xa_raw): (Ta, Tb)."""
         self._sync_params()

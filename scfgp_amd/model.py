@@ -19,6 +19,7 @@ Deliberate departures from the reference:
 import string
 import sys
 import time
+import warnings
 
 import numpy as np
 import numpy.random as npr
@@ -285,6 +286,73 @@ class SCFGP(object):
         asub = owner.pred_gradcov_raw(Xs, self.X_scaler, self.alpha, self.Li, w=w, want=('asub',))['asub']
         lam, vec = np.linalg.eigh(asub)
         return lam[::-1].copy(), vec[:, ::-1].copy(), asub
+
+    def _measure(self, who, bounds, measure):
+        """(kind, p0, p1, scaled) of sobol / integral: bounds (D_raw, 2) = uniform raw inputs, measure = (kind, p0, p1) per raw column
+        in raw units; neither: uniform on the per-column range of the scaled training inputs, at the kept columns"""
+        if bounds is not None and measure is not None:
+            raise ValueError('%s: give bounds or measure, not both' % who)
+        if measure is not None:
+            kind, p0, p1 = measure
+            return kind, np.asarray(p0, dtype=np.float64), np.asarray(p1, dtype=np.float64), False
+        if bounds is not None:
+            b = np.asarray(bounds, dtype=np.float64)
+            if b.ndim != 2 or b.shape[1] != 2:
+                raise ValueError('%s: bounds must be (D, 2)' % who)
+            return None, b[:, 0].copy(), b[:, 1].copy(), False
+        if getattr(self, 'X', None) is None:
+            raise ValueError('%s: no training inputs to take the default measure from (a restored checkpoint): give bounds or measure' % who)
+        cols = [int(cc) for cc in self.X_scaler.data['cols']]
+        D_raw = max(cols) + 1
+        p0 = np.zeros(D_raw); p1 = np.zeros(D_raw)
+        p0[cols] = self.X.min(0); p1[cols] = self.X.max(0)
+        return None, p0, p1, True
+
+    def sobol(self, bounds=None, measure=None, nsamples=0, seed=0):
+        """Variance-based sensitivity of the fitted function under a product measure over the inputs, in closed form (include/
+        scfgp_hip.h: scfgp_sobol): a dict with 'S' (D_raw,) the first-order and 'T' (D_raw,) the total-effect Sobol indices of the
+        posterior MEAN, 'V' its variance and 'f0' its mean in SCALED y units (the y scaler's backward transform is not affine:
+        partial_dependence's argument).  bounds (D_raw, 2): independent uniform inputs in raw X units; measure = (kind, p0, p1) per raw
+        column: 0 = uniform on [p0, p1], 1 = normal(p0, p1^2); both need an affine X scaler ('min-max', 'normal').  Neither: uniform on
+        the range of the scaled training inputs, which any scaler allows.  Columns the scaler dropped get S = T = 0.  nsamples > 0 adds
+        the posterior distribution of every index over that many exact draws of the weights (sample_weights with `seed`): 'S_samples',
+        'T_samples' (nsamples, D_raw), 'V_samples', and 'S_mean', 'S_q05', 'S_q95', 'T_mean', 'T_q05', 'T_q95' (NaN-aware).  A function
+        whose variance is not above rounding level (1e-12 of its mean square) has no indices: NaN, not a division by zero."""
+        owner = self._owner('sobol')
+        kind, p0, p1, scaled = self._measure('sobol', bounds, measure)
+
+        def ratios(o):
+            V = o['V']
+            ok = V > 1e-12 * (V + o['f0'] ** 2)
+            den = np.where(ok, V, np.nan)[:, None]
+            with np.errstate(invalid='ignore', divide='ignore'):
+                return o['Vmain'] / den, o['Vtot'] / den
+
+        o = owner.sobol_raw(kind, p0, p1, self.X_scaler, np.asarray(self.alpha, dtype=np.float64).reshape(-1, 1), scaled=scaled)
+        S, T = ratios(o)
+        out = {'S': S[0], 'T': T[0], 'V': float(o['V'][0]), 'f0': float(o['f0'][0])}
+        if nsamples > 0:
+            W = owner.sample_weights(self.alpha, self.Li, int(nsamples), seed=seed)
+            os_ = owner.sobol_raw(kind, p0, p1, self.X_scaler, W, scaled=scaled)
+            Ss, Ts = ratios(os_)
+            out.update(S_samples=Ss, T_samples=Ts, V_samples=os_['V'])
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)          # a column that is NaN in every sample
+                for name, v in (('S', Ss), ('T', Ts)):
+                    out[name + '_mean'] = np.nanmean(v, 0)
+                    out[name + '_q05'], out[name + '_q95'] = np.nanquantile(v, [0.05, 0.95], 0)
+        return out
+
+    def integral(self, bounds=None, measure=None):
+        """Bayesian quadrature: (mean, sd) of the integral of the latent function against the product measure of sobol(), in SCALED y
+        units: int f dmu ~ N(phibar^T alpha, kappa |Li phibar|^2) with phibar = E_mu phi(x) from the device (scfgp_sobol) and the
+        K-vector products on the host."""
+        owner = self._owner('integral')
+        kind, p0, p1, scaled = self._measure('integral', bounds, measure)
+        phibar = owner.sobol_raw(kind, p0, p1, self.X_scaler, None, want=('phibar',), scaled=scaled)['phibar']
+        kappa = float(np.log1p(np.exp(owner.params.get_value(borrow=True)[2])))
+        mean = float(phibar @ np.asarray(self.alpha, dtype=np.float64).reshape(-1))
+        return mean, float(np.sqrt(kappa) * np.linalg.norm(np.asarray(self.Li, dtype=np.float64) @ phibar))
 
     def partial_dependence(self, X, dims=None, grid=20, weights=None, ice=False, cov=False):
         """Partial-dependence (PD) curves of single inputs over the raw pool rows X, with their exact posterior uncertainty: a dict with

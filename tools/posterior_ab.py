@@ -10,8 +10,9 @@ symmetric at 2500 rows, cross at all rows x 50 and at 2500 x 9000 (two panels pe
 1, 7, 64 from host rows and block 7 on resident rows; select without weights and with weights around the chunk boundaries, with
 std_after; predict_gradcov with all four outputs and weights over three chunks, in raw mode, and with its default outputs over all rows;
 predict_pd with all four outputs and weights over all rows for three dimensions, in raw mode, and with its default outputs for every
-dimension; condition_grad over three chunks of whole points with values and a rho that holds zeros, and in raw mode along two dims (each
-of the last three where the build has it: outputs that only one build produces are listed as new, not as different); with
+dimension; condition_grad over three chunks of whole points with values and a rho that holds zeros, and in raw mode along two dims; sobol
+with all five outputs for 40 sampled columns under a mixed measure (each of the last four where the build has it: outputs that only one
+build produces are listed as new, not as different); with
 weights that are zero across every chunk boundary, at both shapes, sample_argmax in mode y with and without them, acquire in raw mode for
 its five kinds (ei with grad), acquire_kg symmetric and with Xr with the node table, select_iv with Xr and wr and as its own reference;
 at the second shape sample_grad with sidx, select_qei with pending rows and forget (a refusal is compared as its text).  With three
@@ -112,6 +113,11 @@ def calls(D, S, M, n, dt):
         rz = rng.choice([0.0, 0.25, 1.0, 100.0], size=(n3, D))
         yield 'condition_grad scaled %d points, values, rho with zeros' % n3, eng.condition_grad(X[:n3], Gd, alpha, Li, rho=rz, y=y[:n3])
         yield 'condition_grad raw 2500 points, dims', eng.condition_grad(Xr[:2500], Gd[:2500, [D - 1, 0]], alpha, Li, dims=[D - 1, 0], raw=True)
+    if hasattr(eng.lib, 'scfgp_sobol'):                          # the same: new in a build that has it
+        kind = (np.arange(D) % 2).astype(np.int32)
+        out = eng.sobol(kind, np.where(kind == 1, 0.5, 0.0), np.where(kind == 1, 0.25, 1.0), eng.sample_weights(alpha, Li, 40, seed=5),
+                        want=('f0', 'V', 'Vmain', 'Vtot', 'phibar'))
+        yield 'sobol mixed measure, 40 sampled columns, all outputs', tuple(out[k] for k in ('f0', 'V', 'Vmain', 'Vtot', 'phibar'))
     # the pool entry points: those that feed weights as targets at both shapes (wz: zero across every chunk boundary), the rest at the
     # second shape only
     wz = np.ones(n)
