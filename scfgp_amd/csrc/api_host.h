@@ -1,6 +1,6 @@
-// Host-side helpers of the posterior and pool entry points (scfgp_api.hip): plain C++17, no HIP, so that a stand-alone program can
-// check them (tests/host/api_host_check.cpp; scfgp_condition_grad's part: tests/host/condgrad_host_check.cpp; scfgp_sobol's:
-// tests/host/sobol_host_check.cpp).
+// Host-side helpers of the posterior and pool entry points (api_predict.hip, api_update.hip, api_pool.hip): plain C++17, no HIP, so
+// that a stand-alone program can check them (tests/host/api_host_check.cpp; scfgp_condition_grad's part:
+// tests/host/condgrad_host_check.cpp; scfgp_sobol's: tests/host/sobol_host_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -114,5 +114,5 @@ void gradobs_rows(const Geom& gr, const Geom& g, const T* Phi, const double* Fal
                        g.N, Psi, tg);
 }
 
-// the update's first pass is fp64 in every context (scfgp_api.hip: scfgp_condition_grad), so this is the instantiation that runs
+// the update's first pass is fp64 in every context (api_update.hip: scfgp_condition_grad), so this is the instantiation that runs
 template void gradobs_rows<double>(const Geom&, const Geom&, const double*, const double*, const GradObs&, double*, double*, hipStream_t);

@@ -1,82 +1,11 @@
-// C ABI of libscfgp_hip.so (declared in include/scfgp_hip.h): context, device memory,
-// the staged evaluation  pass1 | factor | pass2 | adjoint | pass3 | finish  and predict.
-#include "../../include/scfgp_hip.h"
-#include "kernels.h"
-#include "api_host.h"
+// C ABI of libscfgp_hip.so (declared in include/scfgp_hip.h), the evaluation side: context, device memory, the staged evaluation
+// pass1 | factor | pass2 | adjoint | pass3 | finish, the optimiser and training, the sums over ranks, options and debug reads.  The
+// posterior and pool entry points are in api_predict.hip, api_update.hip and api_pool.hip.
+#include "api_ctx.h"
 
-#include <dlfcn.h>
-// RCCL: types and prototypes only -- the library is looked up at run time (scfgp_comm_init), no link-time dependency.  A ROCm
-// install without the RCCL development headers still builds: the handful of declarations used here are then spelled out
-// (they are RCCL's public, NCCL-compatible ABI).
-#if __has_include(<rccl/rccl.h>)
-#include <rccl/rccl.h>
-#else
-extern "C" {
-typedef struct ncclComm* ncclComm_t;
-typedef struct { char internal[128]; } ncclUniqueId;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclFloat64 = 8 } ncclDataType_t;
-typedef enum { ncclSum = 0 } ncclRedOp_t;
-ncclResult_t ncclGetUniqueId(ncclUniqueId*);
-ncclResult_t ncclCommInitRank(ncclComm_t*, int, ncclUniqueId, int);
-ncclResult_t ncclAllReduce(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t);
-ncclResult_t ncclCommDestroy(ncclComm_t);
-const char* ncclGetErrorString(ncclResult_t);
-}
-#endif
-
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#define HIPCHK(ctx, call)                                                                           \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return SCFGP_EHIP;                                                                      \
-        }                                                                                           \
-    } while (0)
-
-static constexpr int XT = 128;              // tile of the X~^T Zbar product and padding unit of J (kernels_sweep.hip)
-static constexpr int64_t PRED_ROWS = 32768; // predict processes test rows in chunks of this size
-// Thresholds of the automatic precision escalation and the error model behind them (profiles/r03_c3_owner.md): with the
-// fp32 Gram products (4096-row flush interval, relative error ~6e-8) the relative error of alpha / Li, and of the frequency
-// gradient blocks, against fp64 mode is about SCFGP_ERR_PER_COND times the condition estimate (measured 7e-8 .. 2e-6 times
-// the estimate at estimates 4 .. 6.4e3: the estimate is a lower bound of cond_2 of varying tightness).  Level 1 keeps the predicted alpha error under 3e-6 (north star: 1e-5), level 2
-// the predicted gradient error under 3e-4 (SURVEY App. E acceptance: 1e-3 per block).
-#ifndef SCFGP_COND_THRESHOLD
-#define SCFGP_COND_THRESHOLD 10.0
-#endif
-#ifndef SCFGP_COND_THRESHOLD_W
-#define SCFGP_COND_THRESHOLD_W 1000.0
-#endif
-#ifndef SCFGP_ERR_PER_COND
-#define SCFGP_ERR_PER_COND 3.0e-7
-#endif
 static void derive_geom(Geom& g, int D, int S, int M);
-static Geom chunk_geom(const Geom& g0, int64_t rows);
 
 thread_local bool g_scfgp_capturing = false;
-
-// roctx ranges around every stage (visible in `rocprofv3 --marker-trace`): OPT-IN (environment SCFGP_ROCTX=1 at context
-// creation or option "roctx"); only then is the profiler's roctx library looked up, at run time, so the product has no
-// link-time dependency on the profiler SDK and an ordinary process never loads it
-struct Roctx {
-    int (*push)(const char*) = nullptr; int (*pop)() = nullptr;
-    Roctx() {
-        void* h = dlopen("librocprofiler-sdk-roctx.so", RTLD_LAZY | RTLD_LOCAL);
-        if (!h) h = dlopen("libroctx64.so", RTLD_LAZY | RTLD_LOCAL);
-        if (!h) return;
-        push = (int (*)(const char*))dlsym(h, "roctxRangePushA");
-        pop = (int (*)())dlsym(h, "roctxRangePop");
-        if (!push || !pop) { push = nullptr; pop = nullptr; }
-    }
-};
-static Roctx& roctx() { static Roctx r; return r; }
 
 // RCCL, resolved at run time the first time a communicator is asked for: a process that already carries a copy (the host
 // framework's, e.g. torch's librccl.so) is served by that copy, otherwise ROCm's is loaded.  Single-GPU users never load it.
@@ -107,194 +36,6 @@ struct Rccl {
     bool ok() const { return resolved; }
 };
 static Rccl& rccl() { static Rccl r; return r; }
-
-struct ProfRec { std::string name; hipEvent_t e0, e1; };
-
-struct scfgp_ctx {
-    Geom g{};
-    int dtype = 0, device = 0;
-    hipStream_t st = nullptr; bool own_stream = false;
-    hipStream_t copy_st = nullptr; hipEvent_t ev_factor = nullptr;          // alpha/Li D2H beside pass 2/3 ...
-    // rank-S form of the backward projection: exchange 3 = [T~^T Zbar (Spp x Jp) ... | 8 scalars at Dpp*Jp | X~^T U (Dpp x Sq)]
-    int lowrank_bwd = -1; int Spp = 0, Sq = 0; bool last_lrb = false;
-    bool want_lrb() const {
-        // T~ = [X l_F | 1] exists only when the forward projection goes through the S columns (g.lowrank), and U needs room in
-        // Phibar's dead sine half
-        const bool fits = g.lowrank && g.Jp + (int)round_up(g.S, 64) <= g.Kp;
-        return fits && (lowrank_bwd == 1 || (lowrank_bwd < 0 && g.Dp >= 4 * g.Sp));
-    }
-    double* x3_scalars() { return d_x3 + (int64_t)Dpp * g.Jp; }
-    double* xs1() { return d_xp1 + n_pk + g.Kp; }                           // the 8 scalars that close exchange buffers 1 and 2
-    double* xs2() { return d_xp2 + n_pk + g.Kp; }
-    // Ranks decide together (common.h: XS_*).  `unsettled`: a precision level was raised (or refused) since the last sum over
-    // ranks, so the next exchange 1 carries every rank's attainable level and scfgp_factor commits to the lowest before pass 2
-    // runs; cap(): the highest level this rank can run at.  test_*: fault injection for the tests (scfgp_set_option).
-    bool unsettled = false; int test_deny_level = 0, test_fail_stage = 0, test_pd_group = 0, test_sobol_group = 0;
-    int cap() const { return esc_denied > 0 ? esc_denied - 1 : 2; }
-    double* x3_xu() { return d_x3 + (int64_t)Dpp * g.Jp + 8; }
-    hipEvent_t ev_fence = nullptr;                                          // scfgp_stream_fence
-    ncclComm_t comm = nullptr; int comm_ranks = 0, comm_rank = 0;           // scfgp_comm_init: the three sums run inside the library
-    double* h_pin = nullptr;                                                // ... through pinned staging (K*K + K doubles)
-    int64_t Ncap = 0, Nglobal = 0, Nglobal_full = 0;        // Nglobal_full: n_global given to scfgp_set_data
-    bool have_params = false, have_data = false;
-    int stage = 0, last_want_grad = 0;
-    std::vector<double> h_params;
-    // parameters
-    double *d_params = nullptr, *d_F = nullptr, *d_Fall = nullptr, *d_Lall = nullptr, *d_Rall = nullptr; Scal* d_sc = nullptr;
-    double *d_Tt = nullptr, *p_Tt = nullptr;                     // T~ = X~ Lall of the rank-S projection (rows / predict chunk)
-    // dataset store (raw rows as uploaded) and the working set the sweeps run on
-    double *d_Xraw = nullptr, *d_yraw = nullptr; int64_t Nstore = 0, store_cap = 0; bool work_full = false;
-    int64_t* d_idx = nullptr; int64_t idx_cap = 0;
-    // rows
-    double *d_Xt = nullptr, *d_y = nullptr, *d_p = nullptr, *d_q = nullptr, *d_mu = nullptr, *d_vpart = nullptr;
-    void *d_Phi = nullptr, *d_V = nullptr;
-    // compute mode SCFGP_F16X3 (apply_f16.hip): fp32 mode whose two square apply products run as a three-term fp16 split wherever
-    // fp32 mode would use its 256-wide LDS-DMA tiles; Phi16 = Phi in plane form (kernels.h), B16 = the K x K operand in plane form
-    bool split16 = false; unsigned* d_Phi16 = nullptr; char* d_B16 = nullptr; float* d_f16scale = nullptr;
-    // ... and the two Gram products too (gram_f16.hip): pass 1's on Phi16, pass 2's on the plane forms of V and of diag(q) V; block
-    // partials of the side vectors; 8 floats of bounds and scales
-    unsigned* d_V16g = nullptr; unsigned* d_qV16g = nullptr; double* d_f16side = nullptr; float* d_f16tmp = nullptr;
-    int f16gram = 1;                                             // tuning knob "f16_gram": 0 keeps the fp32 Gram in this mode
-    bool f16_on() const { return split16 && dma() == 2; }
-    // rows per job and per slab set of the fp16 Gram (its fp32 chains end every 512 rows whatever this is): twice the fp32 Gram's flush
-    // interval, less where that would leave fewer than 512 jobs = two rounds of the chip
-    int64_t f16_chunk() const {
-        const int64_t top = gram_chunk > 0 ? 2 * gram_chunk : 8192, fill = g.Np * F16x3Kernels::gram_tiles(g) / 512 / 512 * 512;
-        return std::max<int64_t>(std::min(top, fill), 1024);
-    }
-    bool f16_gram() const { return f16_on() && f16gram && !last_cform; }      // factor form (level 2) keeps its fp32 products
-    F16Operands f16ops() const { return F16Operands{d_Phi16, d_B16, d_f16scale, nullptr, d_f16tmp + 5}; }
-    // exchange buffers and K-stage
-    // exchange buffers xp1/xp2 = [packed lower tiles | vector Kp | 8 scalars], x3 = [X~^T Zbar | 8 scalars];
-    // x1/x2 = the same matrices unpacked to full Kp x Kp (+ vector) for the K x K stage
-    double *d_xp1 = nullptr, *d_xp2 = nullptr; int64_t n_xp = 0, n_pk = 0;
-    double *d_x1 = nullptr, *d_x2 = nullptr, *d_x3 = nullptr; int64_t n_x1 = 0, n_x2 = 0, n_x3 = 0; int Dpp = 0;
-    double *d_Li = nullptr, *d_B = nullptr, *d_T1 = nullptr, *d_T2 = nullptr, *d_Abar = nullptr;
-    void *d_BT = nullptr, *d_AbarT = nullptr;                      // sweep operands: typed copies of B (or Li) and Abar (or Li^T)
-    int apply_dma = -1;                                            // option: -1 = by problem size, 0 off, 1 = 128-wide tiles, 2 = 256-wide (fp32)
-    double *d_vecs = nullptr;            // beta, alpha, u, ut, alpha_pred (Kp each)
-    double *d_scalars = nullptr, *d_yy = nullptr; int* d_flag = nullptr;
-    float* d_ws2 = nullptr;                                        // fp32 mode: packed (weight, side multiplier) rows of the Gram launches (kernels.h)
-    double *d_slabs = nullptr; size_t slabs_bytes = 0;
-    double *d_partial = nullptr; int64_t n_partial = 0;
-    double *d_work = nullptr, *d_grad = nullptr;
-    int xs_mode = 0; double* d_xscale = nullptr;                 // X scaler for scfgp_predict_raw (5*D doubles)
-    int ys_mode = 0; double* d_yscale = nullptr;                 // y scaler for scfgp_predict_y (5 doubles)
-    // predict chunk buffers
-    double *p_Xt = nullptr, *p_vpart = nullptr, *p_mupart = nullptr; void *p_Phi = nullptr;
-    int64_t p_rows = 0;                                          // padded rows of the chunk p_Xt holds (debug_read "pXt")
-    // ... and those of scfgp_predict_grad, allocated by its first call: FT = Fall^T typed; with the std gradient C = Phi* Li^T, V = C Li
-    // (PRED_ROWS x Kp each, typed) and the typed Li
-    void *p_FT = nullptr, *p_C = nullptr, *p_V = nullptr, *p_Li = nullptr;
-    // ... and those of scfgp_condition, allocated by its first call (ensure_update): the update stage's own K x K matrices (fp64: the old
-    // factor, S / Li', M, M^-1, S^-1; typed: Li^T), its vectors [alpha | gamma | alpha' | 32 partial sums] (Kp each), the summed and the
-    // per-chunk [packed C^T C | C^T r], targets and residuals of a chunk, the Gram launch's slabs, row weights and queue heads
-    // (u_flag: [0] Cholesky flag, [1] non-finite flag, [8..15] queue heads)
-    double *u_Li = nullptr, *u_S = nullptr, *u_Lm = nullptr, *u_Mi = nullptr, *u_Si = nullptr, *u_vec = nullptr, *u_acc = nullptr, *u_part = nullptr;
-    double *u_y = nullptr, *u_r = nullptr, *u_slabs = nullptr; size_t u_slabs_bytes = 0;
-    void* u_LiT = nullptr; float* u_ws2 = nullptr; int* u_flag = nullptr;
-    // ... and those of scfgp_loo, allocated by its first call (ensure_loo): targets and residuals of a chunk, one record per block of a
-    // chunk, two staging halves of [mu | std | lev], the running stats ([0..3] sums, [4] max h) and the flags ([0] non-finite, [1] first
-    // block without a Cholesky factor)
-    double *l_y = nullptr, *l_r = nullptr, *l_rec = nullptr, *l_out = nullptr, *l_acc = nullptr; unsigned long long* l_bad = nullptr;
-    // ... and those of scfgp_forget beyond scfgp_condition's, allocated by its first call (ensure_forget): two staging halves of
-    // [mu | std], the stats' terms of a chunk (3 x PRED_ROWS) and the scalars ([0..2] running sums, [3] r^T r, [4] joint, [5] min M_ii^2)
-    // In fp32 contexts its first pass runs in fp64 (the fp64 features, C and Gram of precision level 1) on f_w: [Phi | C] (PRED_ROWS x Kp
-    // each) and [Li^T | Li] (Kp x Kp each), all fp64
-    double *f_out = nullptr, *f_w = nullptr;
-    // on-device optimiser + captured training iteration
-    int opt_algo = -1; OptHyper opt_h{}; double *d_opt = nullptr, *d_tctr = nullptr, *d_hist = nullptr; int hist_cap = 0;
-    hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr; int64_t graph_N = -1; bool in_train = false, warm = false;
-    int use_graph = 1;
-    // options
-    int gram_nsplit = 0, gram_taper = 1, xtz_nsplit = 0; int64_t gram_chunk = 4096;
-    RowSplits splits{};
-    // Precision escalation (fp32 mode; profiles/r03_c3_owner.md).  The fp32 Gram products carry a relative error
-    // of ~6e-8 that reaches alpha / Li (pass 1) and the gradient (pass 2's V^T diag(q) V) multiplied by the condition of A,
-    // so the K x K stage's free condition estimate decides how the two TN products are formed:
-    //   level 0  both in fp32 MFMA (fp64 across 4096-row chunks)
-    //   level 1  pass 1: G = Phi^T Phi and Phi^T y by the fp64 kernels from fp64 features (alpha, Li, cost, mu*, sigma* then
-    //            equal fp64 mode's to ~1e-8; alpha and Li bit for bit)
-    //   level 2  also pass 2 in its factor form (C = Phi Li^T, v = rowsum(C^2), B W B = Li^T (C^T diag(q) C) Li, V = C Li):
-    //            rounding errors amplified by sqrt(cond) instead of cond (gradient blocks)
-    // option gram64: 0 never, 1 always level 1, 2 auto (default), 3 always level 2.  Auto is sticky: when the estimate of a
-    // finished evaluation asks for a higher level that evaluation is repeated (scfgp_finish returns SCFGP_REDO; scfgp_eval
-    // does so itself) and the following ones start at that level; the level drops when the estimate falls below a quarter
-    // of the threshold.  Inside one scfgp_train call the level is fixed (the iteration may be a captured graph).
-    int gram64 = 2, esc_level = 0, esc_denied = 0; double esc_thr = SCFGP_COND_THRESHOLD, escw_thr = SCFGP_COND_THRESHOLD_W; bool last_used64 = false;
-    int last_level = 0; bool cond_valid = false;               // cond_valid: cond[] describes the current parameters and rows
-    double cond[3] = {0, 0, 0};                                         // min L_ii^2, max L_ii^2, max_j (A^-1)_jj of the last factorisation
-    void* d_Phi64 = nullptr; int64_t phi64_cap = 0; RowSplits splits64{};
-    // factor form of pass 2 (C = Phi Li^T, V = C Li: SweepKernels::apply_c): -1 auto (precision level 2), 0 never, 1 always
-    int factor_form = -1; bool last_cform = false; void* d_C = nullptr; int64_t c_cap = 0;
-    bool want_cform() const { return factor_form == 1 || (factor_form < 0 && level() >= 2); }
-    int level() const { return dtype != SCFGP_F32 || gram64 == 0 ? 0 : (gram64 == 1 ? 1 : (gram64 == 3 ? 2 : esc_level)); }
-    bool use64() const { return level() >= 1; }
-    double cond_est() const { return cond[1] * cond[2]; }
-    // predicted relative error of alpha / Li behind an fp32 Gram: SCFGP_ERR_PER_COND x estimate.  The estimate is a lower bound
-    // of cond_2(A) whose tightness varies (cond_2 / estimate: 30 .. 330 over the measured cases), so the prediction is an order
-    // of magnitude: measured error / prediction lies in 0.2 .. 7 (profiles/r03_c3_owner.md)
-    double alpha_err_fp32() const { return SCFGP_ERR_PER_COND * cond_est(); }
-    int want_level(double est, double slack) const { return est > escw_thr * slack ? 2 : (est > esc_thr * slack ? 1 : 0); }
-    // profiling
-    bool roctx_on = false;
-    bool prof = false; std::vector<ProfRec> recs; std::vector<hipEvent_t> pool; size_t pool_used = 0;
-    std::string err;
-
-    double* beta() { return d_vecs; }
-    double* alpha() { return d_vecs + g.Kp; }
-    // the apply products by LDS-DMA (apply.hip: apply_dma_kernel).  Auto: whenever the column plan has 128-wide tiles (K > 256)
-    // and there are >= 16384 rows -- measured at K = 544 and 992, 16384 .. 100000 rows, both dtypes: 128-wide LDS-DMA tiles are
-    // 4-13 % ahead of the loader-staged ones per product, 256-wide ones behind at these sizes (profiles/r04_tuning.md); fp32
-    // 256-wide tiles from K >= 1024 and 65536 rows (equal to 128-wide at H since both are pipelined, 2/3 of the fabric traffic).
-    // Below that the loader-staged tiles, whose single 64-wide launch per product matters more there
-    int dma() const {
-        const int auto_dma = g.K > 256 && g.Np >= 16384 ? (dtype == SCFGP_F32 && g.K >= 1024 && g.Np >= 65536 ? 2 : 1) : 0;
-        return apply_dma < 0 ? auto_dma : apply_dma;
-    }
-    double* u() { return d_vecs + 2 * g.Kp; }
-    double* ut() { return d_vecs + 3 * g.Kp; }
-    double* alpha_pred() { return d_vecs + 4 * g.Kp; }
-    size_t tsize() const { return dtype == SCFGP_F32 ? 4 : 8; }
-    KStage kstage() {
-        KStage k; k.K = g.K; k.Kp = g.Kp; k.A = d_x1; k.Li = d_Li; k.B = d_B; k.T1 = d_T1; k.T2 = d_T2;
-        k.g = d_x1 + (int64_t)g.Kp * g.Kp; k.beta = beta(); k.alpha = alpha(); k.h = d_x2 + (int64_t)g.Kp * g.Kp;
-        k.u = u(); k.ut = ut(); k.scalars = d_scalars; k.flag = d_flag;
-        return k;
-    }
-};
-
-struct ProfScope {
-    scfgp_ctx* c; size_t idx = (size_t)-1; bool ranged = false;
-    ProfScope(scfgp_ctx* c_, const char* name) : c(c_) {
-        if (g_scfgp_capturing) return;
-        if (c->roctx_on && roctx().push) { roctx().push(name); ranged = true; }
-        if (!c->prof) return;
-        auto get = [&]() {
-            if (c->pool_used == c->pool.size()) { hipEvent_t e; hipEventCreate(&e); c->pool.push_back(e); }
-            return c->pool[c->pool_used++];
-        };
-        ProfRec r; r.name = name; r.e0 = get(); r.e1 = get();
-        hipEventRecord(r.e0, c->st);
-        c->recs.push_back(r); idx = c->recs.size() - 1;
-    }
-    ~ProfScope() {
-        if (idx != (size_t)-1) hipEventRecord(c->recs[idx].e1, c->st);
-        if (ranged) roctx().pop();
-    }
-};
-
-template <typename P> static int dmalloc(scfgp_ctx* c, P** p, size_t bytes) {
-    HIPCHK(c, hipMalloc((void**)p, bytes ? bytes : 16));
-    return SCFGP_OK;
-}
-template <typename P> static void dfree(P*& p) { if (p) { hipFree((void*)p); p = nullptr; } }
-// call-scoped device buffer: released on every return path
-struct DevTmp {
-    double* p = nullptr;
-    ~DevTmp() { if (p) hipFree(p); }
-    operator double*() const { return p; }
-};
 
 // Row splits of the X~^T Zbar grid (few output tiles, equally long workgroups, two per CU): ONE round of the 512 resident
 // workgroups.  The former "about 1152 workgroups" were 2.25 rounds at the headline shape (9 tiles x 128 splits) -- a third
@@ -548,9 +289,6 @@ static void unpack_exchange(scfgp_ctx* c, const double* xp, double* x) {
     hipMemcpyAsync(x + (int64_t)g.Kp * g.Kp, xp + c->n_pk, sizeof(double) * (g.Kp + 8), hipMemcpyDeviceToDevice, c->st);
 }
 
-// typed operands of the first pass of scfgp_condition / scfgp_forget (Impl::update_chunk): Phi and C of a chunk (PRED_ROWS x Kp, padding
-// columns zero), the factor's transpose and the factor (Kp x Kp)
-struct UpdateOperands { void *Phi, *C, *LiT, *Li; };
 template <typename T> struct Impl {
     typedef SweepKernels<T> SK;
     // out = [packed lower tiles of M^T diag(w) M | M^T side (Kp)],  M = Phi (pass 1) or V = Phi B (pass 2)
@@ -711,238 +449,9 @@ template <typename T> struct Impl {
         HIPCHK(c, hipGetLastError());
         return SCFGP_OK;
     }
-    // ---- chunk bodies of the posterior entry points (the pipeline that feeds them is described at RowFeed below) ----
-    // typed operands arrive as void*: both arms of DISPATCH get the same arguments
-    // Phi of the chunk's packed rows (p_Xt -> p_Phi)
-    static void features(scfgp_ctx* c, const Geom& g) {
-        SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)c->p_Phi, c->st);
-    }
-    // C = Phi Li^T by pass 2's level-2 product (loader-staged tiles); its by-products land in the chunk's partials: vpart (slices of
-    // rowsum(C^2)) and mupart (slices of Phi avec)
-    static void factor_c(scfgp_ctx* c, const Geom& g, const T* LiT, const double* avec, T* C) {
-        SK::apply_c(g, (const T*)c->p_Phi, LiT, (const T*)c->p_Li, C, c->p_vpart, avec, avec, c->p_mupart, c->st, 0);
-    }
-    // typed copies of a padded fp64 factor: its transpose into LiT and / or the factor itself into Li (either may be NULL)
-    static void type_factor(scfgp_ctx* c, const double* L64, void* LiT, void* Li) {
-        if (LiT) SK::convert_transposed(L64, (T*)LiT, c->g.K, c->g.Kp, c->st);
-        if (Li) SK::convert(L64, (T*)Li, c->g.K, c->g.Kp, c->st);
-    }
-    static int predict_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, double* mu, double* sd) {
-        features(c, g);
-        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
-        SK::rowpredict(g, c->p_mupart, c->p_vpart, c->d_sc, mu, sd, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // FT = F_all^T in the context's type, the operand of predict_grad_chunk (once per call)
-    static void grad_operand(scfgp_ctx* c) { predgrad_operand(c->g, c->d_Fall, (T*)c->p_FT, c->st); }
-    // after predict_chunk: d mu / d x~ and (dstd != NULL) d sigma / d x~ of the chunk's rows (predgrad.hip).  V* = Phi* B in the factor
-    // form C = Phi* Li^T, V = C Li: its rounding errors grow with sqrt(cond(A)) where those of V = Phi* B formed directly grow with
-    // cond(A).  factor_c's by-products land in the chunk's partials, which rowpredict has consumed.
-    static int predict_grad_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const double* sd, double* dmu, double* dstd) {
-        if (dstd) {
-            factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
-            SK::apply_vc(g, (const T*)c->p_C, (const T*)c->p_Li, (const T*)LiT, (T*)c->p_V, c->st, 0);
-        }
-        predgrad<T>(g, (const T*)c->p_Phi, (const T*)c->p_V, c->alpha_pred(), (const T*)c->p_FT, sd, c->d_sc, dmu, dstd, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_predict_cov, scfgp_select: C = Phi* Li^T of the chunk's rows (the by-products are ignored)
-    static int cov_factor_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, void* C) {
-        features(c, g);
-        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)C);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    static void cov_panel(scfgp_ctx* c, const void* Ca, const void* Cb, int64_t nrows, int64_t Tb, int64_t row_base, int noise, double* out) {
-        predcov<T>(c->g, (const T*)Ca, (const T*)Cb, nrows, Tb, row_base, noise, c->d_sc, out, c->st);
-    }
-    static void pick_init(scfgp_ctx* c, const SelectBufs& b, const void* C) { select_init<T>(b, (const T*)C, c->st); }
-    static void pick(scfgp_ctx* c, const SelectBufs& b, const void* C, int j) { select_step<T>(b, (const T*)C, j, c->d_sc, c->st); }
-    // scfgp_select_iv: packed lower tiles of C^T diag(w) C of a chunk (w == NULL: C^T C) into `out`, by the Gram tiles update_chunk
-    // uses, with the update's slabs (fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs: never the fp16 split)
-    static int iv_gram_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const void* C, const double* w, double* out) {
-        const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
-        double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
-        SK::gram(g, (const T*)C, w, nullptr, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
-        reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    static void iv_init(scfgp_ctx* c, const SelectBufs& b, const SelectIvBufs& iv, const void* C, void* Qt) {
-        SK::convert(iv.Q, (T*)Qt, c->g.K, c->g.Kp, c->st);
-        select_iv_init<T>(b, iv, (const T*)C, (const T*)Qt, c->g.K, c->d_sc, c->st);
-    }
-    static void iv_pick(scfgp_ctx* c, const SelectBufs& b, const SelectIvBufs& iv, const void* C, int j) {
-        select_iv_step<T>(b, iv, (const T*)C, j, c->d_sc, c->st);
-    }
-    // workgroups per row split of the Gram launch on the context's geometry (update_splits)
-    static int gram_jobs(const scfgp_ctx* c) { return SK::gram_jobs(c->g); }
-    // scfgp_condition, scfgp_forget: C = Phi_n Li^T with the update's own factor and alpha (o.LiT / o.Li, u_vec), the residual
-    // r = y - Phi_n alpha, then [packed lower tiles of C^T C | C^T r] of the chunk into `out` by the evaluation's Gram tiles on the
-    // chunk's geometry with the update's own slabs: fp64 MFMA, or exact fp32 MFMA flushed into the fp64 slabs every gram_chunk rows
-    // (never the fp16 split: an f16x3 context runs fp32 mode's kernels here).  The typed operands come with the call (UpdateOperands):
-    // scfgp_forget runs the fp64 arm on buffers of its own in an fp32 context.
-    // have_rows: o.Phi and u_y already hold the chunk's rows and targets (scfgp_condition_grad: gradobs_chunk)
-    static int update_chunk(scfgp_ctx* c, const Geom& g, const RowSplits& rs, const UpdateOperands& o, double* out, bool have_rows = false) {
-        if (!have_rows) SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.Phi, c->st);
-        SK::apply_c(g, (const T*)o.Phi, (const T*)o.LiT, (const T*)o.Li, (T*)o.C, c->p_vpart, c->u_vec, c->u_vec, c->p_mupart, c->st, 0);
-        SK::rowresidual(g, c->p_mupart, c->u_y, c->u_r, c->st);
-        const int nts = g.Kp / g.tile, ntiles = nts * (nts + 1) / 2;
-        double* sidepart = c->u_slabs + (size_t)rs.nsplit * ntiles * g.tile * g.tile;
-        SK::gram(g, (const T*)o.C, nullptr, c->u_r, rs, sizeof(T) == 4 ? c->gram_chunk : 0, c->u_slabs, sidepart, c->u_flag + 8, c->u_ws2, c->st);
-        reduce_tri_tiles(c->u_slabs, rs.nsplit, nts, g.tile, out, c->st);
-        reduce_side(sidepart, rs.nsplit, g.Kp, g.gfull * g.tile + g.gstrip * 64, out + c->n_pk, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_condition_grad (condgrad.hip): Phi of the chunk's g.N packed points into o.C (which the product that follows overwrites), then
-    // their gr.N observation rows into o.Phi and the rows' targets into u_y, where update_chunk (have_rows) finds them
-    static int gradobs_chunk(scfgp_ctx* c, const Geom& g, const Geom& gr, const UpdateOperands& o, const GradObs& a) {
-        { ProfScope ps(c, "gradobs_featuremap");
-          SK::featuremap(g, c->p_Xt, Projection{c->d_Fall, c->d_Lall, c->d_Rall, c->p_Tt}, c->d_sc, (T*)o.C, c->st); }
-        { ProfScope ps(c, "gradobs_rows"); gradobs_rows<T>(gr, g, (const T*)o.C, c->d_Fall, a, (T*)o.Phi, c->u_y, c->st); }
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_loo: C = Phi_I Li^T and r = y - Phi_I alpha of the chunk's rows, then the block kernel and the ordered sum of its records
-    // (loo.hip)
-    static int loo_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int block, int64_t blk0, double* mu, double* sd, double* lev) {
-        features(c, g);
-        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
-        SK::rowresidual(g, c->p_mupart, c->l_y, c->l_r, c->st);
-        loo_blocks<T>(g, (const T*)c->p_C, c->l_r, c->l_y, block, blk0, c->d_sc, mu, sd, lev, c->l_rec, c->l_acc, c->l_bad, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_predict_gradcov (gradcov.hip).  Qt: the typed direction basis, once per call
-    static void gradcov_basis(scfgp_ctx* c, void* Qt) { gradcov_operand<T>(c->g, c->d_params, c->d_Fall, (T*)Qt, c->st); }
-    // a chunk of g.N points: dmu by predict_grad's own kernel (mean only) and chain rule, so that it has scfgp_predict_grad's bits; then
-    // the g.N q derivative rows Psi into p_V, C' = Psi Li^T into p_C (its by-products land in the chunk's partials and are ignored), the
-    // block kernel and, rec != NULL, the ordered sum of its records.  x: the chunk's raw rows (xmode != 0: gfac <- the scaler's factors)
-    static int gradcov_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const void* Qt, const double* x, int xmode, double* gfac,
-                             const double* wgt, double* dmu, double* dvar, double* dcov, double* rec, double* acc) {
-        const int q = std::min(g.D, g.S);
-        features(c, g);
-        { ProfScope ps(c, "gradcov_dmu");
-          predgrad<T>(g, (const T*)c->p_Phi, (const T*)c->p_V, c->alpha_pred(), (const T*)c->p_FT, nullptr, c->d_sc, dmu, nullptr, c->st);
-          if (xmode) {
-              gradcov_ones(gfac, g.N * g.D, c->st);
-              xgrad_chunk(x, g.N, g.D, xmode, c->d_xscale, dmu, gfac, c->st);
-          } }
-        if (dvar || dcov || rec) {
-            const Geom gr = chunk_geom(g, g.N * q);
-            { ProfScope ps(c, "gradfeat"); gradfeat<T>(gr, g, (const T*)c->p_Phi, (const T*)Qt, (T*)c->p_V, c->st); }
-            { ProfScope ps(c, "gradcov_apply_c");
-              SK::apply_c(gr, (const T*)c->p_V, (const T*)LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(),
-                          c->p_mupart, c->st, 0); }
-            { ProfScope ps(c, "gradcov_block");
-              gradcov_blocks<T>(gr, g, (const T*)c->p_C, c->d_params, c->d_sc, xmode ? gfac : nullptr, dmu, wgt, dvar, dcov, rec, c->st); }
-            if (rec) { ProfScope ps(c, "gradcov_reduce"); gradcov_reduce(rec, g.N, g.D, acc, c->st); }
-        }
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_predict_pd (pd.hip).  The sums of a chunk's packed rows for ng dimensions, added into the call's running sums
-    static int pd_sums_chunk(scfgp_ctx* c, const Geom& g, const double* wgt, const int* dims, int ng, double* rec, double* acc) {
-        ProfScope ps(c, "pd_sums");
-        pd_sums<T>(g, c->p_Xt, c->d_Fall, c->d_sc, wgt, dims, ng, rec, acc, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // the curves of ng dimensions: their stacked mean rows Phibar into p_Phi (gr: the geometry in those rows), Cbar = Phibar Li^T into p_C;
-    // pd = the sum of mupart in rowpredict's order, sd = sqrt(kappa sum vpart) by kg_sigma's arithmetic.  pd, scratch, sd: gr.Np each
-    static int pd_curves(scfgp_ctx* c, const Geom& gr, const void* LiT, const double* acc, double W, const int* dims, const double* grid, int ng,
-                         int G, double* pd, double* scratch, double* sd) {
-        ProfScope ps(c, "pd_curves");
-        pd_mean_rows<T>(gr, c->g, acc, W, c->d_Fall, dims, grid, ng, G, (T*)c->p_Phi, c->st);
-        SK::apply_c(gr, (const T*)c->p_Phi, (const T*)LiT, (const T*)c->p_Li, (T*)c->p_C, c->p_vpart, c->alpha_pred(), c->alpha_pred(),
-                    c->p_mupart, c->st, 0);
-        SK::rowpredict(gr, c->p_mupart, c->p_vpart, c->d_sc, pd, scratch, c->st);
-        kg_sigma(gr, ApplyKernels<T>::partials(gr), c->p_vpart, c->d_sc, 0, sd, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // the covariance of dimension number a of the last pd_curves: predcov on its own rows of p_C twice, so the result is symmetric bit for bit
-    static int pd_cov_dim(scfgp_ctx* c, int a, int G, double* out) {
-        const T* Ca = (const T*)c->p_C + (int64_t)a * pd_grid_rows(G) * c->g.Kp;
-        predcov<T>(c->g, Ca, Ca, G, G, 0, 0, c->d_sc, out, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // the ICE block of dimension d over the chunk's packed rows: column d of p_Xt is cleared for the feature map and put back
-    static int pd_ice_chunk(scfgp_ctx* c, const Geom& g, int d, const double* grid_d, int G, void* R, double* keep, double* out) {
-        pd_column(g, c->p_Xt, d, 1, keep, c->st);
-        { ProfScope ps(c, "pd_ice_featuremap"); features(c, g); }
-        { ProfScope ps(c, "pd_ice_product");
-          pd_ice_weights<T>(c->g, c->alpha_pred(), c->d_Fall, d, grid_d, G, (T*)R, c->st);
-          sample_product<T>(g, (const T*)c->p_Phi, (const T*)R, G, 0, 0, 0, -1, c->d_yscale, c->d_sc, out, c->st); }
-        pd_column(g, c->p_Xt, d, 0, keep, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_sample: the weights of the sample functions (sample.hip), then per chunk out (N x nsamp) = Phi* W and the epilogue
-    static void weights(scfgp_ctx* c, const double* Li, const double* alpha, int nsamp, uint64_t seed, double* Z, double* W, void* Wt) {
-        sample_weights<T>(c->g, Li, alpha, c->d_sc, nsamp, seed, Z, W, (T*)Wt, c->st);
-    }
-    static int sample_chunk(scfgp_ctx* c, const Geom& g, const void* Wt, int nsamp, int64_t t0, uint64_t seed, int noise, int ymode,
-                            double* out) {
-        features(c, g);
-        sample_product<T>(g, (const T*)c->p_Phi, (const T*)Wt, nsamp, t0, seed, noise, ymode, c->d_yscale, c->d_sc, out, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_sample_argmax: the same product, reduced per sample column in its epilogue and merged into the call's running best
-    static int sample_argmax_chunk(scfgp_ctx* c, const Geom& g, const void* Wt, int nsamp, const double* w, int minimize, int64_t t0,
-                                   const SampleArgmaxBufs& b) {
-        features(c, g);
-        sample_argmax_product<T>(g, (const T*)c->p_Phi, (const T*)Wt, nsamp, w, minimize, t0, t0 == 0, b, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_acquire: predict_chunk with acquire.hip's row kernels in rowpredict's place (the same partials in the same order, so mu has
-    // scfgp_predict's bits), then the chunk's best eligible row into the call's running best
-    static int acquire_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, const AcquireSpec& a, const double* w, int64_t t0, const AcquireBufs& b) {
-        features(c, g);
-        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
-        acquire_rows(g, ApplyKernels<T>::partials(g), c->p_mupart, c->p_vpart, c->d_sc, a, b, c->st);
-        acquire_argmax(g, w, t0, t0 == 0, b, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_acquire_kg, the reference job: predict_chunk's product on the R reference rows, whose partials give u_r with scfgp_predict's
-    // bits (kg.hip: d_r and the per-call constants of the nodes), then Cb = Phi Li^T into p_V, where it stays for the call
-    static int kg_ref_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int minimize, const double* z, int J, const KgBufs& b, int* flag) {
-        features(c, g);
-        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
-        kg_reference(ApplyKernels<T>::partials(g), c->p_mupart, g.Np, g.N, minimize, z, J, b.d, b.zf, flag, c->st);
-        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_V);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // a chunk of candidates: sigma from predict_chunk's product (scfgp_acquire's bits), Ca = Phi Li^T into p_C, then the fused product
-    // with the node reduction and the two sums (kg.hip)
-    static int kg_chunk(scfgp_ctx* c, const Geom& g, const void* LiT, int64_t R, int J, int noise, const KgBufs& b) {
-        features(c, g);
-        SK::apply_predict(g, (const T*)c->p_Phi, (const T*)LiT, c->p_vpart, c->alpha_pred(), c->p_mupart, c->st);
-        kg_sigma(g, ApplyKernels<T>::partials(g), c->p_vpart, c->d_sc, noise, b.sd, c->st);
-        factor_c(c, g, (const T*)LiT, c->alpha_pred(), (T*)c->p_C);
-        kg_nodes<T>(g, (const T*)c->p_C, (const T*)c->p_V, R, J, b, c->d_sc, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
-    // scfgp_sample_grad: f and d f / d x~ of the chunk's rows, each under its own sample's weights (samplegrad.hip; FT: grad_operand)
-    static int sample_grad_chunk(scfgp_ctx* c, const Geom& g, const double* WT, const double* sidx, int64_t t0, int nsamp, double* val,
-                                 double* grad) {
-        features(c, g);
-        samplegrad<T>(g, (const T*)c->p_Phi, WT, sidx, t0, nsamp, (const T*)c->p_FT, val, grad, c->st);
-        HIPCHK(c, hipGetLastError());
-        return SCFGP_OK;
-    }
 };
 
-#define DISPATCH(c, fn, ...) ((c)->dtype == SCFGP_F32 ? Impl<float>::fn(__VA_ARGS__) : Impl<double>::fn(__VA_ARGS__))
+#define DISPATCH(c, fn, ...) DISPATCH_TO(Impl, c, fn, __VA_ARGS__)
 
 static int ready(scfgp_ctx* c) {
     if (!c) return SCFGP_EARG;
@@ -1281,1984 +790,6 @@ extern "C" int scfgp_eval_rows(scfgp_ctx* c, const int64_t* idx, int64_t n, int 
     HIPCHK(c, hipMemcpyAsync(c->d_idx, idx, sizeof(int64_t) * n, hipMemcpyHostToDevice, c->st));
     if (int rc = load_working_set(c, c->d_idx, n, n)) return rc;       // per-batch N, as SCFGP.py:126,128
     return run_eval(c, want_grad, cost, grad, alpha, Li, true);
-}
-
-// the chunk buffers of the predict family and of scfgp_sample (first call only); the padding columns of Phi* stay zero
-static int ensure_pred_chunk(scfgp_ctx* c) {
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
-    const size_t ts = c->tsize();
-    int rc;
-    if (!c->p_Xt) {
-        if ((rc = dmalloc(c, &c->p_Xt, sizeof(double) * PRED_ROWS * g0.Dp))) return rc;
-        if (g0.lowrank && (rc = dmalloc(c, &c->p_Tt, sizeof(double) * PRED_ROWS * g0.Sp))) return rc;
-        if ((rc = dmalloc(c, &c->p_vpart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
-        if ((rc = dmalloc(c, &c->p_mupart, sizeof(double) * PRED_ROWS * (Kp / 64)))) return rc;
-        if ((rc = dmalloc(c, &c->p_Phi, ts * PRED_ROWS * Kp))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->p_Phi, 0, ts * PRED_ROWS * Kp, c->st));
-    }
-    return SCFGP_OK;
-}
-
-// the factor-form buffers that the std gradient of scfgp_predict_grad and scfgp_predict_cov share (first call of either only): the
-// typed Li and two PRED_ROWS x Kp typed arrays (C = Phi* Li^T and V = C Li there; Ca and Cb here), padding columns zero
-static int ensure_pred_factor(scfgp_ctx* c) {
-    if (c->p_V) return SCFGP_OK;
-    const int64_t Kp = c->g.Kp;
-    const size_t ts = c->tsize();
-    int rc;
-    if ((rc = dmalloc(c, &c->p_Li, ts * Kp * Kp))) return rc;
-    if ((rc = dmalloc(c, &c->p_C, ts * PRED_ROWS * Kp))) return rc;
-    if ((rc = dmalloc(c, &c->p_V, ts * PRED_ROWS * Kp))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->p_C, 0, ts * PRED_ROWS * Kp, c->st));
-    HIPCHK(c, hipMemsetAsync(c->p_V, 0, ts * PRED_ROWS * Kp, c->st));
-    return SCFGP_OK;
-}
-
-// buffers of scfgp_predict_grad beside predict's own (first call only; the std gradient's on its first call)
-static int ensure_pred_grad(scfgp_ctx* c, bool want_std) {
-    const Geom& g = c->g;
-    const size_t ts = c->tsize();
-    int rc;
-    if (!c->p_FT && (rc = dmalloc(c, &c->p_FT, ts * round_up(g.J, 16) * predgrad_ft_cols(g.D)))) return rc;
-    if (want_std && (rc = ensure_pred_factor(c))) return rc;
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// the chunk pipeline of the posterior entry points: the predict family, scfgp_sample, scfgp_sample_argmax, scfgp_predict_cov,
-// scfgp_condition, scfgp_condition_grad, scfgp_forget, scfgp_loo, scfgp_predict_gradcov, scfgp_predict_pd, scfgp_select, scfgp_select_qei and scfgp_acquire_kg
-// ----------------------------------------------------------------------------------------------
-// Rows come from pageable host memory in jobs of at most PRED_ROWS rows.  Job i + 1 is uploaded on the copy stream (the call blocks
-// the host while it stages) after the kernels of job i have been enqueued on the context's stream, so the copy runs beside them.  A
-// RowFeed owns the two halves that the uploads alternate between and the events that order a half between the streams: up (the rows
-// are there: st waits before pack_data reads them) and fre (they have been read: the copy stream waits before job i + 2 overwrites
-// them).  The caller places release(): right after pack_data, or after the last kernel that still reads the raw rows.
-// Results that do not stay on the device leave through two staging slots of the caller, ordered by an OutRing: done (slot k is
-// computed: the copy stream waits before it copies the slot out) and copied (st waits before slot k + 2 overwrites it).  Each loop
-// enqueues in the order "compute slot k, upload job k + 1, drain slot k - 1" and drains the last slot behind the loop: the host's
-// blocking copies in both directions fall under the next chunk's kernels, and device memory does not grow with the row count.
-// The waits for reuse run from the third job or slot on.
-//
-// Around it the entry points share (the parts that need no HIP are in api_host.h; each is described where it is defined): RowJobs, the
-// job schedule that RowFeed::upload(job, jobs) stages from (`base` shifts the feed's job number behind an earlier schedule; the loops stay
-// in the entry points, since where release, ring.acquire, ring.computed and the downloads fall differs); scan_weights, one pass over a
-// weight vector (all callers report the first negative row even behind a non-finite one, scfgp_predict_gradcov the first entry that is
-// either); Fail and need_model, the one way to refuse a call; load_factor's short form; BestBlock, the running best of a pool sweep.
-// Not through these helpers, and why:
-//   scfgp_loo with resident rows      the rows are read where they lie on the device: its loop skips the uploads and the feed
-//   scfgp_select_iv                   two schedules in a row (the reference chunks, then the pool): a one-line lambda picks a job's
-//   scfgp_condition, _condition_grad, scfgp_forget    load_factor's long form (update_gather): other buffers, and the finite check
-//   scfgp_predict_grad, _raw, _y      scaler checks under their own names and texts, apart from predict_impl's parameter check
-//   scfgp_select, _select_iv, _qei    bare int flags, fetched twice under two different synchronisations: a helper would not be shorter
-// scfgp_forget's second phase and scfgp_predict_pd's second pass use RowJobs through `base`: their feed goes on counting.
-template <int N> struct Events {                                  // call-scoped events: released on every return path
-    hipEvent_t e[N] = {};
-    int create(scfgp_ctx* c) {
-        for (hipEvent_t& x : e) HIPCHK(c, hipEventCreateWithFlags(&x, hipEventDisableTiming));
-        return SCFGP_OK;
-    }
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-struct RowFeed {
-    scfgp_ctx* c = nullptr;
-    DevTmp raw;                                                   // two halves of `stride` doubles: rows (n x D), targets at PRED_ROWS * D
-    int64_t stride = 0;
-    Events<4> ev;                                                 // up[2] | fre[2]
-    // also_holds: what else the buffer is used for (the host layout of Li, before the first job); stride 0: no rows will be fed
-    int open(scfgp_ctx* c_, int64_t stride_, int64_t also_holds = 0) {
-        c = c_; stride = stride_;
-        if (int rc = dmalloc(c, &raw.p, sizeof(double) * std::max<int64_t>(also_holds, 2 * stride))) return rc;
-        return ev.create(c);
-    }
-    int upload(int64_t job, const double* X, const double* y, int64_t rows) {
-        const int h = (int)(job & 1);
-        if (job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[2 + h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * stride, X, sizeof(double) * rows * c->g.D, hipMemcpyHostToDevice, c->copy_st));
-        if (y) HIPCHK(c, hipMemcpyAsync(raw + h * stride + PRED_ROWS * c->g.D, y, sizeof(double) * rows, hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
-        return SCFGP_OK;
-    }
-    // a job of a schedule, as the feed's job base + job.  A schedule with further target arrays (RowJobs::y1, y2: scfgp_condition_grad)
-    // stages every segment at its place in the block behind the rows; its stride is PRED_ROWS * D + CH * target_width() doubles
-    int upload(int64_t job, const RowJobs& j, int64_t base = 0) {
-        if (!j.y1 && !j.y2) return upload(base + job, j.x(job, c->g.D), j.targets(job), j.rows(job));
-        const int h = (int)((base + job) & 1);
-        const int64_t rows = j.rows(job);
-        if (base + job >= 2) HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[2 + h], 0));
-        HIPCHK(c, hipMemcpyAsync(raw + h * stride, j.x(job, c->g.D), sizeof(double) * rows * c->g.D, hipMemcpyHostToDevice, c->copy_st));
-        for (int k = 0; k < RowJobs::SEGS; ++k)
-            if (const double* src = j.seg(job, k))
-                HIPCHK(c, hipMemcpyAsync(raw + h * stride + PRED_ROWS * c->g.D + j.seg_off(k), src, sizeof(double) * rows * j.seg_width(k),
-                                         hipMemcpyHostToDevice, c->copy_st));
-        HIPCHK(c, hipEventRecord(ev.e[h], c->copy_st));
-        return SCFGP_OK;
-    }
-    int acquire(int64_t job, const double** x, const double** y = nullptr) {
-        const int h = (int)(job & 1);
-        HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[h], 0));
-        *x = raw + h * stride;
-        if (y) *y = raw + h * stride + PRED_ROWS * c->g.D;
-        return SCFGP_OK;
-    }
-    int release(int64_t job) {
-        HIPCHK(c, hipEventRecord(ev.e[2 + (int)(job & 1)], c->st));
-        return SCFGP_OK;
-    }
-};
-struct OutRing {
-    scfgp_ctx* c = nullptr;
-    Events<4> ev;                                                 // done[2] | copied[2]
-    int open(scfgp_ctx* c_) { c = c_; return ev.create(c); }
-    int acquire(int64_t k) {
-        if (k >= 2) HIPCHK(c, hipStreamWaitEvent(c->st, ev.e[2 + (int)(k & 1)], 0));
-        return SCFGP_OK;
-    }
-    int computed(int64_t k) {
-        HIPCHK(c, hipEventRecord(ev.e[(int)(k & 1)], c->st));
-        return SCFGP_OK;
-    }
-    // copies: the caller's hipMemcpyAsync calls on the copy stream (pageable: the host waits in them while the next slot computes)
-    template <typename F> int drain(int64_t k, F copies) {
-        const int h = (int)(k & 1);
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, ev.e[h], 0));
-        if (int rc = copies()) return rc;
-        HIPCHK(c, hipEventRecord(ev.e[2 + h], c->copy_st));
-        return SCFGP_OK;
-    }
-};
-static Geom chunk_geom(const Geom& g0, int64_t rows) {
-    Geom g = g0;
-    g.N = rows; g.Np = round_up(rows, 256);
-    return g;
-}
-// pack_data of one chunk of a posterior call into p_Xt; the chunk's padded row count is kept for debug_read("pXt")
-static void pack_chunk(scfgp_ctx* c, const Geom& g, const double* Xraw, const double* yraw, const int64_t* idx, double* y,
-                       int mode = 0, const double* sp = nullptr) {
-    c->p_rows = g.Np;
-    pack_data(g, Xraw, yraw, idx, c->p_Xt, y, c->st, mode, sp);
-}
-// The factor pass.  Li (K x K, host) -> raw -> L64 (Kp x Kp fp64) by `pad` (pad_square: identity padding; update_load_factor: the
-// lower triangle only, so that entries above the diagonal are never read) -> the typed Li^T into LiT and, Li_typed != NULL, the typed
-// Li.  alpha != NULL: zero-padded into avec.  finite != NULL: scfgp_condition's checks of what was loaded.  raw may be reused once the
-// stream has been synchronised.
-typedef void (*PadFn)(const double*, int, int, double*, hipStream_t);
-static int load_factor(scfgp_ctx* c, double* raw, const double* Li, PadFn pad, double* L64, void* LiT, void* Li_typed,
-                       const double* alpha = nullptr, double* avec = nullptr, int* finite = nullptr) {
-    const Geom& g = c->g;
-    HIPCHK(c, hipMemcpyAsync(raw, Li, sizeof(double) * g.K * g.K, hipMemcpyHostToDevice, c->st));
-    pad(raw, g.K, g.Kp, L64, c->st);
-    if (alpha) {
-        HIPCHK(c, hipMemsetAsync(avec, 0, sizeof(double) * g.Kp, c->st));
-        HIPCHK(c, hipMemcpyAsync(avec, alpha, sizeof(double) * g.K, hipMemcpyHostToDevice, c->st));
-    }
-    if (finite) {
-        update_check_finite(L64, (int64_t)g.Kp * g.Kp, finite, c->st);
-        update_check_finite(avec, g.Kp, finite, c->st);
-    }
-    DISPATCH(c, type_factor, c, L64, LiT, Li_typed);
-    return SCFGP_OK;
-}
-// The usual operands: L64 is d_T1, the typed Li^T goes to d_AbarT (scratch outside adjoint..pass3) and is handed back in *LiT, the
-// typed Li to p_Li (typed_Li), alpha to alpha_pred().  The caller synchronises the stream before the feed's buffer is reused.
-static int load_factor(scfgp_ctx* c, RowFeed& feed, const double* Li, PadFn pad, bool typed_Li, const double* alpha, const void** LiT) {
-    *LiT = c->d_AbarT;
-    return load_factor(c, feed.raw, Li, pad, c->d_T1, c->d_AbarT, typed_Li ? c->p_Li : nullptr, alpha, alpha ? c->alpha_pred() : nullptr);
-}
-
-// One way to refuse a call: "<who>: <what>" is the context's error text.
-struct Fail {
-    scfgp_ctx* c; const char* who;
-    int set(const std::string& what, int code) const { c->err = std::string(who) + ": " + what; return code; }
-    int arg(const std::string& what) const { return set(what, SCFGP_EARG); }
-    int nonfinite(const std::string& what) const { return set(what, SCFGP_ENONFINITE); }
-};
-// what a posterior entry point needs of the context before it reads its other arguments' values
-static int need_model(const Fail& f, bool x_scaler, bool y_scaler = false) {
-    if (x_scaler && !f.c->d_xscale) return f.arg("no X scaler set");
-    if (y_scaler && !f.c->d_yscale) return f.arg("no y scaler set");
-    if (!f.c->have_params) return f.arg("parameters not set");
-    return SCFGP_OK;
-}
-
-// The running best of a pool sweep: n (value, row) pairs and one double that holds the call's int flags, behind the workgroups' records
-// of two chunks (values of slot 0, of slot 1, then the rows of each; chunk i writes slot i & 1): 4 * nrec + 2 * n + 1 doubles.
-struct BestBlock {
-    double* rec = nullptr; int64_t n = 0, nrec = 0;
-    static int64_t doubles(int64_t n, int64_t nrec) { return 4 * nrec + 2 * n + 1; }
-    void carve(double* base, int64_t n_, int64_t nrec_) { rec = base; n = n_; nrec = nrec_; }
-    double* v() const { return rec + 4 * nrec; }
-    long long* t() const { return (long long*)(v() + n); }
-    int* flag() const { return (int*)(v() + 2 * n); }
-    double* rec_v(int64_t i) const { return rec + (i & 1) * nrec; }
-    long long* rec_t(int64_t i) const { return (long long*)(rec + (2 + (i & 1)) * nrec); }
-    int clear(scfgp_ctx* c) const { HIPCHK(c, hipMemsetAsync(flag(), 0, sizeof(double), c->st)); return SCFGP_OK; }
-    // host: 2 * n + 1 doubles, [v | t | flags]; both streams have drained on return, so the caller can refuse before it writes an output
-    int fetch(scfgp_ctx* c, double* host) const {
-        HIPCHK(c, hipMemcpyAsync(host, v(), sizeof(double) * (2 * n + 1), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(c, hipStreamSynchronize(c->copy_st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        return SCFGP_OK;
-    }
-    int host_flag(const double* host, int k = 0) const { int f[2]; memcpy(f, host + 2 * n, sizeof(f)); return f[k]; }
-};
-
-// raw_mode: apply the registered X scaler while packing; post: y-scaler backward transform of the outputs on
-// the device and, with targets ys, the six validation metrics; dmu != NULL: also the gradients of mu (and, dstd != NULL, of std) in
-// the inputs, T x D each (scfgp_predict_grad).  mu and sd of all T rows stay on the device until the end.
-static int predict_impl(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
-                        double* mu, double* sd, int raw_mode, int post = 0, const double* ys = nullptr,
-                        double* metrics = nullptr, double* dmu = nullptr, double* dstd = nullptr) {
-    if (!c || !Xs || !alpha || !Li || !mu || !sd || T < 1) { if (c) c->err = "predict: bad arguments"; return SCFGP_EARG; }
-    int rc;
-    if ((rc = need_model({c, "predict"}, false))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    const bool grad = dmu != nullptr;
-    if (grad && (rc = ensure_pred_grad(c, dstd != nullptr))) return rc;
-    RowFeed feed; DevTmp d_out, d_ys, d_part;                     // Li / two chunks of Xs | mu, sd of all T rows | targets, mean, metrics | chunk partials
-    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
-    if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 2 * T))) return rc;
-    double* d_mu = d_out; double* d_sd = d_out + T;
-    // the sweep operand is Li^T itself: sigma* needs rowsum((Phi* Li^T)^2) (SCFGP/SCFGP.py:144), a triangular product
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, false, alpha, &LiT))) return rc;
-    DevTmp d_grad;                                                // dmu | dstd of all T rows (T x D each)
-    if (grad) {
-        if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D * (dstd ? 2 : 1)))) return rc;
-        DISPATCH(c, grad_operand, c);
-        if (dstd) DISPATCH(c, type_factor, c, c->d_T1, nullptr, c->p_Li);      // p_Li exists with the std gradient only
-    }
-    double* d_dmu = d_grad; double* d_dsd = grad && dstd ? d_grad + T * g0.D : nullptr;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    const RowJobs jobs = {Xs, nullptr, T, PRED_ROWS};
-    const int nchunks = (int)jobs.count();
-    if (post && ys) {
-        if ((rc = dmalloc(c, &d_ys.p, sizeof(double) * (T + 8)))) return rc;
-        if ((rc = dmalloc(c, &d_part.p, sizeof(double) * 4 * YPOST_BLOCKS * nchunks))) return rc;
-        HIPCHK(c, hipMemcpyAsync(d_ys, ys, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
-        ypost_mean(d_ys, T, d_ys + T, c->st);
-    }
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = jobs.row0(i);
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double* x;
-        if ((rc = feed.acquire(i, &x))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, raw_mode ? c->xs_mode : 0, c->d_xscale);
-        if (!grad && (rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, predict_chunk, c, g, LiT, d_mu + t0, d_sd + t0))) return rc;
-        if (grad) {
-            // the gradients in x~, then the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is
-            // released after them), the y scaler's at the scaled mu, sigma (before ypost_chunk transforms them in place)
-            double* gm = d_dmu + t0 * g0.D; double* gs = d_dsd ? d_dsd + t0 * g0.D : nullptr;
-            if ((rc = DISPATCH(c, predict_grad_chunk, c, g, LiT, d_sd + t0, gm, gs))) return rc;
-            if (raw_mode && c->xs_mode) xgrad_chunk(x, g.N, g0.D, c->xs_mode, c->d_xscale, gm, gs, c->st);
-            if (post) ygrad_chunk(d_mu + t0, d_sd + t0, g.N, g0.D, c->ys_mode, c->d_yscale, gm, gs, c->st);
-            if ((rc = feed.release(i))) return rc;
-        }
-        if (post)
-            ypost_chunk(d_mu + t0, d_sd + t0, d_ys.p ? d_ys + t0 : nullptr, g.N, c->ys_mode, c->d_yscale, d_ys.p ? d_ys + T : nullptr,
-                        d_part.p ? d_part + 4 * YPOST_BLOCKS * i : nullptr, c->st);
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (grad) HIPCHK(c, hipMemcpyAsync(dmu, d_dmu, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
-    if (grad && dstd) HIPCHK(c, hipMemcpyAsync(dstd, d_dsd, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (post && ys) {
-        ypost_metrics(d_part, YPOST_BLOCKS * nchunks, T, d_ys + T + 1, c->st);
-        HIPCHK(c, hipMemcpyAsync(metrics, d_ys + T + 1, sizeof(double) * 6, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-    }
-    HIPCHK(c, hipGetLastError());
-    return SCFGP_OK;
-}
-
-extern "C" int scfgp_predict(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
-                             double* mu, double* sd) {
-    return predict_impl(c, Xs, T, alpha, Li, mu, sd, 0);
-}
-
-// SCFGP.predict feeds pred_func with X_scaler.forward_transform(Xs) (SCFGP/SCFGP.py:279); for large test
-// sets that element-wise host pass dominates, so the same transform can run inside the packing kernel.
-extern "C" int scfgp_set_x_scaler(scfgp_ctx* c, int mode, const double* mn, const double* mx, const double* boxcox,
-                                  const double* mu, const double* sd) {
-    if (!c || mode < 0 || mode > 5) return SCFGP_EARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int D = c->g.D;
-    std::vector<double> h(5 * D, 0.0);
-    const double* src[5] = {mn, mx, boxcox, mu, sd};
-    for (int k = 0; k < 5; ++k)
-        if (src[k]) std::copy(src[k], src[k] + D, h.begin() + k * D);
-    if (!c->d_xscale) { if (int rc = dmalloc(c, &c->d_xscale, sizeof(double) * 5 * D)) return rc; }
-    HIPCHK(c, hipMemcpy(c->d_xscale, h.data(), sizeof(double) * 5 * D, hipMemcpyHostToDevice));
-    c->xs_mode = mode;
-    return SCFGP_OK;
-}
-extern "C" int scfgp_predict_raw(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
-                                 double* mu, double* sd) {
-    if (c && c->xs_mode && !c->d_xscale) { c->err = "predict_raw: no scaler set"; return SCFGP_EARG; }
-    return predict_impl(c, Xs, T, alpha, Li, mu, sd, 1);
-}
-
-// The rest of SCFGP.predict (SCFGP/SCFGP.py:281-293): y_scaler.backward_transform of mu and of the mu +- std
-// band, std_y = half the transformed band, and with targets the metrics MAE, NMAE, MSE, NMSE, MNLP, SCORE.
-extern "C" int scfgp_set_y_scaler(scfgp_ctx* c, int mode, double mn, double mx, double boxcox, double mu, double sd) {
-    if (!c || mode < 0 || mode > 5) return SCFGP_EARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const double h[5] = {mn, mx, boxcox, mu, sd};
-    if (!c->d_yscale) { if (int rc = dmalloc(c, &c->d_yscale, sizeof(double) * 5)) return rc; }
-    HIPCHK(c, hipMemcpy(c->d_yscale, h, sizeof(h), hipMemcpyHostToDevice));
-    c->ys_mode = mode;
-    return SCFGP_OK;
-}
-extern "C" int scfgp_predict_y(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li,
-                               const double* ys, double* mu_y, double* std_y, double* metrics) {
-    if (c && ((c->xs_mode && !c->d_xscale) || !c->d_yscale)) { c->err = "predict_y: scalers not set"; return SCFGP_EARG; }
-    if (c && ys && !metrics) { c->err = "predict_y: targets given without a metrics buffer"; return SCFGP_EARG; }
-    return predict_impl(c, Xs, T, alpha, Li, mu_y, std_y, 1, 1, ys, metrics);
-}
-
-// Gradients of the predictive mean and std in the inputs (predgrad.hip).  mu, std are those of scfgp_predict (mode 0),
-// scfgp_predict_raw (1) or scfgp_predict_y (2), bit for bit: the same chunks, kernels and order.
-extern "C" int scfgp_predict_grad(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li, int mode,
-                                  double* mu, double* sd, double* dmu, double* dstd) {
-    if (!c) return SCFGP_EARG;
-    if (!Xs || !alpha || !Li || !mu || !sd || !dmu || T < 1 || mode < 0 || mode > 2) { c->err = "predict_grad: bad arguments"; return SCFGP_EARG; }
-    if (mode >= 1 && !c->d_xscale) { c->err = "predict_grad: no X scaler set"; return SCFGP_EARG; }
-    if (mode == 2 && !c->d_yscale) { c->err = "predict_grad: no y scaler set"; return SCFGP_EARG; }
-    return predict_impl(c, Xs, T, alpha, Li, mu, sd, mode >= 1 ? 1 : 0, mode == 2 ? 1 : 0, nullptr, nullptr, dmu, dstd);
-}
-
-// ----------------------------------------------------------------------------------------------
-// posterior sample functions (sample.hip; derivation and random-number contract in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int SAMPLE_MAX = 1024;
-// the weights of nsamp sample functions on the device: W (fp64) and Wt (the context's type), sample_w_rows(K) x sample_w_cols(nsamp)
-struct SampleW { DevTmp z, w, wt; };
-static int sample_weights_dev(scfgp_ctx* c, const double* alpha, const double* Li, int nsamp, uint64_t seed, SampleW& sw) {
-    const Geom& g = c->g;
-    const int64_t n = sample_w_rows(g.K) * sample_w_cols(nsamp);
-    DevTmp dli, dal;
-    int rc;
-    if ((rc = dmalloc(c, &dli.p, sizeof(double) * g.K * g.K))) return rc;
-    if ((rc = dmalloc(c, &dal.p, sizeof(double) * g.K))) return rc;
-    if ((rc = dmalloc(c, &sw.z.p, sizeof(double) * n))) return rc;
-    if ((rc = dmalloc(c, &sw.w.p, sizeof(double) * n))) return rc;
-    if ((rc = dmalloc(c, &sw.wt.p, c->tsize() * n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(dli, Li, sizeof(double) * g.K * g.K, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemcpyAsync(dal, alpha, sizeof(double) * g.K, hipMemcpyHostToDevice, c->st));
-    DISPATCH(c, weights, c, dli.p, dal.p, nsamp, seed, sw.z.p, sw.w.p, sw.wt.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // dli, dal are released on return
-    return SCFGP_OK;
-}
-static int sample_check(scfgp_ctx* c, bool ptrs_ok, int nsamp, const char* who) {
-    if (!ptrs_ok) { c->err = std::string(who) + ": bad arguments"; return SCFGP_EARG; }
-    if (nsamp < 1 || nsamp > SAMPLE_MAX) { c->err = std::string(who) + ": nsamp must lie in 1..1024"; return SCFGP_EARG; }
-    return SCFGP_OK;
-}
-
-extern "C" int scfgp_sample_weights(scfgp_ctx* c, const double* alpha, const double* Li, int nsamp, uint64_t seed, double* W) {
-    if (!c) return SCFGP_EARG;
-    if (int rc = sample_check(c, alpha && Li && W, nsamp, "sample_weights")) return rc;
-    if (int rc = need_model({c, "sample_weights"}, false)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    SampleW sw;
-    if (int rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw)) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(W, sizeof(double) * nsamp, sw.w, sizeof(double) * sample_w_cols(nsamp), sizeof(double) * nsamp, c->g.K,
-                               hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SCFGP_OK;
-}
-
-// The chunk pipeline (RowFeed, OutRing) with the X scaler in modes 1, 2; per chunk Phi* W into one of two staging buffers: device memory
-// is two chunks of samples whatever T is.
-extern "C" int scfgp_sample(scfgp_ctx* c, const double* Xs, int64_t T, const double* alpha, const double* Li, int nsamp, uint64_t seed,
-                            int mode, int noise, double* out) {
-    if (!c) return SCFGP_EARG;
-    int rc;
-    if ((rc = sample_check(c, Xs && alpha && Li && out && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample"))) return rc;
-    if ((rc = need_model({c, "sample"}, mode >= 1, mode == 2))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    SampleW sw;
-    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    const RowJobs jobs = {Xs, nullptr, T, PRED_ROWS};
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count();
-    RowFeed feed; OutRing ring; DevTmp stage;                     // two chunks of Xs | two chunks of samples
-    if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
-    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * nsamp))) return rc;
-    if ((rc = ring.open(c))) return rc;
-    auto slot = [&](int64_t i) { return stage + (i & 1) * rows * nsamp; };
-    auto download = [&](int64_t i) {
-        return ring.drain(i, [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(out + jobs.row0(i) * nsamp, slot(i), sizeof(double) * jobs.rows(i) * nsamp, hipMemcpyDeviceToHost, c->copy_st));
-            return SCFGP_OK;
-        });
-    };
-    const int ymode = mode == 2 ? c->ys_mode : -1;
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double* x;
-        if ((rc = feed.acquire(i, &x))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode >= 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
-        if ((rc = ring.acquire(i))) return rc;
-        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, noise, ymode, slot(i)))) return rc;
-        if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-        if (i >= 1 && (rc = download(i - 1))) return rc;
-    }
-    if ((rc = download(nchunks - 1))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    return SCFGP_OK;
-}
-
-// scfgp_sample's pipeline without the OutRing: the weights w travel as the feed's targets and reach the product's epilogue through
-// pack_data's zero-padded copy; per chunk the workgroups' records (two slots, alternating) are merged into nsamp running (value, row)
-// pairs on the device.  The run owns its buffers: `best` (n = nsamp) is valid once the context's stream has drained.  xraw: the rows go
-// through the registered X scaler.
-struct SampleArgmaxRun {
-    RowFeed feed; DevTmp wchunk, rec;                             // two chunks of [Xs | w] | w of the chunk, padded | records, running best, flag
-    BestBlock best;
-};
-static int sample_argmax_run(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const void* Wt, int nsamp, bool xraw, int minimize,
-                             SampleArgmaxRun& r) {
-    const Geom& g0 = c->g;
-    int rc;
-    const RowJobs jobs = {Xs, w, T, PRED_ROWS};
-    const int64_t nchunks = jobs.count();
-    const int64_t nrec = sample_blocks(round_up(std::min<int64_t>(T, PRED_ROWS), 256), c->tsize()) * nsamp;      // records of a chunk
-    if ((rc = r.feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0))))) return rc;
-    if (w && (rc = dmalloc(c, &r.wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
-    if ((rc = dmalloc(c, &r.rec.p, sizeof(double) * BestBlock::doubles(nsamp, nrec)))) return rc;
-    r.best.carve(r.rec, nsamp, nrec);
-    const BestBlock& best = r.best;
-    if ((rc = best.clear(c))) return rc;
-    if ((rc = r.feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double *x, *wraw;
-        if ((rc = r.feed.acquire(i, &x, &wraw))) return rc;
-        pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, r.wchunk.p, xraw ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = r.feed.release(i))) return rc;
-        const SampleArgmaxBufs b = {best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
-        if ((rc = DISPATCH(c, sample_argmax_chunk, c, g, Wt, nsamp, r.wchunk.p, minimize, jobs.row0(i), b))) return rc;
-        if (i + 1 < nchunks && (rc = r.feed.upload(i + 1, jobs))) return rc;
-    }
-    return SCFGP_OK;
-}
-
-// sample_argmax_run; the running best is all that the host fetches, once, with the non-finite flag.  w is checked on the host before
-// any device work, as scfgp_select does.
-extern "C" int scfgp_sample_argmax(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int nsamp,
-                                   uint64_t seed, int mode, int minimize, int64_t* idx, double* val) {
-    if (!c) return SCFGP_EARG;
-    int rc;
-    if ((rc = sample_check(c, Xs && alpha && Li && idx && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_argmax"))) return rc;
-    const Fail fail = {c, "sample_argmax"};
-    if ((rc = need_model(fail, mode >= 1, mode == 2))) return rc;
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) return fail.nonfinite("non-finite rows, weights or factors");
-        if (!ws.positive) return fail.arg("no row has a positive weight");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    SampleW sw;
-    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    SampleArgmaxRun run;
-    if ((rc = sample_argmax_run(c, Xs, T, w, sw.wt.p, nsamp, mode >= 1, minimize, run))) return rc;
-    if (mode == 2 && val) sample_argmax_finalize(run.best.v(), nsamp, c->ys_mode, c->d_yscale, c->d_sc, c->st);
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> h(2 * nsamp + 1);                         // the outputs are written on success only
-    if ((rc = run.best.fetch(c, h.data()))) return rc;
-    if (run.best.host_flag(h.data())) return fail.nonfinite("non-finite rows, weights or factors");
-    memcpy(idx, &h[nsamp], sizeof(int64_t) * nsamp);
-    if (val) memcpy(val, h.data(), sizeof(double) * nsamp);
-    return SCFGP_OK;
-}
-
-// predict_impl's pipeline (the factor pass, the feed of [Xs | w], mu / sd / acq of all T rows on the device until the end) with
-// acquire.hip's kernels in rowpredict's place and scfgp_sample_argmax's running best and non-finite flag.  With grad, predict_grad_chunk
-// gets the sigma in use as its sd, so its d sigma / d x is that sigma's; the combine runs before the X scaler's chain rule, which is
-// linear per column.  par, fstar and w are checked on the host before any device work; the outputs are written on success only.
-static constexpr int ACQUIRE_MAX_STAR = 1024;
-extern "C" int scfgp_acquire(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li, int kind,
-                             const double* par, int npar, const double* fstar, int nstar, int mode, int noise, int minimize, double* acq,
-                             int64_t* idx, double* val, double* mu, double* sd, double* grad) {
-    if (!c) return SCFGP_EARG;
-    const Fail fail = {c, "acquire"};
-    if (!Xs || !alpha || !Li) return fail.arg("NULL Xs, alpha or Li");
-    if (T < 1) return fail.arg("T must be at least 1");
-    if (kind < 0 || kind > 4) return fail.arg("kind must lie in 0..4");
-    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
-    const int need = kind == 0 ? 1 : (kind == 4 ? 0 : 2);
-    if (npar != need) return fail.arg("npar does not match the kind");
-    if (need && !par) return fail.arg("NULL par");
-    if (kind == 4 && (!fstar || nstar < 1 || nstar > ACQUIRE_MAX_STAR)) return fail.arg("MES needs fstar with 1 <= nstar <= 1024");
-    if (kind != 4 && (fstar || nstar)) return fail.arg("fstar given for a kind other than MES");
-    if (!acq && !idx && !grad) return fail.arg("no output requested (acq, idx and grad are all NULL)");
-    if (val && !idx) return fail.arg("val without idx");
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    AcquireSpec spec = {kind, {0.0, 0.0}, nullptr, kind == 4 ? nstar : 0, noise ? 1 : 0, minimize ? 1 : 0};
-    bool nonfinite = false;
-    for (int i = 0; i < need; ++i) { spec.par[i] = par[i]; if (!std::isfinite(par[i])) nonfinite = true; }
-    for (int i = 0; i < spec.nstar; ++i) if (!std::isfinite(fstar[i])) nonfinite = true;
-    if (!nonfinite && kind == 0 && par[0] < 0.0) return fail.arg("beta must not be negative");
-    if (!nonfinite && (kind >= 1 && kind <= 3) && par[1] < 0.0) return fail.arg("xi must not be negative");
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) nonfinite = true;
-        if (!nonfinite && !ws.positive) return fail.arg("no row has a positive weight");
-    }
-    if (nonfinite) return fail.nonfinite("non-finite par, fstar or weights");
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if (grad && (rc = ensure_pred_grad(c, true))) return rc;
-    const RowJobs jobs = {Xs, w, T, PRED_ROWS};
-    const int64_t nchunks = jobs.count();
-    const int64_t nrec = acquire_blocks(PRED_ROWS);
-    RowFeed feed; DevTmp d_out, d_grad, work;     // Li / two chunks of [Xs | w] | mu, sd, acq of all T rows | grad of all T rows | chunk scratch
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0)), (int64_t)g0.K * g0.K))) return rc;
-    if ((rc = dmalloc(c, &d_out.p, sizeof(double) * 3 * T))) return rc;
-    // work: w of the chunk, padded | a_u | a_sigma | d sigma / d x of the chunk | records of two chunks | running best, flag | fstar
-    const int64_t n_dsd = grad ? PRED_ROWS * g0.D : 0;
-    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + n_dsd + BestBlock::doubles(1, nrec) + ACQUIRE_MAX_STAR)))) return rc;
-    double* d_mu = d_out; double* d_sd = d_out + T; double* d_acq = d_out + 2 * T;
-    double* d_w = work; double* d_au = work + PRED_ROWS; double* d_as = work + 2 * PRED_ROWS; double* d_dsd = work + 3 * PRED_ROWS;
-    BestBlock best;
-    best.carve(d_dsd + n_dsd, 1, nrec);
-    double* d_fstar = best.rec + BestBlock::doubles(1, nrec);
-    if ((rc = best.clear(c))) return rc;
-    if (kind == 4) {
-        HIPCHK(c, hipMemcpyAsync(d_fstar, fstar, sizeof(double) * nstar, hipMemcpyHostToDevice, c->st));
-        spec.fstar = d_fstar;
-    }
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, false, alpha, &LiT))) return rc;
-    if (grad) {
-        if ((rc = dmalloc(c, &d_grad.p, sizeof(double) * T * g0.D))) return rc;
-        DISPATCH(c, grad_operand, c);
-        DISPATCH(c, type_factor, c, c->d_T1, nullptr, c->p_Li);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = jobs.row0(i);
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double *x, *wraw;
-        if ((rc = feed.acquire(i, &x, &wraw))) return rc;
-        pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, w ? d_w : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if (!grad && (rc = feed.release(i))) return rc;
-        const AcquireBufs b = {d_mu + t0, d_sd + t0, d_acq + t0, d_au, d_as, best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
-        if ((rc = DISPATCH(c, acquire_chunk, c, g, LiT, spec, w ? d_w : nullptr, t0, b))) return rc;
-        if (grad) {
-            double* gm = d_grad + t0 * g0.D;
-            if ((rc = DISPATCH(c, predict_grad_chunk, c, g, LiT, d_sd + t0, gm, d_dsd))) return rc;
-            acquire_grad(g, b, spec.minimize, d_dsd, gm, c->st);
-            if (mode == 1 && c->xs_mode) xgrad_chunk(x, g.N, g0.D, c->xs_mode, c->d_xscale, gm, nullptr, c->st);
-            if ((rc = feed.release(i))) return rc;
-        }
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    double h[3];                                                  // the running best and the flag first: the outputs are written on success only
-    if ((rc = best.fetch(c, h))) return rc;
-    if (best.host_flag(h)) return fail.nonfinite("an eligible row has a non-finite mu, sigma or value, or sigma = 0");
-    if (acq) HIPCHK(c, hipMemcpyAsync(acq, d_acq, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (mu) HIPCHK(c, hipMemcpyAsync(mu, d_mu, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (sd) HIPCHK(c, hipMemcpyAsync(sd, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (grad) HIPCHK(c, hipMemcpyAsync(grad, d_grad, sizeof(double) * T * g0.D, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (idx) memcpy(idx, &h[1], sizeof(int64_t));
-    if (val) val[0] = h[0];
-    return SCFGP_OK;
-}
-
-// scfgp_acquire's pipeline with scfgp_predict_cov's first job: job 0 of the feed is the reference rows (Cb stays in p_V, d_r on the
-// device), the chunks of [Xc | w] follow; each chunk's kg / kg_hi (and node table) join the call's T-sized arrays, its best eligible row
-// the running best, through acquire.hip's argmax kernels (kg_hi in mu's place: an eligible row's kg, kg_hi and sigma must be finite,
-// sigma not 0).  The symmetric form is the call with Xr = Xc.  z and w are checked on the host before any device work; the outputs are
-// written on success only.
-static constexpr int KG_MAX_NODES = 32;
-extern "C" int scfgp_acquire_kg(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* alpha,
-                                const double* Li, const double* z, int J, int mode, int noise, int minimize, double* kg, double* kg_hi,
-                                int64_t* idx, double* val, double* m, double* s) {
-    if (!c) return SCFGP_EARG;
-    const Fail fail = {c, "acquire_kg"};
-    if (!Xc || !alpha || !Li || !z) return fail.arg("NULL Xc, alpha, Li or z");
-    if (T < 1) return fail.arg("T must be at least 1");
-    if (!Xr) {
-        if (T > PRED_ROWS) return fail.arg("the symmetric form (Xr == NULL) takes 1..32768 rows");
-        Xr = Xc; R = T;
-    } else if (R < 1 || R > PRED_ROWS) return fail.arg("R must lie in 1..32768");
-    if (J < 3 || J > KG_MAX_NODES) return fail.arg("J must lie in 3..32");
-    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
-    if (!kg && !kg_hi && !idx && !m && !s) return fail.arg("no output requested (kg, kg_hi, idx, m and s are all NULL)");
-    if (val && !idx) return fail.arg("val without idx");
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    bool nonfinite = false;
-    for (int j = 0; j < J; ++j) if (!std::isfinite(z[j])) nonfinite = true;
-    if (!nonfinite) {
-        int zeros = z[0] == 0.0 ? 1 : 0;
-        for (int j = 1; j < J; ++j) {
-            if (!(z[j] > z[j - 1])) return fail.arg("the nodes must be strictly increasing");
-            if (z[j] == 0.0) ++zeros;
-        }
-        if (zeros != 1) return fail.arg("exactly one node must be 0.0");
-    }
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) nonfinite = true;
-        if (!nonfinite && !ws.positive) return fail.arg("no row has a positive weight");
-    }
-    if (nonfinite) return fail.nonfinite("non-finite nodes or weights");
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    const RowJobs jobs = {Xc, w, T, PRED_ROWS, Xr, R};              // job 0: the reference rows
-    const int64_t njobs = jobs.count();
-    const int64_t nrec = acquire_blocks(PRED_ROWS), SR = kg_state_rows();
-    const bool table = m || s;
-    RowFeed feed; DevTmp d_out, work;             // Li / two jobs of [X | w] | kg, kg_hi (and m, s) of all T rows | chunk scratch
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (w ? 1 : 0)), (int64_t)g0.K * g0.K))) return rc;
-    if ((rc = dmalloc(c, &d_out.p, sizeof(double) * T * (2 + (table ? 2 * J : 0))))) return rc;
-    // work: w of the chunk, padded | sigma of the chunk | d_r | z as given | nodes and h(-|z|) | records of two chunks | running best, flags |
-    // bmin, bmax and the (m, s) states per row and column split
-    if ((rc = dmalloc(c, &work.p, sizeof(double) * (3 * PRED_ROWS + 96 + BestBlock::doubles(1, nrec) + SR * (2 + 2 * J))))) return rc;
-    double* d_kg = d_out; double* d_hi = d_out + T; double* d_m = table ? d_out + 2 * T : nullptr; double* d_s = table ? d_m + T * J : nullptr;
-    double* d_w = work; double* d_sd = work + PRED_ROWS; double* d_d = work + 2 * PRED_ROWS; double* d_z = work + 3 * PRED_ROWS;
-    double* d_zf = d_z + 32;
-    BestBlock best;                                               // flag [0]: a candidate (acquire_argmax); [1]: a reference row
-    best.carve(d_zf + 64, 1, nrec);
-    double* d_stb = best.rec + BestBlock::doubles(1, nrec); double* d_stm = d_stb + 2 * SR; double* d_sts = d_stm + SR * J;
-    if ((rc = best.clear(c))) return rc;
-    HIPCHK(c, hipMemcpyAsync(d_z, z, sizeof(double) * J, hipMemcpyHostToDevice, c->st));
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, jobs.rows(job));
-        const double *x, *wraw;
-        if ((rc = feed.acquire(job, &x, &wraw))) return rc;
-        const bool cand = !jobs.lead(job);
-        pack_chunk(c, g, x, cand && w ? wraw : nullptr, nullptr, cand && w ? d_w : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(job))) return rc;
-        const int64_t i = jobs.chunk(job), t0 = i * PRED_ROWS;
-        const KgBufs b = {d_d, d_zf, d_sd, d_stm, d_sts, d_stb, cand ? d_kg + t0 : nullptr, cand ? d_hi + t0 : nullptr,
-                          cand && table ? d_m + t0 * J : nullptr, cand && table ? d_s + t0 * J : nullptr};
-        if (!cand) {
-            if ((rc = DISPATCH(c, kg_ref_chunk, c, g, LiT, minimize ? 1 : 0, d_z, J, b, best.flag()))) return rc;
-        } else {
-            if ((rc = DISPATCH(c, kg_chunk, c, g, LiT, R, J, noise ? 1 : 0, b))) return rc;
-            const AcquireBufs ab = {b.kg_hi, d_sd, b.kg, nullptr, nullptr, best.rec_v(i), best.rec_t(i), best.v(), best.t(), best.flag()};
-            acquire_argmax(g, w ? d_w : nullptr, t0, i == 0, ab, c->st);
-        }
-        if (job + 1 < njobs && (rc = feed.upload(job + 1, jobs))) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    double h[3];                                                  // the running best and the flags first: the outputs are written on success only
-    if ((rc = best.fetch(c, h))) return rc;
-    if (best.host_flag(h, 1)) return fail.nonfinite("a reference row has a non-finite mean");
-    if (best.host_flag(h, 0)) return fail.nonfinite("an eligible candidate has a non-finite value or sigma, or sigma = 0");
-    if (kg) HIPCHK(c, hipMemcpyAsync(kg, d_kg, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (kg_hi) HIPCHK(c, hipMemcpyAsync(kg_hi, d_hi, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (m) HIPCHK(c, hipMemcpyAsync(m, d_m, sizeof(double) * T * J, hipMemcpyDeviceToHost, c->st));
-    if (s) HIPCHK(c, hipMemcpyAsync(s, d_s, sizeof(double) * T * J, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (idx) memcpy(idx, &h[1], sizeof(int64_t));
-    if (val) val[0] = h[0];
-    return SCFGP_OK;
-}
-
-// scfgp_sample's pipeline (RowFeed, OutRing) with the weights given: W is uploaded and transposed once, the rows' sample indices travel
-// as the feed's targets (doubles: exact below 1024) and reach the kernel through pack_data's zero-padded copy, and each chunk leaves
-// [grad (rows x D) | val (rows)] in one of two staging slots.  W and sidx are checked on the host before any device work.
-extern "C" int scfgp_sample_grad(scfgp_ctx* c, const double* Xs, int64_t T, const double* W, int nsamp, const int64_t* sidx, int mode,
-                                 double* val, double* grad) {
-    if (!c) return SCFGP_EARG;
-    int rc;
-    if ((rc = sample_check(c, Xs && W && grad && T >= 1 && mode >= 0 && mode <= 2, nsamp, "sample_grad"))) return rc;
-    const Fail fail = {c, "sample_grad"};
-    if ((rc = need_model(fail, mode >= 1, mode == 2))) return rc;
-    const Geom& g0 = c->g;
-    std::vector<double> hs;                                       // sidx as the feed's targets
-    if (sidx) {
-        hs.resize(T);
-        for (int64_t t = 0; t < T; ++t) {
-            if (sidx[t] < 0 || sidx[t] >= nsamp)
-                return fail.arg("sample index " + std::to_string(sidx[t]) + " at row " + std::to_string(t) + " is outside [0, nsamp)");
-            hs[t] = (double)sidx[t];
-        }
-    }
-    for (int64_t e = 0, n = (int64_t)g0.K * nsamp; e < n; ++e)
-        if (!std::isfinite(W[e])) return fail.nonfinite("non-finite weights");
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_grad(c, false))) return rc;
-    DevTmp wraw, wt, schunk, stage;                               // W as uploaded | its transpose | sidx of the chunk, padded | two slots
-    const int ldw = samplegrad_w_ld(g0.K);
-    if ((rc = dmalloc(c, &wraw.p, sizeof(double) * g0.K * nsamp))) return rc;
-    if ((rc = dmalloc(c, &wt.p, sizeof(double) * (int64_t)nsamp * ldw))) return rc;
-    if (sidx && (rc = dmalloc(c, &schunk.p, sizeof(double) * PRED_ROWS))) return rc;
-    HIPCHK(c, hipMemcpyAsync(wraw, W, sizeof(double) * g0.K * nsamp, hipMemcpyHostToDevice, c->st));
-    samplegrad_weights(wraw, g0.K, nsamp, wt, c->st);
-    DISPATCH(c, grad_operand, c);
-    const RowJobs jobs = {Xs, sidx ? hs.data() : nullptr, T, PRED_ROWS};
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count(), slot_len = rows * (g0.D + 1);
-    RowFeed feed; OutRing ring;
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + (sidx ? 1 : 0))))) return rc;
-    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
-    if ((rc = ring.open(c))) return rc;
-    auto slot_grad = [&](int64_t i) { return stage + (i & 1) * slot_len; };
-    auto slot_val = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * g0.D; };
-    auto download = [&](int64_t i) {
-        return ring.drain(i, [&]() -> int {
-            const int64_t t0 = jobs.row0(i), n = jobs.rows(i);
-            HIPCHK(c, hipMemcpyAsync(grad + t0 * g0.D, slot_grad(i), sizeof(double) * n * g0.D, hipMemcpyDeviceToHost, c->copy_st));
-            if (val) HIPCHK(c, hipMemcpyAsync(val + t0, slot_val(i), sizeof(double) * n, hipMemcpyDeviceToHost, c->copy_st));
-            return SCFGP_OK;
-        });
-    };
-    const int xmode = mode >= 1 ? c->xs_mode : 0;
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double *x, *sraw;
-        if ((rc = feed.acquire(i, &x, &sraw))) return rc;
-        pack_chunk(c, g, x, sidx ? sraw : nullptr, nullptr, schunk.p, xmode, c->d_xscale);
-        if ((rc = ring.acquire(i))) return rc;
-        if ((rc = DISPATCH(c, sample_grad_chunk, c, g, wt.p, schunk.p, jobs.row0(i), nsamp, slot_val(i), slot_grad(i)))) return rc;
-        // the scalers' chain rules: the X scaler's at the raw inputs (still in the feed's half: it is released after them), the y
-        // scaler's at the scaled value, which its backward transform then replaces
-        if (xmode) xgrad_chunk(x, g.N, g0.D, xmode, c->d_xscale, slot_grad(i), nullptr, c->st);
-        if ((rc = feed.release(i))) return rc;
-        if (mode == 2) {
-            ygrad_chunk(slot_val(i), nullptr, g.N, g0.D, c->ys_mode, c->d_yscale, slot_grad(i), nullptr, c->st);
-            sample_argmax_finalize(slot_val(i), (int)g.N, c->ys_mode, c->d_yscale, c->d_sc, c->st);
-        }
-        if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-        if (i >= 1 && (rc = download(i - 1))) return rc;
-    }
-    if ((rc = download(nchunks - 1))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// joint posterior covariance between test points (predcov.hip; contract in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-// The chunk pipeline (RowFeed, OutRing) with the X scaler in mode 1; the chunk body is C = Phi* Li^T.  Cb (the rows of Xb) is formed
-// once, into p_V, by job 0 of the feed; each chunk of Xa gives Ca in p_C; in the symmetric case (Ta <= PRED_ROWS) Ca is both operands.
-// A chunk's rows of the result are computed in panels of R rows x Tb, full rows in the symmetric case too (its symmetry comes from the
-// commutativity of the products, predcov.hip); the ring's slots are panels, not chunks: device memory does not grow with Ta x Tb.
-static constexpr int64_t COV_PANEL_BYTES = (int64_t)128 << 20;   // per staging panel: the size scfgp_sample stages per chunk at 512 samples
-extern "C" int scfgp_predict_cov(scfgp_ctx* c, const double* Xa, int64_t Ta, const double* Xb, int64_t Tb, const double* Li, int mode,
-                                 int noise, double* cov) {
-    if (!c) return SCFGP_EARG;
-    if (!Xa || !Li || !cov || mode < 0 || mode > 1) { c->err = "predict_cov: bad arguments"; return SCFGP_EARG; }
-    const bool sym = Xb == nullptr;
-    if (sym) Tb = Ta;
-    const Fail fail = {c, "predict_cov"};
-    if (Ta < 1) return fail.arg("Ta must be at least 1");
-    if (Tb < 1 || Tb > PRED_ROWS) return fail.arg(sym ? "the symmetric form takes 1..32768 rows" : "Tb must lie in 1..32768");
-    if (!sym && noise) return fail.arg("noise is defined for the symmetric form (Xb == NULL) only");
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
-    const size_t ts = c->tsize();
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    // panel height: whole 128-row tiles within COV_PANEL_BYTES, no more than a chunk holds
-    const int64_t R = std::min<int64_t>(round_up(std::min<int64_t>(Ta, PRED_ROWS), 128),
-                                        std::max<int64_t>(128, COV_PANEL_BYTES / ((int64_t)sizeof(double) * Tb) / 128 * 128));
-    RowFeed feed; OutRing ring; DevTmp stage;                     // Li / two chunks of X | two panels of the result
-    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
-    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * R * Tb))) return rc;
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, true, nullptr, &LiT))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = ring.open(c))) return rc;
-    const RowJobs jobs = {Xa, nullptr, Ta, PRED_ROWS, Xb, Tb};       // job 0 is Xb in the cross form, the chunks of Xa follow
-    const int64_t njobs = jobs.count();
-    // panel p: rows [row0, row0 + n) of the result
-    struct Panel { int64_t row0, n; };
-    auto slot = [&](int64_t p) { return stage + (p & 1) * R * Tb; };
-    auto download = [&](int64_t p, Panel pn) {
-        return ring.drain(p, [&]() -> int {
-            HIPCHK(c, hipMemcpyAsync(cov + pn.row0 * Tb, slot(p), sizeof(double) * pn.n * Tb, hipMemcpyDeviceToHost, c->copy_st));
-            return SCFGP_OK;
-        });
-    };
-    int64_t npanel = 0;
-    Panel prev = {0, 0};
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, jobs.rows(job));
-        const double* x;
-        if ((rc = feed.acquire(job, &x))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(job))) return rc;
-        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, jobs.lead(job) ? c->p_V : c->p_C))) return rc;
-        if (job + 1 < njobs && (rc = feed.upload(job + 1, jobs))) return rc;
-        if (jobs.lead(job)) continue;
-        const int64_t t0 = jobs.row0(job);
-        const void* Cb = sym ? c->p_C : c->p_V;
-        for (int64_t r0 = 0; r0 < g.N; r0 += R, ++npanel) {
-            const Panel pn = {t0 + r0, std::min<int64_t>(R, g.N - r0)};
-            if ((rc = ring.acquire(npanel))) return rc;
-            DISPATCH(c, cov_panel, c, (const char*)c->p_C + ts * r0 * Kp, Cb, pn.n, Tb, pn.row0, noise, slot(npanel));
-            HIPCHK(c, hipGetLastError());
-            if ((rc = ring.computed(npanel))) return rc;
-            if (npanel >= 1 && (rc = download(npanel - 1, prev))) return rc;
-            prev = pn;
-        }
-    }
-    if ((rc = download(npanel - 1, prev))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// absorbing new observations into a fitted posterior (kernels_kstage.hip: kstage_update; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-// row splits of the update's Gram product over a chunk of Np rows, and the slabs they need
-static RowSplits update_splits(const scfgp_ctx* c, int64_t Np, bool wide = false) {
-    if (wide) return gram_row_splits(Impl<double>::gram_jobs(c), Np, false, 0, 1);     // the fp64 job list in an fp32 context
-    return gram_row_splits(DISPATCH(c, gram_jobs, c), Np, c->dtype == SCFGP_F32, 0, 1);
-}
-// the update stage's own buffers (first call only; the slabs grow to what the call's chunks need)
-static int ensure_update(scfgp_ctx* c, size_t slabs_bytes) {
-    const int64_t Kp = c->g.Kp, K2 = Kp * Kp;
-    int rc;
-    if (!c->u_flag) {
-        if ((rc = dmalloc(c, &c->u_Li, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_S, sizeof(double) * K2)) ||
-            (rc = dmalloc(c, &c->u_Lm, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_Mi, sizeof(double) * K2)) ||
-            (rc = dmalloc(c, &c->u_Si, sizeof(double) * K2)) || (rc = dmalloc(c, &c->u_LiT, c->tsize() * K2)) ||
-            (rc = dmalloc(c, &c->u_vec, sizeof(double) * 35 * Kp)) || (rc = dmalloc(c, &c->u_acc, sizeof(double) * (c->n_pk + Kp))) ||
-            (rc = dmalloc(c, &c->u_part, sizeof(double) * (c->n_pk + Kp))) || (rc = dmalloc(c, &c->u_y, sizeof(double) * PRED_ROWS)) ||
-            (rc = dmalloc(c, &c->u_r, sizeof(double) * PRED_ROWS)) || (rc = dmalloc(c, &c->u_ws2, sizeof(float) * 2 * (PRED_ROWS + 32))))
-            return rc;
-        HIPCHK(c, hipMemsetAsync(c->u_Mi, 0, sizeof(double) * K2, c->st));       // its blocks above the diagonal stay zero for good
-        HIPCHK(c, hipMemsetAsync(c->u_ws2, 0, sizeof(float) * 2 * (PRED_ROWS + 32), c->st));
-        if ((rc = dmalloc(c, &c->u_flag, sizeof(int) * 16))) return rc;
-    }
-    if (slabs_bytes > c->u_slabs_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        dfree(c->u_slabs); c->u_slabs_bytes = 0;
-        if ((rc = dmalloc(c, &c->u_slabs, slabs_bytes))) return rc;
-        c->u_slabs_bytes = slabs_bytes;
-    }
-    return SCFGP_OK;
-}
-
-// The first pass of scfgp_condition and scfgp_forget: the chunk pipeline (RowFeed) with the targets behind the rows of their chunk and
-// the X scaler in mode 1.  The factors are loaded into the update's buffers (u_Li, u_LiT, alpha at u_vec), then each chunk adds its
-// C^T C and C^T r to a running fp64 sum in u_acc and, rr != NULL, its r^T r to rr[0].  u_flag[0..3] are cleared first; u_flag[1] tells
-// of non-finite rows, targets or factors.  `feed` is opened here and stays open for the caller.  wide != NULL (fp32 contexts only): the
-// pass runs the fp64 kernels on these operands.
-//
-// How a chunk's rows and targets are produced is the caller's: produce(i, g, x, targets, ops, &have_rows) packs job i (g: its geometry
-// in points; x, targets: its place in the feed), releases the feed's half when the raw rows have been read, and either leaves the
-// feature map to update_chunk (the packed rows ARE the update's rows, targets in u_y) or writes the rows of the update itself into
-// ops.Phi and u_y (have_rows; rpp of them per point: scfgp_condition_grad).
-template <typename Produce>
-static int update_gather(scfgp_ctx* c, RowFeed& feed, const RowJobs& jobs, int64_t rpp, const double* alpha, const double* Li, double* rr,
-                         const UpdateOperands* wide, Produce produce) {
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
-    const int64_t nchunks = jobs.count(), n = jobs.n * rpp, CHR = jobs.CH * rpp;      // the update's rows: in all, per full chunk
-    int rc;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    {   // slabs of the widest split among the call's chunk shapes (full chunks and the ragged last one)
-        const int nts = Kp / g0.tile, ntiles = nts * (nts + 1) / 2;
-        size_t need = 0;
-        for (int64_t np : {round_up(std::min<int64_t>(n, CHR), 256), round_up(n - (nchunks - 1) * CHR, 256)})
-            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np, wide).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
-        if ((rc = ensure_update(c, need))) return rc;
-    }
-    const UpdateOperands own = {c->p_Phi, c->p_C, c->u_LiT, c->p_Li};
-    const UpdateOperands& ops = wide ? *wide : own;
-    // Li in host layout (in, then out) / two chunks of [X | y]
-    if ((rc = feed.open(c, PRED_ROWS * g0.D + jobs.CH * std::max<int64_t>(1, jobs.target_width()), (int64_t)g0.K * g0.K))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->u_flag, 0, sizeof(int) * 4, c->st));
-    if (rr) HIPCHK(c, hipMemsetAsync(rr, 0, sizeof(double), c->st));
-    if ((rc = load_factor(c, feed.raw, Li, update_load_factor, c->u_Li, wide ? nullptr : ops.LiT, wide ? nullptr : ops.Li, alpha, c->u_vec,
-                          c->u_flag))) return rc;
-    if (wide) Impl<double>::type_factor(c, c->u_Li, ops.LiT, ops.Li);
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom gp = chunk_geom(g0, jobs.rows(i));
-        const double *x, *yi;
-        if ((rc = feed.acquire(i, &x, &yi))) return rc;
-        bool have_rows = false;
-        if ((rc = produce(i, gp, x, yi, ops, &have_rows))) return rc;
-        const Geom g = have_rows ? chunk_geom(g0, jobs.rows(i) * rpp) : gp;
-        double* out = i == 0 ? c->u_acc : c->u_part;
-        if ((rc = wide ? Impl<double>::update_chunk(c, g, update_splits(c, g.Np, true), ops, out, have_rows)
-                       : DISPATCH(c, update_chunk, c, g, update_splits(c, g.Np), ops, out, have_rows))) return rc;
-        if (i > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk + Kp, c->st);
-        if (rr) update_sumsq(c->u_r, g.N, rr, c->st);
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-    }
-    // non-finite rows or targets have reached C^T C or C^T r by now
-    update_check_finite(c->u_acc, c->n_pk + Kp, c->u_flag, c->st);
-    return SCFGP_OK;
-}
-// scfgp_condition, scfgp_forget: the n rows (X, y) in chunks of PRED_ROWS are the update's rows
-static int update_gather(scfgp_ctx* c, RowFeed& feed, const double* X, const double* y, int64_t n, const double* alpha, const double* Li,
-                         int mode, double* rr, const UpdateOperands* wide = nullptr) {
-    const RowJobs jobs = {X, y, n, PRED_ROWS};
-    return update_gather(c, feed, jobs, 1, alpha, Li, rr, wide,
-                         [&](int64_t i, const Geom& g, const double* x, const double* yi, const UpdateOperands&, bool*) {
-                             pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-                             return feed.release(i);
-                         });
-}
-static KUpdate update_buffers(scfgp_ctx* c) {
-    const int64_t Kp = c->g.Kp;
-    KUpdate k;
-    k.K = c->g.K; k.Kp = c->g.Kp; k.packed = c->u_acc; k.n_pk = c->n_pk; k.Li = c->u_Li; k.alpha = c->u_vec; k.S = c->u_S; k.Lm = c->u_Lm;
-    k.Mi = c->u_Mi; k.Si = c->u_Si; k.gamma = c->u_vec + Kp; k.alpha_out = c->u_vec + 2 * Kp; k.part = c->u_vec + 3 * Kp; k.flag = c->u_flag;
-    return k;
-}
-
-// One K x K stage turns the first pass's sum into the new factors, which leave through the feed's buffer.  The outputs are fetched only
-// when the stage succeeded.  who, what: the entry point and its name for the targets in the error texts
-static int update_finish(scfgp_ctx* c, RowFeed& feed, const char* who, const char* what, double* alpha_out, double* Li_out) {
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    const Fail fail = {c, who};
-    const KUpdate k = update_buffers(c);
-    kstage_update(k, c->st);
-    update_check_finite(c->u_S, K2, c->u_flag, c->st);
-    update_check_finite(k.alpha_out, Kp, c->u_flag, c->st);
-    update_store_factor(c->u_S, g0.K, g0.Kp, feed.raw, c->st);
-    HIPCHK(c, hipGetLastError());
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flags[1]) return fail.nonfinite(std::string("non-finite rows, ") + what + " or factors");
-    if (flags[0]) return fail.set("I + C^T C is not positive definite", SCFGP_ENOTPD);
-    HIPCHK(c, hipMemcpyAsync(Li_out, feed.raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SCFGP_OK;
-}
-extern "C" int scfgp_condition(scfgp_ctx* c, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
-                               double* alpha_out, double* Li_out) {
-    if (!c) return SCFGP_EARG;
-    if (!Xn || !yn || !alpha || !Li || !alpha_out || !Li_out || mode < 0 || mode > 1) { c->err = "condition: bad arguments"; return SCFGP_EARG; }
-    if (n < 1) { c->err = "condition: n must be at least 1"; return SCFGP_EARG; }
-    int rc;
-    if ((rc = need_model({c, "condition"}, mode == 1))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    RowFeed feed;
-    if ((rc = update_gather(c, feed, Xn, yn, n, alpha, Li, mode, nullptr))) return rc;
-    return update_finish(c, feed, "condition", "targets", alpha_out, Li_out);
-}
-
-// ----------------------------------------------------------------------------------------------
-// absorbing derivative observations into a fitted posterior (condgrad.hip; derivation and promises in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-// scfgp_condition's path with another producer of a chunk's rows: a chunk holds whole points, np = PRED_ROWS / nb of them (GradBlocks,
-// api_host.h), whose features are expanded into nb observation rows each (Impl::gradobs_chunk).  A job uploads [X | yn | Gn | rho] of its
-// points; the raw rows stay in the feed's half until the scaler's factors g_t have been formed from them (mode 1) and the targets
-// until the row kernel has read them.  In fp32 contexts the first pass is the fp64 one on scfgp_forget's buffers, as there: a derivative
-// row is |F_all[d, :]| sqrt(rho / J) times as long as a value row, the rounding errors of the fp32 products grow with its square, and
-// the predictions feel them (DESIGN 4.20 has the measured ratios).
-static int ensure_forget(scfgp_ctx* c);
-extern "C" int scfgp_condition_grad(scfgp_ctx* c, const double* Xn, int64_t n, const int32_t* dims, int nd, const double* Gn, const double* rho,
-                                    const double* yn, const double* alpha, const double* Li, int mode, double* alpha_out, double* Li_out) {
-    if (!c) return SCFGP_EARG;
-    const Fail fail = {c, "condition_grad"};
-    if (!Xn || !Gn || !alpha || !Li || !alpha_out || !Li_out) return fail.arg("bad arguments");
-    if (n < 1) return fail.arg("n must be at least 1");
-    const Geom& g0 = c->g;
-    const int D = g0.D;
-    if (nd < 1 || nd > D) return fail.arg("nd must lie in 1..D");
-    const GradBlocks gb = {nd, yn != nullptr, rho != nullptr};
-    if (gb.nb() > PRED_ROWS) return fail.arg("the rows of a point (nd, and one for its value) must not exceed 32768");
-    if (!dims && nd != D) return fail.arg("dims == NULL needs nd == D");
-    if (dims) {
-        std::vector<char> seen(D);
-        const int j = first_bad_dim(dims, nd, D, seen.data());
-        if (j >= 0) return fail.arg("dims[" + std::to_string(j) + "] is out of range or repeated");
-    }
-    if (mode < 0 || mode > 1) return fail.arg("bad mode");
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    if (rho) {
-        const WeightScan ws = scan_weights(rho, n * nd);
-        auto at = [&](int64_t e) { return "rho[" + std::to_string(e / nd) + ", " + std::to_string(e % nd) + "]"; };
-        if (ws.first_negative >= 0) return fail.arg(at(ws.first_negative) + " is negative");
-        if (ws.first_nonfinite >= 0) return fail.nonfinite(at(ws.first_nonfinite) + " is not finite");
-        if (!yn && ws.positive == 0) return fail.arg("every rho is zero and no values are given");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/condition_grad_time.py)
-    const int xmode = mode == 1 ? c->xs_mode : 0;
-    const RowJobs jobs = gb.jobs(Xn, yn, Gn, rho, n, PRED_ROWS);
-    DevTmp d_dims, gfac;                                          // dims | g_t of a chunk's points
-    if (dims) {
-        if ((rc = dmalloc(c, &d_dims.p, sizeof(int) * nd))) return rc;
-        HIPCHK(c, hipMemcpyAsync(d_dims.p, dims, sizeof(int) * nd, hipMemcpyHostToDevice, c->st));
-    }
-    if (xmode && (rc = dmalloc(c, &gfac.p, sizeof(double) * std::min(n, jobs.CH) * D))) return rc;
-    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    if (c->dtype == SCFGP_F32 && (rc = ensure_forget(c))) return rc;
-    const UpdateOperands wide = {c->f_w, c->f_w + PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp + K2};
-    RowFeed feed;
-    auto produce = [&](int64_t i, const Geom& g, const double* x, const double* tg, const UpdateOperands& ops, bool* have_rows) -> int {
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
-        if (xmode) {
-            gradcov_ones(gfac.p, g.N * D, c->st);
-            xgrad_chunk(x, g.N, D, xmode, c->d_xscale, gfac.p, nullptr, c->st);
-        }
-        const GradObs obs = {(const int*)d_dims.p, nd, xmode ? gfac.p : nullptr, yn ? tg + jobs.seg_off(0) : nullptr, tg + jobs.seg_off(1),
-                             rho ? tg + jobs.seg_off(2) : nullptr};
-        const Geom gr = chunk_geom(g0, g.N * gb.nb());
-        if (int r = Impl<double>::gradobs_chunk(c, g, gr, ops, obs)) return r;      // fp64 operands in every context
-        *have_rows = true;
-        return feed.release(i);
-    };
-    if ((rc = update_gather(c, feed, jobs, gb.nb(), alpha, Li, nullptr, c->dtype == SCFGP_F32 ? &wide : nullptr, produce))) return rc;
-    return update_finish(c, feed, "condition_grad", "observations", alpha_out, Li_out);
-}
-
-// ----------------------------------------------------------------------------------------------
-// removing observations from a fitted posterior (kernels_kstage.hip: kstage_downdate; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static int ensure_forget(scfgp_ctx* c) {
-    if (c->f_out) return SCFGP_OK;
-    const int64_t Kp = c->g.Kp;
-    int rc;
-    if (c->dtype == SCFGP_F32) {
-        const size_t bytes = sizeof(double) * 2 * (PRED_ROWS * Kp + Kp * Kp);
-        if ((rc = dmalloc(c, &c->f_w, bytes))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->f_w, 0, bytes, c->st));               // the padding columns of Phi and C stay zero
-    }
-    return dmalloc(c, &c->f_out, sizeof(double) * (7 * PRED_ROWS + 8));
-}
-// scfgp_condition's first pass over the rows (plus r^T r), the K x K stage in its downdate form, then -- mu != NULL -- a second pass of
-// the same feed over the rows: predict_chunk on the typed transpose of the device's Li', mu | std leaving through two staging halves
-// (OutRing), the stats' sums formed on the device.  The host learns whether the stage succeeded before anything is written.
-extern "C" int scfgp_forget(scfgp_ctx* c, const double* Xo, const double* yo, int64_t n, const double* alpha, const double* Li, int mode,
-                            double* alpha_out, double* Li_out, double* mu, double* sd, double* stats) {
-    if (!c) return SCFGP_EARG;
-    if (!Xo || !yo || !alpha || !Li || mode < 0 || mode > 1) { c->err = "forget: bad arguments"; return SCFGP_EARG; }
-    if ((!alpha_out) != (!Li_out)) { c->err = "forget: alpha_out and Li_out go together"; return SCFGP_EARG; }
-    if ((!mu) != (!sd)) { c->err = "forget: mu and std go together"; return SCFGP_EARG; }
-    if (stats && !mu) { c->err = "forget: stats need mu and std"; return SCFGP_EARG; }
-    if (!alpha_out && !mu) { c->err = "forget: no output asked for"; return SCFGP_EARG; }
-    if (n < 1) { c->err = "forget: n must be at least 1"; return SCFGP_EARG; }
-    int rc;
-    if ((rc = need_model({c, "forget"}, mode == 1))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    const RowJobs jobs = {Xo, yo, n, PRED_ROWS};
-    const int64_t nchunks = jobs.count();
-    if ((rc = ensure_forget(c))) return rc;
-    double* rec = c->f_out + 4 * PRED_ROWS; double* acc = c->f_out + 7 * PRED_ROWS;
-    // In fp32 contexts the first pass is the fp64 one: the error of C^T C is divided by lam_min(S) here, and what the fp32 chains of the
-    // Gram launch add to it (~1e-6 of its entries) is felt in the predictions once most of a fit is removed.
-    const UpdateOperands wide = {c->f_w, c->f_w + PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp, c->f_w + 2 * PRED_ROWS * Kp + K2};
-    RowFeed feed;
-    if ((rc = update_gather(c, feed, Xo, yo, n, alpha, Li, mode, acc + 3, c->dtype == SCFGP_F32 ? &wide : nullptr))) return rc;
-    const KUpdate k = update_buffers(c);
-    kstage_downdate(k, acc + 3, (double)n, c->d_sc, acc + 4, c->st);
-    // u_flag[1]: what went in; u_flag[2]: what came out (a factorisation that failed leaves NaN behind, which is u_flag[0]'s to tell)
-    update_check_finite(c->u_S, K2, c->u_flag + 1, c->st);
-    update_check_finite(k.alpha_out, Kp, c->u_flag + 1, c->st);
-    HIPCHK(c, hipGetLastError());
-    int flags[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flags[1]) { c->err = "forget: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
-    if (flags[0]) { c->err = "forget: I - C^T C is not positive definite: these rows were not in this fit"; return SCFGP_ENOTPD; }
-    if (flags[2]) { c->err = "forget: the downdated factors are not finite"; return SCFGP_ENONFINITE; }
-    if (mu) {
-        // the operands predict would build from the returned factors: the typed Li'^T (over the old one) and alpha', zero-padded
-        DISPATCH(c, type_factor, c, c->u_S, c->u_LiT, nullptr);
-        HIPCHK(c, hipMemsetAsync(c->alpha_pred(), 0, sizeof(double) * Kp, c->st));
-        HIPCHK(c, hipMemcpyAsync(c->alpha_pred(), k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToDevice, c->st));
-        HIPCHK(c, hipMemsetAsync(acc, 0, sizeof(double) * 3, c->st));
-        OutRing ring;
-        if ((rc = ring.open(c))) return rc;
-        // the feed's jobs go on counting behind the first pass's (base nchunks), so its halves and events keep their order
-        auto slot = [&](int64_t i) { return c->f_out + (i & 1) * 2 * PRED_ROWS; };
-        auto download = [&](int64_t i) {
-            return ring.drain(i, [&]() -> int {
-                const int64_t t0 = jobs.row0(i), m = jobs.rows(i);
-                const double* o = slot(i);
-                HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-                HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-                return SCFGP_OK;
-            });
-        };
-        if ((rc = feed.upload(0, jobs, nchunks))) return rc;
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, jobs.rows(i));
-            const double *x, *yi;
-            if ((rc = feed.acquire(nchunks + i, &x, &yi))) return rc;
-            pack_chunk(c, g, x, yi, nullptr, c->u_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-            if ((rc = feed.release(nchunks + i))) return rc;
-            if ((rc = ring.acquire(i))) return rc;
-            double* o = slot(i);
-            if ((rc = DISPATCH(c, predict_chunk, c, g, c->u_LiT, o, o + PRED_ROWS))) return rc;
-            if (stats) forget_stats(o, o + PRED_ROWS, c->u_y, g.N, PRED_ROWS, rec, acc, c->st);
-            if ((rc = ring.computed(i))) return rc;
-            if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs, nchunks))) return rc;
-            if (i >= 1 && (rc = download(i - 1))) return rc;
-        }
-        if ((rc = download(nchunks - 1))) return rc;
-    }
-    double h_acc[6];
-    if (stats) HIPCHK(c, hipMemcpyAsync(h_acc, acc, sizeof(h_acc), hipMemcpyDeviceToHost, c->st));
-    if (alpha_out) {
-        update_store_factor(c->u_S, g0.K, g0.Kp, c->u_Si, c->st);          // S^-1 is done with: Li' in host layout
-        HIPCHK(c, hipMemcpyAsync(Li_out, c->u_Si, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (stats) {
-        stats[0] = (double)n; stats[1] = h_acc[0]; stats[2] = h_acc[1]; stats[3] = h_acc[2]; stats[4] = h_acc[4]; stats[5] = h_acc[5];
-        stats[6] = 1.0; stats[7] = 0.0;
-    }
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// exact leave-one-out / leave-block-out predictions of rows that are in the fit (loo.hip; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int LOO_MAX_BLOCK = 64;
-static int ensure_loo(scfgp_ctx* c) {
-    if (c->l_bad) return SCFGP_OK;
-    int rc;
-    if ((rc = dmalloc(c, &c->l_y, sizeof(double) * PRED_ROWS)) || (rc = dmalloc(c, &c->l_r, sizeof(double) * PRED_ROWS)) ||
-        (rc = dmalloc(c, &c->l_rec, sizeof(double) * 5 * PRED_ROWS)) || (rc = dmalloc(c, &c->l_out, sizeof(double) * 6 * PRED_ROWS)) ||
-        (rc = dmalloc(c, &c->l_acc, sizeof(double) * 8)) || (rc = dmalloc(c, &c->l_bad, sizeof(unsigned long long) * 2)))
-        return rc;
-    return SCFGP_OK;
-}
-
-// The chunk pipeline (RowFeed, OutRing) with the targets behind the rows of their chunk; resident rows bypass the feed and are read
-// where they lie (d_Xraw / d_yraw, never the evaluation's working set).  Per chunk C = Phi_I Li^T, the residual and the block kernel.  A
-// chunk holds floor(32768 / block) whole blocks, so no block straddles two chunks.  mu | std | lev leave through the two halves of
-// l_out; the stats and the flags are fetched once, at the end.
-extern "C" int scfgp_loo(scfgp_ctx* c, const double* X, const double* y, int64_t n, const double* alpha, const double* Li, int mode,
-                         int block, double* mu, double* sd, double* lev, double* stats) {
-    if (!c) return SCFGP_EARG;
-    const bool resident = !X && !y;
-    if ((!X) != (!y) || !alpha || !Li || !mu || !sd || mode < 0 || mode > 1) { c->err = "loo: bad arguments"; return SCFGP_EARG; }
-    if (block < 1 || block > LOO_MAX_BLOCK) { c->err = "loo: block must lie in 1..64"; return SCFGP_EARG; }
-    if (resident) {
-        if (mode != 0) { c->err = "loo: resident rows are scaled rows (mode must be 0)"; return SCFGP_EARG; }
-        if (!c->have_data || c->Nstore < 1) { c->err = "loo: no resident rows (scfgp_set_data)"; return SCFGP_EARG; }
-        n = c->Nstore;
-    }
-    if (n < 1) { c->err = "loo: n must be at least 1"; return SCFGP_EARG; }
-    int rc;
-    if ((rc = need_model({c, "loo"}, mode == 1))) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    const int64_t CH = PRED_ROWS / block * block;               // rows per chunk: whole blocks
-    const RowJobs jobs = {X, y, n, CH};
-    const int64_t nchunks = jobs.count();
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    if ((rc = ensure_loo(c))) return rc;
-    RowFeed feed; OutRing ring;                                   // Li in host layout / two chunks of [X | y] (resident rows: Li only)
-    if ((rc = feed.open(c, resident ? 0 : PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
-    const unsigned long long bad0[2] = {0ull, ~0ull};
-    HIPCHK(c, hipMemsetAsync(c->l_acc, 0, sizeof(double) * 8, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->l_bad, bad0, sizeof(bad0), hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = ring.open(c))) return rc;
-    auto slot = [&](int64_t i) { return c->l_out + (i & 1) * 3 * PRED_ROWS; };
-    auto download = [&](int64_t i) {
-        return ring.drain(i, [&]() -> int {
-            const int64_t t0 = jobs.row0(i), m = jobs.rows(i);
-            const double* o = slot(i);
-            HIPCHK(c, hipMemcpyAsync(mu + t0, o, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-            HIPCHK(c, hipMemcpyAsync(sd + t0, o + PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-            if (lev) HIPCHK(c, hipMemcpyAsync(lev + t0, o + 2 * PRED_ROWS, sizeof(double) * m, hipMemcpyDeviceToHost, c->copy_st));
-            return SCFGP_OK;
-        });
-    };
-    if (!resident && (rc = feed.upload(0, jobs))) return rc;    // resident rows are read where they lie: nothing is uploaded
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const int64_t t0 = jobs.row0(i);
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        if (resident) {
-            pack_chunk(c, g, c->d_Xraw + t0 * g0.D, c->d_yraw + t0, nullptr, c->l_y);
-        } else {
-            const double *xi, *yi;
-            if ((rc = feed.acquire(i, &xi, &yi))) return rc;
-            pack_chunk(c, g, xi, yi, nullptr, c->l_y, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-            if ((rc = feed.release(i))) return rc;
-        }
-        if ((rc = ring.acquire(i))) return rc;
-        double* o = slot(i);
-        if ((rc = DISPATCH(c, loo_chunk, c, g, LiT, block, t0 / block, o, o + PRED_ROWS, o + 2 * PRED_ROWS))) return rc;
-        if ((rc = ring.computed(i))) return rc;
-        if (!resident && i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-        if (i >= 1 && (rc = download(i - 1))) return rc;
-    }
-    if ((rc = download(nchunks - 1))) return rc;
-    double acc[8]; unsigned long long bad[2];
-    HIPCHK(c, hipMemcpyAsync(acc, c->l_acc, sizeof(acc), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(bad, c->l_bad, sizeof(bad), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (bad[0]) { c->err = "loo: non-finite rows, targets or factors"; return SCFGP_ENONFINITE; }
-    if (bad[1] != ~0ull) {
-        const long long j = (long long)bad[1];
-        c->err = "loo: I - H of block " + std::to_string(j) + " (rows " + std::to_string(j * block) + ".." +
-                 std::to_string(std::min<long long>((j + 1) * block, n) - 1) + ") is not positive definite: these rows are not in the fit";
-        return SCFGP_ENOTPD;
-    }
-    if (stats) {
-        stats[0] = (double)n; stats[1] = acc[0]; stats[2] = acc[1]; stats[3] = acc[2]; stats[4] = acc[3]; stats[5] = acc[4];
-        stats[6] = (double)((n + block - 1) / block); stats[7] = 0.0;
-    }
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// posterior covariance of the input gradient (gradcov.hip; derivation and promises in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int GRADCOV_MAX_Q = 64;                          // a point's q rows lie in one 64-row group of the block kernel
-static constexpr int64_t GRADCOV_SLOT_BYTES = (int64_t)64 << 20;  // per-point D x D arrays of a chunk (a dcov slot, the records)
-// points per chunk (the formula of the header): whole groups of (64 / q) points in the 32 768-row chunk buffers and, where a chunk
-// carries a D x D array per point, no more points than the slot budget holds
-static int64_t gradcov_points(const Geom& g, bool want_cov) {
-    const int q = std::min(g.D, g.S), ppg = 64 / q;
-    int64_t np = PRED_ROWS / (ppg * q) * ppg;
-    if (want_cov) np = std::min(np, std::max<int64_t>(1, GRADCOV_SLOT_BYTES / (8 * (int64_t)g.D * g.D)));
-    return np;
-}
-// The chunk pipeline (RowFeed, OutRing) with the weights behind the rows of their chunk.  dmu | dvar | dcov of a chunk leave through the
-// two slots of `stage`; the records and the running D x D sums stay on the device, the sums are fetched once, at the end.
-extern "C" int scfgp_predict_gradcov(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
-                                     int mode, double* dmu, double* dvar, double* dcov, double* asub) {
-    if (!c) return SCFGP_EARG;
-    if (!Xs || !alpha || !Li || T < 1 || mode < 0 || mode > 1) { c->err = "predict_gradcov: bad arguments"; return SCFGP_EARG; }
-    if (!dmu && !dvar && !dcov && !asub) { c->err = "predict_gradcov: no output requested"; return SCFGP_EARG; }
-    const Fail fail = {c, "predict_gradcov"};
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    const Geom& g0 = c->g;
-    const int D = g0.D, q = std::min(g0.D, g0.S);
-    if (q > GRADCOV_MAX_Q) return fail.arg("min(D, S) must be at most 64");
-    double sw = (double)T;
-    if (asub && w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_bad() >= 0) return fail.arg("weight " + std::to_string(ws.first_bad()) + " is negative or not finite");
-        sw = ws.sum;
-        if (!(sw > 0.0)) return fail.arg("the weights sum to zero");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/predict_gradcov_time.py)
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_grad(c, false))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    const bool feed_w = asub && w;
-    const int xmode = mode == 1 ? c->xs_mode : 0;
-    const int64_t DD = (int64_t)D * D;
-    const RowJobs jobs = {Xs, feed_w ? w : nullptr, T, gradcov_points(g0, dcov || asub)};
-    const int64_t nchunks = jobs.count(), rows = std::min(T, jobs.CH);
-    const int64_t slot_len = rows * D * 2 + (dcov ? rows * DD : 0);
-    RowFeed feed; OutRing ring; DevTmp qt, gfac, stage, rec, acc;  // Li / two chunks of [Xs | w] | Q | g_t | two slots | records | sums
-    if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
-    if ((rc = dmalloc(c, &qt.p, c->tsize() * q * g0.Jp))) return rc;
-    if (xmode && (rc = dmalloc(c, &gfac.p, sizeof(double) * rows * D))) return rc;
-    if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * slot_len))) return rc;
-    if (asub && ((rc = dmalloc(c, &rec.p, sizeof(double) * rows * DD)) || (rc = dmalloc(c, &acc.p, sizeof(double) * DD)))) return rc;
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
-    DISPATCH(c, grad_operand, c);
-    DISPATCH(c, gradcov_basis, c, qt.p);
-    if (asub) HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * DD, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = ring.open(c))) return rc;
-    auto slot_dmu = [&](int64_t i) { return stage + (i & 1) * slot_len; };
-    auto slot_dvar = [&](int64_t i) { return stage + (i & 1) * slot_len + rows * D; };
-    auto slot_dcov = [&](int64_t i) { return stage + (i & 1) * slot_len + 2 * rows * D; };
-    auto download = [&](int64_t i) {
-        return ring.drain(i, [&]() -> int {
-            const int64_t t0 = jobs.row0(i), n = jobs.rows(i);
-            if (dmu) HIPCHK(c, hipMemcpyAsync(dmu + t0 * D, slot_dmu(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
-            if (dvar) HIPCHK(c, hipMemcpyAsync(dvar + t0 * D, slot_dvar(i), sizeof(double) * n * D, hipMemcpyDeviceToHost, c->copy_st));
-            if (dcov) HIPCHK(c, hipMemcpyAsync(dcov + t0 * DD, slot_dcov(i), sizeof(double) * n * DD, hipMemcpyDeviceToHost, c->copy_st));
-            return SCFGP_OK;
-        });
-    };
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double *x, *wi;
-        if ((rc = feed.acquire(i, &x, &wi))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
-        if ((rc = ring.acquire(i))) return rc;
-        // the raw rows and the weights stay in the feed's half until the block kernel has read them
-        if ((rc = DISPATCH(c, gradcov_chunk, c, g, LiT, qt.p, x, xmode, gfac.p, feed_w ? wi : nullptr, slot_dmu(i), dvar ? slot_dvar(i) : nullptr,
-                           dcov ? slot_dcov(i) : nullptr, rec.p, acc.p)))
-            return rc;
-        if ((rc = feed.release(i))) return rc;
-        if ((rc = ring.computed(i))) return rc;
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-        if (i >= 1 && (rc = download(i - 1))) return rc;
-    }
-    if ((rc = download(nchunks - 1))) return rc;
-    std::vector<double> sums;
-    if (asub) {
-        sums.resize(DD);
-        HIPCHK(c, hipMemcpyAsync(sums.data(), acc.p, sizeof(double) * DD, hipMemcpyDeviceToHost, c->st));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (asub)                                                     // one division per entry of the lower triangle, mirrored
-        for (int d = 0; d < D; ++d)
-            for (int e = 0; e <= d; ++e) asub[(int64_t)d * D + e] = asub[(int64_t)e * D + d] = sums[(int64_t)d * D + e] / sw;
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// partial dependence and ICE curves over a pool (pd.hip; derivation and promises in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int PD_MAX_G = SAMPLE_MAX;                       // the ICE block is sample_product's shape
-static constexpr int64_t PD_RECORD_BYTES = GRADCOV_SLOT_BYTES;    // block records of one launch of the sums kernel
-// Two passes of the chunk pipeline.  The first (pd, pd_sd or pd_cov wanted) feeds [Xs | w] and leaves the running sums of the zeroed-column
-// features on the device, the dimensions in groups whose block records fit PD_RECORD_BYTES; the sums are checked, then the curves come
-// from the stacked mean rows in groups of dimensions that fit the chunk buffers.  The second (ice wanted) feeds Xs again and sends one
-// T_chunk x G block per (chunk, dimension) through the two slots of an OutRing.  No output is written before the last refusal is past.
-extern "C" int scfgp_predict_pd(scfgp_ctx* c, const double* Xs, int64_t T, const double* w, const double* alpha, const double* Li,
-                                const int* dims, int ndim, const double* grid, int G, int mode, double* pd, double* pd_sd, double* pd_cov,
-                                double* ice) {
-    if (!c) return SCFGP_EARG;
-    if (!Xs || !alpha || !Li || !dims || !grid) { c->err = "predict_pd: bad arguments"; return SCFGP_EARG; }
-    if (!pd && !pd_sd && !pd_cov && !ice) { c->err = "predict_pd: no output requested"; return SCFGP_EARG; }
-    const Geom& g0 = c->g;
-    const int D = g0.D;
-    if (T < 1) { c->err = "predict_pd: T must be at least 1"; return SCFGP_EARG; }
-    if (G < 1 || G > PD_MAX_G) { c->err = "predict_pd: G must lie in 1..1024"; return SCFGP_EARG; }
-    if (ndim < 1 || ndim > D) { c->err = "predict_pd: ndim must lie in 1..D"; return SCFGP_EARG; }
-    if (mode < 0 || mode > 1) { c->err = "predict_pd: bad mode"; return SCFGP_EARG; }
-    {
-        std::vector<char> seen(D, 0);
-        for (int a = 0; a < ndim; ++a) {
-            if (dims[a] < 0 || dims[a] >= D) { c->err = "predict_pd: dimension " + std::to_string(dims[a]) + " is out of range"; return SCFGP_EARG; }
-            if (seen[dims[a]]) { c->err = "predict_pd: dimension " + std::to_string(dims[a]) + " is given twice"; return SCFGP_EARG; }
-            seen[dims[a]] = 1;
-        }
-    }
-    const Fail fail = {c, "predict_pd"};
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    double W = (double)T;
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        W = ws.sum;
-        if (ws.first_nonfinite >= 0 || !std::isfinite(W)) return fail.nonfinite("non-finite weights");
-        if (!ws.positive) return fail.arg("no row has a positive weight");
-    }
-    const int xmode = mode == 1 ? c->xs_mode : 0;
-    const int64_t NG = (int64_t)ndim * G;
-    if (!xmode)
-        for (int64_t e = 0; e < NG; ++e)
-            if (!std::isfinite(grid[e])) return fail.nonfinite("non-finite grid value");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->prof) { c->recs.clear(); c->pool_used = 0; }          // timings describe this call's chunks (tools/pd_time.py)
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    const bool curves = pd || pd_sd || pd_cov;
-    const RowJobs jobs = {Xs, w, T, PRED_ROWS}, rows_only = {Xs, nullptr, T, PRED_ROWS};      // pass 1 | pass 2
-    const int64_t rows = std::min<int64_t>(T, PRED_ROWS), nchunks = jobs.count(), Jp2 = 2 * (int64_t)g0.Jp;
-    const int Gp = pd_grid_rows(G);
-    DevTmp d_dims, d_grid, wchunk;                                // dims | the (transformed) grid | w of the chunk, padded
-    if ((rc = dmalloc(c, &d_dims.p, sizeof(int) * ndim))) return rc;
-    if ((rc = dmalloc(c, &d_grid.p, sizeof(double) * NG))) return rc;
-    if (w && curves && (rc = dmalloc(c, &wchunk.p, sizeof(double) * PRED_ROWS))) return rc;
-    const int* dv = (const int*)d_dims.p;
-    HIPCHK(c, hipMemcpyAsync(d_dims.p, dims, sizeof(int) * ndim, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemcpyAsync(d_grid.p, grid, sizeof(double) * NG, hipMemcpyHostToDevice, c->st));
-    if (xmode) {
-        std::vector<double> hg(NG);
-        pd_grid(d_grid, dv, ndim, G, D, xmode, c->d_xscale, c->st);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(hg.data(), d_grid.p, sizeof(double) * NG, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        for (int64_t e = 0; e < NG; ++e)
-            if (!std::isfinite(hg[e])) { c->err = "predict_pd: non-finite grid value after the X scaler"; return SCFGP_ENONFINITE; }
-    }
-    RowFeed feed;                                                 // Li / two chunks of [Xs | w], for both passes
-    if ((rc = feed.open(c, PRED_ROWS * (D + 1), (int64_t)g0.K * g0.K))) return rc;
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, pad_square, true, alpha, &LiT))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    std::vector<double> h_pd, h_sd;
-    if (curves) {
-        // ---- pass 1: the running sums, ndim x 2 x Jp ----
-        const Geom gmax = chunk_geom(g0, rows);
-        int ngs = (int)std::min<int64_t>(ndim, std::max<int64_t>(1, PD_RECORD_BYTES / (int64_t)sizeof(double) / pd_record_len(gmax, 1)));
-        if (c->test_pd_group > 0) ngs = std::min(ngs, c->test_pd_group);
-        DevTmp rec, acc, flag;
-        if ((rc = dmalloc(c, &rec.p, sizeof(double) * pd_record_len(gmax, ngs)))) return rc;
-        if ((rc = dmalloc(c, &acc.p, sizeof(double) * ndim * Jp2))) return rc;
-        if ((rc = dmalloc(c, &flag.p, sizeof(int) * 4))) return rc;
-        HIPCHK(c, hipMemsetAsync(acc.p, 0, sizeof(double) * ndim * Jp2, c->st));
-        HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int) * 4, c->st));
-        if ((rc = feed.upload(0, jobs))) return rc;
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, jobs.rows(i));
-            const double *x, *wraw;
-            if ((rc = feed.acquire(i, &x, &wraw))) return rc;
-            pack_chunk(c, g, x, w ? wraw : nullptr, nullptr, wchunk.p, xmode, c->d_xscale);
-            if ((rc = feed.release(i))) return rc;
-            for (int a0 = 0; a0 < ndim; a0 += ngs)
-                if ((rc = DISPATCH(c, pd_sums_chunk, c, g, wchunk.p, dv + a0, std::min(ngs, ndim - a0), rec.p, acc + a0 * Jp2))) return rc;
-            if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-        }
-        update_check_finite(acc, ndim * Jp2, (int*)flag.p, c->st);
-        int hflag[4];
-        HIPCHK(c, hipMemcpyAsync(hflag, flag.p, sizeof(hflag), hipMemcpyDeviceToHost, c->st));
-        HIPCHK(c, hipStreamSynchronize(c->copy_st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        HIPCHK(c, hipGetLastError());
-        if (hflag[1]) { c->err = "predict_pd: non-finite weighted sum of the features"; return SCFGP_ENONFINITE; }
-        // ---- the curves: groups of dimensions whose stacked rows fit the chunk buffers ----
-        int ngc = (int)std::min<int64_t>(ndim, PRED_ROWS / Gp);
-        if (c->test_pd_group > 0) ngc = std::min(ngc, c->test_pd_group);
-        const int64_t GG = (int64_t)G * G;
-        DevTmp cur, stage; OutRing ring;                          // pd | scratch | sd of a group | two slots of G x G
-        if ((rc = dmalloc(c, &cur.p, sizeof(double) * 3 * PRED_ROWS))) return rc;
-        if (pd_cov && (rc = dmalloc(c, &stage.p, sizeof(double) * 2 * GG))) return rc;
-        if ((rc = ring.open(c))) return rc;
-        h_pd.resize(NG); h_sd.resize(NG);
-        int64_t nslot = 0, prev = 0;
-        auto download = [&](int64_t k, int64_t a) {
-            return ring.drain(k, [&]() -> int {
-                HIPCHK(c, hipMemcpyAsync(pd_cov + a * GG, stage + (k & 1) * GG, sizeof(double) * GG, hipMemcpyDeviceToHost, c->copy_st));
-                return SCFGP_OK;
-            });
-        };
-        for (int a0 = 0; a0 < ndim; a0 += ngc) {
-            const int ng = std::min(ngc, ndim - a0);
-            const Geom gr = chunk_geom(g0, (int64_t)ng * Gp);
-            if ((rc = DISPATCH(c, pd_curves, c, gr, LiT, acc + a0 * Jp2, W, dv + a0, d_grid + (int64_t)a0 * G, ng, G, cur.p, cur + PRED_ROWS,
-                               cur + 2 * PRED_ROWS)))
-                return rc;
-            HIPCHK(c, hipMemcpy2DAsync(h_pd.data() + (int64_t)a0 * G, sizeof(double) * G, cur.p, sizeof(double) * Gp, sizeof(double) * G, ng,
-                                       hipMemcpyDeviceToHost, c->st));
-            HIPCHK(c, hipMemcpy2DAsync(h_sd.data() + (int64_t)a0 * G, sizeof(double) * G, cur + 2 * PRED_ROWS, sizeof(double) * Gp,
-                                       sizeof(double) * G, ng, hipMemcpyDeviceToHost, c->st));
-            if (pd_cov)
-                for (int a = 0; a < ng; ++a, ++nslot) {
-                    if ((rc = ring.acquire(nslot))) return rc;
-                    if ((rc = DISPATCH(c, pd_cov_dim, c, a, G, stage + (nslot & 1) * GG))) return rc;
-                    if ((rc = ring.computed(nslot))) return rc;
-                    if (nslot >= 1 && (rc = download(nslot - 1, prev))) return rc;
-                    prev = a0 + a;
-                }
-            // the copies out of cur and predcov's reads of p_C are on the context's stream, ahead of the next group's kernels
-        }
-        if (pd_cov && nslot >= 1 && (rc = download(nslot - 1, prev))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->copy_st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        HIPCHK(c, hipGetLastError());
-    }
-    if (ice) {
-        // ---- pass 2: one T_chunk x G block per (chunk, dimension) ----
-        OutRing ring; DevTmp stage, R, keep;                      // two blocks | the rotated weights | the saved column
-        // The rows go through the feed of pass 1 again.  Both streams have drained, so its events are all past; the jobs go on from an
-        // even number, so that the halves alternate as before and a wait for reuse meets a recorded (or never used) event.
-        const int64_t j0 = curves ? (nchunks + 1) / 2 * 2 : 0;
-        if ((rc = dmalloc(c, &stage.p, sizeof(double) * 2 * rows * G))) return rc;
-        if ((rc = dmalloc(c, &R.p, c->tsize() * sample_w_rows(g0.K) * sample_w_cols(G)))) return rc;
-        if ((rc = dmalloc(c, &keep.p, sizeof(double) * PRED_ROWS))) return rc;
-        if ((rc = ring.open(c))) return rc;
-        auto slot = [&](int64_t k) { return stage + (k & 1) * rows * G; };
-        auto download = [&](int64_t k) {
-            const int64_t i = k / ndim, a = k % ndim;
-            return ring.drain(k, [&]() -> int {
-                HIPCHK(c, hipMemcpyAsync(ice + (a * T + jobs.row0(i)) * G, slot(k), sizeof(double) * jobs.rows(i) * G, hipMemcpyDeviceToHost,
-                                         c->copy_st));
-                return SCFGP_OK;
-            });
-        };
-        if ((rc = feed.upload(0, rows_only, j0))) return rc;
-        int64_t k = 0;
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const Geom g = chunk_geom(g0, jobs.rows(i));
-            const double* x;
-            if ((rc = feed.acquire(j0 + i, &x))) return rc;
-            pack_chunk(c, g, x, nullptr, nullptr, nullptr, xmode, c->d_xscale);
-            if ((rc = feed.release(j0 + i))) return rc;
-            for (int a = 0; a < ndim; ++a, ++k) {
-                if ((rc = ring.acquire(k))) return rc;
-                if ((rc = DISPATCH(c, pd_ice_chunk, c, g, dims[a], d_grid + (int64_t)a * G, G, R.p, keep.p, slot(k)))) return rc;
-                if ((rc = ring.computed(k))) return rc;
-                if (a == 0 && i + 1 < nchunks && (rc = feed.upload(i + 1, rows_only, j0))) return rc;
-                if (k >= 1 && (rc = download(k - 1))) return rc;
-            }
-        }
-        if ((rc = download(k - 1))) return rc;
-        HIPCHK(c, hipStreamSynchronize(c->copy_st));
-        HIPCHK(c, hipStreamSynchronize(c->st));
-        HIPCHK(c, hipGetLastError());
-    }
-    if (pd) memcpy(pd, h_pd.data(), sizeof(double) * NG);
-    if (pd_sd) memcpy(pd_sd, h_sd.data(), sizeof(double) * NG);
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// closed-form Sobol indices under a product measure (sobol.hip; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int SOBOL_MAX_NW = SAMPLE_MAX;
-static constexpr int64_t SOBOL_RECORD_BYTES = GRADCOV_SLOT_BYTES;  // the workgroups' records of one pass over a block of columns
-// No rows, no factors, no scaler: the tables from Fall / Scal, then the columns of W in passes whose records fit SOBOL_RECORD_BYTES.  The
-// schedule of the pair kernel (api_host.h) depends on J and D only, so a column has one summation order whatever nw is.
-extern "C" int scfgp_sobol(scfgp_ctx* c, const int32_t* kind, const double* p0, const double* p1, const double* W, int nw, double* f0,
-                           double* V, double* Vmain, double* Vtot, double* phibar) {
-    if (!c) return SCFGP_EARG;
-    const Fail f = {c, "sobol"};
-    const Geom& g = c->g;
-    const int D = g.D, J = g.J, K = g.K;
-    const bool cols = f0 || V || Vmain || Vtot;
-    if (!p0 || !p1) return f.arg("p0 and p1 are needed");
-    if (!cols && !phibar) return f.arg("no output asked for");
-    if (cols && !W) return f.arg("W is needed for f0, V, Vmain and Vtot");
-    if (cols && (nw < 1 || nw > SOBOL_MAX_NW)) return f.arg("nw must lie in 1..1024");
-    if (int d = sobol_first_bad_kind(kind, D); d >= 0) return f.arg("kind[" + std::to_string(d) + "] must be 0 (uniform) or 1 (normal)");
-    if (int d = sobol_first_bad_range(kind, p0, p1, D); d >= 0)
-        return f.arg("input " + std::to_string(d) + (kind && kind[d] == 1 ? ": p1 (the standard deviation) is negative" : ": p1 < p0 on a uniform input"));
-    if (int rc = need_model(f, false)) return rc;
-    if (int d = sobol_first_nonfinite(p0, p1, D); d >= 0) return f.nonfinite("non-finite measure at input " + std::to_string(d));
-    if (cols)
-        for (int64_t i = 0; i < (int64_t)K * nw; ++i)
-            if (!std::isfinite(W[i])) return f.nonfinite("non-finite W");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!cols) nw = 0;
-
-    const int Jt = (int)round_up(J, SOBOL_T), nb = Jt / SOBOL_T, nsets = 1 + 2 * D;
-    const int flags = (V || Vtot ? 1 : 0) | (Vmain ? 2 : 0) | (Vtot ? 4 : 0);
-    std::vector<int> units;
-    int pass = 0;
-    if (flags) {
-        sobol_units(nb, sobol_kseg(nb, nsets, SOBOL_COLS, SOBOL_RECORD_BYTES), units);
-        pass = std::min<int>((int)round_up(nw, SOBOL_COLS), sobol_pass_cols((int64_t)units.size() / 3, nsets, SOBOL_COLS, SOBOL_RECORD_BYTES));
-    }
-    const int64_t nunits = (int64_t)units.size() / 3;
-    int G = std::min(D, SOBOL_GROUP);
-    if (c->test_sobol_group > 0) G = std::min(G, c->test_sobol_group);
-    // one allocation: meas | psi1 | Ed | E | Eb | phibar | W | A | f0 | sums | units | rec
-    const int64_t n_meas = 3 * D, n_tab = 2 * (int64_t)D * Jt, n_e = 2 * Jt, n_w = (int64_t)K * nw, n_a = 2 * (int64_t)Jt * nw,
-                  n_sums = (int64_t)nsets * nw, n_units = (3 * nunits + 1) / 2, n_rec = nunits * nsets * pass;
-    DevTmp buf;
-    if (int rc = dmalloc(c, &buf.p, sizeof(double) * (n_meas + 2 * n_tab + 2 * n_e + K + n_w + n_a + nw + n_sums + n_units + n_rec))) return rc;
-    double* d_meas = buf.p; double* d_psi1 = d_meas + n_meas; double* d_Ed = d_psi1 + n_tab; double* d_E = d_Ed + n_tab;
-    double* d_Eb = d_E + n_e; double* d_phibar = d_Eb + n_e; double* d_W = d_phibar + K; double* d_A = d_W + n_w; double* d_f0 = d_A + n_a;
-    double* d_sums = d_f0 + nw; int* d_units = (int*)(d_sums + n_sums); double* d_rec = d_sums + n_sums + n_units;
-
-    std::vector<double> h(std::max<int64_t>(n_meas, K + nw + n_sums));
-    sobol_measure(kind, p0, p1, D, h.data());
-    HIPCHK(c, hipMemcpyAsync(d_meas, h.data(), sizeof(double) * n_meas, hipMemcpyHostToDevice, c->st));
-    if (cols) HIPCHK(c, hipMemcpyAsync(d_W, W, sizeof(double) * n_w, hipMemcpyHostToDevice, c->st));
-    if (nunits) HIPCHK(c, hipMemcpyAsync(d_units, units.data(), sizeof(int) * 3 * nunits, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));                      // h is reused for the results
-    { ProfScope ps(c, "sobol_tables"); sobol_tables(g, c->d_Fall, c->d_sc, d_meas, Jt, d_psi1, d_Ed, d_E, d_Eb, d_phibar, c->st); }
-    if (cols) { ProfScope ps(c, "sobol_weights"); sobol_weights(g, d_W, c->d_sc, d_E, Jt, nw, d_A, d_f0, c->st); }
-    for (int w0 = 0; flags && w0 < nw; w0 += pass) {
-        const int ncols = std::min(pass, nw - w0);
-        { ProfScope ps(c, "sobol_pairs");
-          sobol_pairs(g, c->d_Fall, d_meas, d_psi1, d_Ed, d_E, d_Eb, d_A, d_units, (int)nunits, Jt, nw, w0, ncols, G, flags, d_rec, c->st); }
-        { ProfScope ps(c, "sobol_reduce"); sobol_reduce(d_rec, (int)nunits, D, ncols, nw, w0, flags, d_sums, c->st); }
-    }
-    HIPCHK(c, hipGetLastError());
-    // phibar | f0 | sums are adjacent on the device only up to W and A in between: three copies
-    double* h_phibar = h.data(); double* h_f0 = h_phibar + K; double* h_sums = h_f0 + nw;
-    HIPCHK(c, hipMemcpyAsync(h_phibar, d_phibar, sizeof(double) * K, hipMemcpyDeviceToHost, c->st));
-    if (cols) HIPCHK(c, hipMemcpyAsync(h_f0, d_f0, sizeof(double) * nw, hipMemcpyDeviceToHost, c->st));
-    if (flags) HIPCHK(c, hipMemcpyAsync(h_sums, d_sums, sizeof(double) * n_sums, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (phibar) memcpy(phibar, h_phibar, sizeof(double) * K);
-    if (f0) memcpy(f0, h_f0, sizeof(double) * nw);
-    if (V) memcpy(V, h_sums, sizeof(double) * nw);
-    for (int w = 0; w < nw; ++w)
-        for (int d = 0; d < D; ++d) {
-            if (Vmain) Vmain[(int64_t)w * D + d] = h_sums[(int64_t)(1 + d) * nw + w];
-            if (Vtot) Vtot[(int64_t)w * D + d] = h_sums[w] - h_sums[(int64_t)(1 + D + d) * nw + w];
-        }
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// greedy maximum-information choice of m rows from a pool (select.hip; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int SELECT_MAX_M = 4096;
-static constexpr int64_t SELECT_MAX_T = (int64_t)1 << 20;
-static constexpr int SELECT_MAX_KP = 8192;                        // u_j lives in LDS as fp64: 64 KB dynamic beside the sweep's 128 B static
-                                                                  // (65 664 B: gfx950 launches it without an opt-in, tests/test_gpu_select_bounds.py)
-// The chunk pipeline (RowFeed) with the X scaler in mode 1; the chunk body is C = Phi_c Li^T, each chunk's C written to its place in a
-// T x Kp buffer that this call owns.  Then d = rowsum(C^2) and m picks, every one of them a handful of eager launches on the context's
-// stream (select.hip); the host waits once before the picks (for the non-finite flag of d) and once after them.  idx / var / gain are
-// fetched at the end, std_after leaves on the copy stream.
-extern "C" int scfgp_select(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Li, int m, int mode, int64_t* idx,
-                            double* var, double* gain, double* std_after) {
-    if (!c) return SCFGP_EARG;
-    if (!Xc || !Li || !idx || mode < 0 || mode > 1) { c->err = "select: bad arguments"; return SCFGP_EARG; }
-    if (T < 1 || T > SELECT_MAX_T) { c->err = "select: T must lie in 1..1048576"; return SCFGP_EARG; }
-    if (m < 1 || m > SELECT_MAX_M) { c->err = "select: m must lie in 1..4096"; return SCFGP_EARG; }
-    const Fail fail = {c, "select"};
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    if (c->g.Kp > SELECT_MAX_KP) return fail.arg("K above 8192 is not supported");
-    int64_t eligible = T;
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) return fail.nonfinite("non-finite rows, weights or factors");
-        eligible = ws.positive;
-    }
-    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp;
-    const size_t ts = c->tsize();
-    const RowJobs jobs = {Xc, nullptr, T, PRED_ROWS};
-    const int64_t nchunks = jobs.count();
-    // the last chunk's product writes whole 256-row blocks
-    const int64_t Crows = jobs.row0(nchunks - 1) + round_up(jobs.rows(nchunks - 1), 256);
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    RowFeed feed; DevTmp Cbuf, rows, picks;                       // Li / two chunks of X | C | w, d, std, partials | U, cp, a, part, idx, var, gain, flag
-    Events<1> sd_done;                                            // std_after is computed
-    if ((rc = feed.open(c, PRED_ROWS * g0.D, (int64_t)g0.K * g0.K))) return rc;
-    if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail.set("no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
-                        std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)", SCFGP_EHIP);
-    }
-    const int npart = select_partials(T), nlchunk = (m + 63) / 64;
-    const int64_t npp = round_up(npart, 8), mp = round_up(m, 8);
-    if ((rc = dmalloc(c, &rows.p, sizeof(double) * (3 * T + 2 * npp)))) return rc;
-    if ((rc = dmalloc(c, &picks.p, sizeof(double) * ((int64_t)m * Kp + Kp + (int64_t)nlchunk * Kp + 4 * mp + 8)))) return rc;
-    SelectBufs b;
-    b.Kp = (int)Kp; b.Trows = T;
-    b.w = rows; b.d = rows + T; double* d_sd = rows + 2 * T; b.pval = rows + 3 * T; b.pidx = (long long*)(rows + 3 * T + npp);
-    b.U = picks; b.cp = b.U + (int64_t)m * Kp; b.part = b.cp + Kp; b.a = b.part + (int64_t)nlchunk * Kp;
-    b.idx = (long long*)(b.a + mp); b.var = b.a + 2 * mp; b.gain = b.a + 3 * mp; b.flag = (int*)(b.a + 4 * mp);
-    HIPCHK(c, hipMemsetAsync(Cbuf.p, 0, ts * Crows * Kp, c->st));   // the product leaves the padding columns K.. as they are: zero
-    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
-    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
-    else select_ones(b.w, T, c->st);
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, update_load_factor, true, nullptr, &LiT))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = sd_done.create(c))) return rc;
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double* x;
-        if ((rc = feed.acquire(i, &x))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, (char*)Cbuf.p + ts * (size_t)jobs.row0(i) * Kp))) return rc;
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-    }
-    DISPATCH(c, pick_init, c, b, Cbuf.p);
-    HIPCHK(c, hipGetLastError());
-    int flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    for (int j = 0; j < m; ++j) DISPATCH(c, pick, c, b, Cbuf.p, j);
-    HIPCHK(c, hipGetLastError());
-    if (std_after) {
-        select_std(b, c->d_sc, d_sd, c->st);
-        HIPCHK(c, hipEventRecord(sd_done.e[0], c->st));
-    }
-    HIPCHK(c, hipMemcpyAsync(&flag, b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (flag) { c->err = "select: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    if (std_after) {
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, sd_done.e[0], 0));
-        HIPCHK(c, hipMemcpyAsync(std_after, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->copy_st));
-    }
-    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
-    if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    if (gain) HIPCHK(c, hipMemcpyAsync(gain, b.gain, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// greedy choice of m pool rows by integrated variance reduction (select.hip; derivation in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-static constexpr int SELECT_IV_MAX_KP = 4096;                     // u_j and v live in LDS as fp64: 64 KB
-// scfgp_select's pipeline with one more product per chunk: the chunks of the reference rows (their weights travel as the feed's
-// targets) go C = Phi_r Li^T -> packed C^T diag(omega) C, summed in fp64 over the chunks into Q; with Xr == NULL the pool's own chunks
-// do, in the pass that fills the pool's C.  Then d, a = rowsum((C Q) o C) and m picks of eager launches (select.hip); the host waits
-// once before the picks (for the non-finite flags) and once after them.
-extern "C" int scfgp_select_iv(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xr, int64_t R, const double* wr,
-                               const double* Li, int m, int mode, int64_t* idx, double* red, double* var, double* ivar, double* std_after) {
-    if (!c) return SCFGP_EARG;
-    if (!Xc || !Li || !idx || mode < 0 || mode > 1) { c->err = "select_iv: bad arguments"; return SCFGP_EARG; }
-    if (T < 1 || T > SELECT_MAX_T) { c->err = "select_iv: T must lie in 1..1048576"; return SCFGP_EARG; }
-    if (m < 1 || m > SELECT_MAX_M) { c->err = "select_iv: m must lie in 1..4096"; return SCFGP_EARG; }
-    if (Xr && R < 1) { c->err = "select_iv: R must be at least 1"; return SCFGP_EARG; }
-    const Fail fail = {c, "select_iv"};
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    if (c->g.Kp > SELECT_IV_MAX_KP) return fail.arg("K above 4096 is not supported");
-    const int64_t Rn = Xr ? R : T;
-    bool nonfinite = false;
-    int64_t eligible = T;
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) nonfinite = true;
-        eligible = ws.positive;
-    }
-    if (wr) {
-        const WeightScan ws = scan_weights(wr, Rn);
-        if (ws.first_negative >= 0) return fail.arg("negative reference weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) nonfinite = true;
-        if (!nonfinite && !ws.positive) return fail.arg("no reference row has a positive weight");
-    }
-    if (nonfinite) return fail.nonfinite("non-finite rows, weights or factors");
-    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    const int64_t Kp = g0.Kp, K2 = Kp * Kp;
-    const size_t ts = c->tsize();
-    // jobs 0 .. nref - 1: the chunks of the reference rows (their weights as targets); then the pool's, which carry wr where the pool is
-    // its own reference
-    const RowJobs ref = {Xr, wr, Xr ? R : 0, PRED_ROWS}, pool = {Xc, Xr ? nullptr : wr, T, PRED_ROWS};
-    const int64_t npool = pool.count(), nref = ref.count(), njobs = nref + npool;
-    const int64_t nqchunks = (Rn + PRED_ROWS - 1) / PRED_ROWS;
-    // the last chunk's product writes whole 256-row blocks
-    const int64_t Crows = pool.row0(npool - 1) + round_up(pool.rows(npool - 1), 256);
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    if ((rc = ensure_pred_factor(c))) return rc;
-    const int nts = (int)(Kp / g0.tile), ntiles = nts * (nts + 1) / 2;
-    {   // slabs of the widest split among the chunk shapes of the reference rows (full chunks and the ragged last one)
-        size_t need = 0;
-        for (int64_t np : {round_up(std::min<int64_t>(Rn, PRED_ROWS), 256), round_up(Rn - (nqchunks - 1) * PRED_ROWS, 256)})
-            need = std::max(need, sizeof(double) * (size_t)update_splits(c, np).nsplit * ((size_t)ntiles * g0.tile * g0.tile + Kp));
-        if ((rc = ensure_update(c, need))) return rc;
-    }
-    RowFeed feed; DevTmp Cbuf, Qbuf, rows, picks;                 // Li / two chunks of [X | omega] | C | Q, typed Q | per row | per pick
-    Events<1> sd_done;                                            // std_after is computed
-    if ((rc = feed.open(c, PRED_ROWS * (g0.D + 1), (int64_t)g0.K * g0.K))) return rc;
-    if (hipMalloc((void**)&Cbuf.p, ts * Crows * Kp) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail.set("no device memory for the pool's factor (" + std::to_string(Crows) + " x " + std::to_string(Kp) + " x " +
-                        std::to_string(ts) + " = " + std::to_string((unsigned long long)(ts * Crows * Kp)) + " bytes)", SCFGP_EHIP);
-    }
-    if ((rc = dmalloc(c, &Qbuf.p, (sizeof(double) + ts) * K2))) return rc;
-    const int npart = select_partials(T), nlchunk = (m + 63) / 64;
-    const int64_t npp = round_up(npart, 8), mp = round_up(m, 8), nat = select_iv_tiles((int)Kp);   // nat: the rows of apart
-    if ((rc = dmalloc(c, &rows.p, sizeof(double) * ((4 + nat) * T + 2 * npp)))) return rc;
-    if ((rc = dmalloc(c, &picks.p, sizeof(double) * ((int64_t)m * Kp + 3 * Kp + (int64_t)nlchunk * Kp + 5 * mp + 16)))) return rc;
-    SelectBufs b; SelectIvBufs iv;
-    b.Kp = (int)Kp; b.Trows = T;
-    b.w = rows; b.d = rows + T; double* d_sd = rows + 2 * T; iv.a = rows + 3 * T; iv.apart = rows + 4 * T;
-    b.pval = rows + (4 + nat) * T; b.pidx = (long long*)(b.pval + npp);
-    b.U = picks; b.cp = b.U + (int64_t)m * Kp; iv.h = b.cp + Kp; iv.v = iv.h + Kp; b.part = iv.v + Kp; b.a = b.part + (int64_t)nlchunk * Kp;
-    b.idx = (long long*)(b.a + mp); b.var = b.a + 2 * mp; b.gain = b.a + 3 * mp; iv.red = b.a + 4 * mp; iv.ivar = b.a + 5 * mp;
-    b.flag = (int*)(iv.ivar + 8);                                 // [0]: select.hip's bits, [1]: update_check_finite's
-    iv.Q = Qbuf;
-    void* Qt = (void*)(Qbuf.p + K2);
-    HIPCHK(c, hipMemsetAsync(Cbuf.p, 0, ts * Crows * Kp, c->st));   // the product leaves the padding columns K.. as they are: zero
-    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
-    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
-    else select_ones(b.w, T, c->st);
-    const void* LiT;
-    if ((rc = load_factor(c, feed, Li, update_load_factor, true, nullptr, &LiT))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));                     // raw is reused below
-    if ((rc = sd_done.create(c))) return rc;
-    auto upload = [&](int64_t job) { return job < nref ? feed.upload(job, ref) : feed.upload(job - nref, pool, nref); };
-    if ((rc = upload(0))) return rc;
-    int64_t nq = 0;                                               // chunks summed into Q so far
-    for (int64_t job = 0; job < njobs; ++job) {
-        const Geom g = chunk_geom(g0, job < nref ? ref.rows(job) : pool.rows(job - nref));
-        const bool in_q = job < nref || !Xr, weighted = in_q && wr;
-        const double *x, *om;
-        if ((rc = feed.acquire(job, &x, &om))) return rc;
-        pack_chunk(c, g, x, weighted ? om : nullptr, nullptr, weighted ? c->u_y : nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(job))) return rc;
-        void* Cj = job < nref ? c->p_C : (void*)((char*)Cbuf.p + ts * (size_t)((job - nref) * PRED_ROWS) * Kp);
-        if ((rc = DISPATCH(c, cov_factor_chunk, c, g, LiT, Cj))) return rc;
-        if (in_q) {
-            if ((rc = DISPATCH(c, iv_gram_chunk, c, g, update_splits(c, g.Np), Cj, weighted ? c->u_y : nullptr, nq == 0 ? c->u_acc : c->u_part)))
-                return rc;
-            if (nq > 0) update_accumulate(c->u_acc, c->u_part, c->n_pk, c->st);
-            ++nq;
-        }
-        if (job + 1 < njobs && (rc = upload(job + 1))) return rc;
-    }
-    // non-finite reference rows have reached Q by now; the pool's show in d and a
-    update_check_finite(c->u_acc, c->n_pk, b.flag, c->st);
-    unpack_tri_tiles(c->u_acc, nts, g0.tile, Qbuf, Kp, c->st);
-    DISPATCH(c, iv_init, c, b, iv, Cbuf.p, Qt);
-    HIPCHK(c, hipGetLastError());
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, b.flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flags[0] || flags[1]) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    for (int j = 0; j < m; ++j) DISPATCH(c, iv_pick, c, b, iv, Cbuf.p, j);
-    HIPCHK(c, hipGetLastError());
-    if (std_after) {
-        select_std(b, c->d_sc, d_sd, c->st);
-        HIPCHK(c, hipEventRecord(sd_done.e[0], c->st));
-    }
-    HIPCHK(c, hipMemcpyAsync(flags, b.flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    HIPCHK(c, hipGetLastError());
-    if (flags[0] || flags[1]) { c->err = "select_iv: non-finite rows, weights or factors"; return SCFGP_ENONFINITE; }
-    if (std_after) {
-        HIPCHK(c, hipStreamWaitEvent(c->copy_st, sd_done.e[0], 0));
-        HIPCHK(c, hipMemcpyAsync(std_after, d_sd, sizeof(double) * T, hipMemcpyDeviceToHost, c->copy_st));
-    }
-    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
-    if (red) HIPCHK(c, hipMemcpyAsync(red, iv.red, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    if (var) HIPCHK(c, hipMemcpyAsync(var, b.var, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    if (ivar) HIPCHK(c, hipMemcpyAsync(ivar, iv.ivar, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SCFGP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------
-// greedy Monte-Carlo batch expected improvement over a pool (selectqei.hip; formulas in include/scfgp_hip.h)
-// ----------------------------------------------------------------------------------------------
-// The pending rows go through sample_argmax_run (their per-sample best values are the start of m); the pool goes through scfgp_sample's
-// chunk body with each chunk's block written to its place in a T x nsamp buffer that this call owns.  Then m picks of two eager launches
-// each on the context's stream (selectqei.hip); the host waits once after the first sweep (for the non-finite flags) and once at the end.
-extern "C" int scfgp_select_qei(scfgp_ctx* c, const double* Xc, int64_t T, const double* w, const double* Xp, int64_t np, const double* alpha,
-                                const double* Li, int nsamp, uint64_t seed, double best, double xi, int m, int mode, int minimize,
-                                int64_t* idx, double* gain, double* score0, double* mstate, double* qei) {
-    if (!c) return SCFGP_EARG;
-    const Fail fail = {c, "select_qei"};
-    if (!Xc || !alpha || !Li || !idx) return fail.arg("NULL Xc, alpha, Li or idx");
-    if (T < 1 || T > SELECT_MAX_T) return fail.arg("T must lie in 1..1048576");
-    if (m < 1 || m > SELECT_MAX_M) return fail.arg("m must lie in 1..4096");
-    if (nsamp < 1 || nsamp > SAMPLE_MAX) return fail.arg("nsamp must lie in 1..1024");
-    if (mode < 0 || mode > 1) return fail.arg("mode must be 0 or 1 (there is no raw-y mode)");
-    if (np < 0) return fail.arg("np must not be negative");
-    if (np > 0 && !Xp) return fail.arg("np > 0 with NULL Xp");
-    int rc;
-    if ((rc = need_model(fail, mode == 1))) return rc;
-    bool nonfinite = !std::isfinite(best) || !std::isfinite(xi);
-    if (!nonfinite && xi < 0.0) return fail.arg("xi must not be negative");
-    int64_t eligible = T;
-    if (w) {
-        const WeightScan ws = scan_weights(w, T);
-        if (ws.first_negative >= 0) return fail.arg("negative weight at row " + std::to_string(ws.first_negative));
-        if (ws.first_nonfinite >= 0) nonfinite = true;
-        eligible = ws.positive;
-    }
-    if (nonfinite) return fail.nonfinite("non-finite best, xi or weights");
-    if (m > eligible) return fail.arg("m = " + std::to_string(m) + " but only " + std::to_string(eligible) + " rows have a positive weight");
-    HIPCHK(c, hipSetDevice(c->device));
-    const Geom& g0 = c->g;
-    if ((rc = ensure_pred_chunk(c))) return rc;
-    SampleW sw;
-    if ((rc = sample_weights_dev(c, alpha, Li, nsamp, seed, sw))) return rc;
-    RowFeed feed; DevTmp Fbuf, state;                             // two chunks of Xc | F | w, score0, m, records, idx, gain, qei, flag
-    if ((rc = feed.open(c, PRED_ROWS * g0.D))) return rc;
-    if (hipMalloc((void**)&Fbuf.p, sizeof(double) * T * nsamp) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail.set("no device memory for the pool's samples (" + std::to_string(T) + " x " + std::to_string(nsamp) + " x 8 = " +
-                        std::to_string((unsigned long long)(sizeof(double) * T * nsamp)) + " bytes)", SCFGP_EHIP);
-    }
-    const int64_t nblk = selectqei_blocks(T), mp = round_up(m, 8);
-    if ((rc = dmalloc(c, &state.p, sizeof(double) * (2 * T + nsamp + 2 * nblk + 2 * mp + 3)))) return rc;
-    SelectQeiBufs b;
-    b.F = Fbuf; b.T = T; b.nsamp = nsamp; b.sgn = minimize ? -1.0 : 1.0;
-    b.w = state; b.score0 = b.w + T; b.ms = b.score0 + T; b.pval = b.ms + nsamp; b.pidx = (long long*)(b.pval + nblk);
-    b.idx = (long long*)(b.pval + 2 * nblk); b.gain = b.pval + 2 * nblk + mp; b.qei = b.gain + mp; b.flag = (int*)(b.qei + 2);
-    HIPCHK(c, hipMemsetAsync(b.flag, 0, sizeof(double), c->st));
-    if (w) HIPCHK(c, hipMemcpyAsync(b.w, w, sizeof(double) * T, hipMemcpyHostToDevice, c->st));
-    else select_ones(b.w, T, c->st);
-    SampleArgmaxRun pend;                                         // the pending rows: every one of them is eligible
-    if (np > 0 && (rc = sample_argmax_run(c, Xp, np, nullptr, sw.wt.p, nsamp, mode == 1, minimize, pend))) return rc;
-    const RowJobs jobs = {Xc, nullptr, T, PRED_ROWS};
-    const int64_t nchunks = jobs.count();
-    if ((rc = feed.upload(0, jobs))) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        const Geom g = chunk_geom(g0, jobs.rows(i));
-        const double* x;
-        if ((rc = feed.acquire(i, &x))) return rc;
-        pack_chunk(c, g, x, nullptr, nullptr, nullptr, mode == 1 ? c->xs_mode : 0, c->d_xscale);
-        if ((rc = feed.release(i))) return rc;
-        if ((rc = DISPATCH(c, sample_chunk, c, g, sw.wt.p, nsamp, jobs.row0(i), seed, 0, -1, Fbuf + jobs.row0(i) * nsamp))) return rc;
-        if (i + 1 < nchunks && (rc = feed.upload(i + 1, jobs))) return rc;
-    }
-    const double base = b.sgn * best + xi;
-    selectqei_state(b, np > 0 ? pend.best.v() : nullptr, base, 1, c->st);
-    selectqei_sweep(b, 0, c->st);
-    HIPCHK(c, hipGetLastError());
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(&flags[0], b.flag, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    if (np > 0) HIPCHK(c, hipMemcpyAsync(&flags[1], pend.best.flag(), sizeof(int), hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->copy_st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    if (flags[0] || flags[1]) { c->err = "select_qei: a non-finite sampled value at an eligible or pending row"; return SCFGP_ENONFINITE; }
-    for (int j = 0; j < m; ++j) {
-        if (j) selectqei_sweep(b, j, c->st);
-        selectqei_commit(b, j, c->st);
-    }
-    selectqei_state(b, nullptr, base, 0, c->st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(idx, b.idx, sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->st));
-    if (gain) HIPCHK(c, hipMemcpyAsync(gain, b.gain, sizeof(double) * m, hipMemcpyDeviceToHost, c->st));
-    if (score0) HIPCHK(c, hipMemcpyAsync(score0, b.score0, sizeof(double) * T, hipMemcpyDeviceToHost, c->st));
-    if (mstate) HIPCHK(c, hipMemcpyAsync(mstate, b.ms, sizeof(double) * nsamp, hipMemcpyDeviceToHost, c->st));
-    if (qei) HIPCHK(c, hipMemcpyAsync(qei, b.qei, sizeof(double) * 2, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-    return SCFGP_OK;
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -179,7 +179,7 @@ def gram_tiles(Kp):
 
 
 def f16_chunk(Np, Kp, gram_chunk=4096):
-    """scfgp_api.hip f16_chunk(): rows per job of the fp16 Gram"""
+    """api_ctx.h f16_chunk(): rows per job of the fp16 Gram"""
     top = 2 * gram_chunk if gram_chunk > 0 else 8192
     fill = Np * gram_tiles(Kp) // 512 // 512 * 512
     return max(min(top, fill), 1024)

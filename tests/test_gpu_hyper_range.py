@@ -153,7 +153,7 @@ def point_ratios(name, ip, res, K):
 
 
 def _lrb_rule(eng, S, lowrank_bwd):
-    """the host rule (scfgp_api.hip: want_lrb) from dims(): does the gradient run the TZ / XU branches?"""
+    """the host rule (api_ctx.h: want_lrb) from dims(): does the gradient run the TZ / XU branches?"""
     d = eng.dims()
     Sp = -(-(S + 1) // 16) * 16
     fits = Sp < d['Dp'] and d['Jp'] + -(-S // 64) * 64 <= d['Kp']

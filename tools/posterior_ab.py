@@ -1,5 +1,5 @@
-"""Bit identity of the posterior entry points between two builds of the library (default: '_head', the parent commit's build made by
-tools/build_head.sh, and '', the working tree's).  For each variant in turn a fresh child process -- one on the GPU at a time, under a
+"""Bit identity of the posterior entry points and of the evaluation between two builds of the library (default: '_head', the parent
+commit's build made by tools/build_head.sh, and '', the working tree's).  For each variant in turn a fresh child process -- one on the GPU at a time, under a
 time limit of its own; this process never opens the GPU -- runs a fixed, seeded list of calls and writes a SHA-256 per output array.
 Then a table, and exit status 1 on any difference.  A child that fails or runs out of time ends the run.
 
@@ -15,7 +15,9 @@ with all five outputs for 40 sampled columns under a mixed measure (each of the 
 build produces are listed as new, not as different); with
 weights that are zero across every chunk boundary, at both shapes, sample_argmax in mode y with and without them, acquire in raw mode for
 its five kinds (ei with grad), acquire_kg symmetric and with Xr with the node table, select_iv with Xr and wr and as its own reference;
-at the second shape sample_grad with sidx, select_qei with pending rows and forget (a refusal is compared as its text).  With three
+at the second shape sample_grad with sidx, select_qei with pending rows and forget (a refusal is compared as its text).  Then the
+evaluation side, at both shapes: eval with gradient on the rows (cost, grad, alpha, Li) and three adam iterations of train (cost
+history, alpha, Li).  With three
 variants (_head,_head,) the first two runs tell which outputs are not bit-stable from run to run: those are marked, not compared.  The factors are a synthetic posterior (tools/select_time.py's): identity of the bits does not depend on their values.
 Usage: python tools/posterior_ab.py [--variants _head,] [--limit SECONDS]        (default limit: 300 per child)
        python tools/posterior_ab.py --child OUT.json                             (the list, in this process, on SCFGP_LIB_VARIANT)"""
@@ -151,6 +153,11 @@ def calls(D, S, M, n, dt):
                                                                    return_score0=True, return_state=True))
         for rows in (n, 64):                                    # most likely refused: these rows are not in the synthetic fit
             yield 'forget %d rows' % rows, attempt(lambda: eng.forget(X[:rows], y[:rows], alpha, Li, factors=True, predict=True))
+    # the evaluation side, last, so that the calls above run on the context as they always did
+    cost, grad, a1, L1 = eng.eval(X, y)
+    yield 'eval with gradient', (cost, grad, a1.copy(), L1.copy())
+    eng.opt_init('adam')
+    yield 'train 3 iterations', eng.train(3)
     eng.close()
 
 
