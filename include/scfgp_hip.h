@@ -543,6 +543,9 @@ int scfgp_predict_gradcov(scfgp_ctx* ctx, const double* Xs, int64_t T, const dou
  * There is no raw-y mode: the y scaler's backward transform is not affine, so a PD curve in raw y units is not Gaussian (the argument of
  * scfgp_predict_cov and scfgp_acquire).
  * Bounds: 1 <= G <= 1024 (the ICE block is the product of scfgp_sample), 1 <= ndim <= D, T >= 1 without limit.
+ * A grid value is a coordinate like a row's own and is not refused for its size: the curves rotate by g_i F_all[d][j] through the feature
+ * map's sin / cos (csrc/sincos.h), so they are right for |g_i F_all[d][j]| < 3.37e9 (2^31 pi/2) and carry a wrong quadrant beyond, as a
+ * row's own phase would.
  * Rows with w_t == 0 contribute nothing to the sums: their term is selected away, not multiplied by zero, so a non-finite row of weight 0
  * is not an error.  They still get their ice rows.
  * How it runs.  The rows go through in chunks of 32768, at most twice: once for the sums (pd, pd_sd or pd_cov wanted), once for ice.  The
@@ -604,8 +607,20 @@ int scfgp_predict_pd(scfgp_ctx* ctx, const double* Xs, int64_t T, const double* 
  * SCFGP_EARG (with a scfgp_last_error text "sobol: ...", before any device work, in this order) for a NULL p0 or p1; no output asked for;
  * W == NULL while f0, V, Vmain or Vtot is wanted; nw out of range (when W is used); a kind outside {0, 1}; p1 < p0 on a uniform input or
  * p1 < 0 on a normal one (the text names the first such input); parameters not set.  SCFGP_ENONFINITE for a non-finite p0, p1 or W.  The
- * outputs are untouched in both cases.  Out of scope: second-order and higher interaction indices, empirical marginals, dependent inputs,
- * raw-y units, a row-sharded form (there are no rows) and weights kept on the device between calls. */
+ * outputs are untouched in both cases.
+ * The domain of the measure.  Every phase goes through the feature map's sin / cos (csrc/sincos.h), which is exact to 0.77 * 2^-53 for
+ * |z| < 2^31 pi/2 = 3.37e9 and returns finite values with the wrong quadrant beyond.  The pair coefficients evaluate psi_d at Om[d][j] +-
+ * Om[d][k], twice the frequencies of the feature map, so the phases of input d reach
+ *     R_d = 2 max_j |Om[d][j]| (|p0 + p1| / 2 + (p1 - p0) / 2)  on a uniform input (the sinc takes a sine at (Om_j +- Om_k) (p1 - p0) / 2),
+ *     R_d = 2 max_j |Om[d][j]| |p0|                             on a normal one (its amplitude takes no sin / cos).
+ * A call with any R_d >= 3.37e9 is refused: SCFGP_EARG, "sobol: input d: the measure's phases leave the sin/cos domain (2 max|Om| |x| <
+ * 3.37e9)", naming the first such input (an index into the SCALED inputs, the d of kind, p0, p1), behind the refusals above and one small
+ * kernel that reads max_j |Om[d][j]| back, before any table, pair or output; it does not depend on which outputs are asked for.  An
+ * input whose frequencies are all zero passes whatever its measure; finite bounds of the order of DBL_MAX are refused wherever a
+ * frequency is not zero, they do not overflow.  Inside the domain the refusal changes no bit.
+ * Out of scope: second-order and higher interaction indices, empirical marginals, dependent inputs, raw-y units, a row-sharded form
+ * (there are no rows), weights kept on the device between calls, and pair phases formed as products of table values, which would widen
+ * the domain to the feature map's. */
 int scfgp_sobol(scfgp_ctx* ctx, const int32_t* kind, const double* p0, const double* p1, const double* W, int nw,
                 double* f0, double* V, double* Vmain, double* Vtot, double* phibar);
 

@@ -93,7 +93,8 @@ inline int sobol_first_nonfinite(const double* p0, const double* p1, int D) {
     return -1;
 }
 // meas (3 x D) as the kernels take it: kind | centre or mean | half width or standard deviation.  The halves are taken before the sum
-// and the difference, so bounds near DBL_MAX do not overflow.
+// and the difference, so bounds near DBL_MAX do not overflow here: the centre and the half width come out finite.  That says nothing
+// about the phases -- a measure that far out is refused by sobol_first_out_of_domain wherever its input has a nonzero frequency.
 inline void sobol_measure(const int32_t* kind, const double* p0, const double* p1, int D, double* meas) {
     for (int d = 0; d < D; ++d) {
         const bool normal = kind && kind[d] == 1;
@@ -101,6 +102,19 @@ inline void sobol_measure(const int32_t* kind, const double* p0, const double* p
         meas[D + d] = normal ? p0[d] : 0.5 * p0[d] + 0.5 * p1[d];
         meas[2 * D + d] = normal ? p1[d] : 0.5 * p1[d] - 0.5 * p0[d];
     }
+}
+// The domain of fast_sincos (sincos.h): |z| < 2^31 pi/2 = 3.373e9, stated as 3.37e9.  The pair kernel evaluates psi_d at Om[d][j] +-
+// Om[d][k], so the phases of input d reach R_d = 2 omax[d] (|centre| + half width) on a uniform input (the sinc takes its sine at
+// (Om_j +- Om_k) half width) and 2 omax[d] |mean| on a normal one, whose amplitude takes no sin / cos.  First input with R_d at or beyond
+// the limit, -1: none.  The two products are formed apart, so that an input with omax = 0 passes whatever its measure (0, never 0 x inf),
+// and a sum that overflows is +inf and refused.  meas as sobol_measure leaves it, omax (D) = max_j |Om[d][j]|, both finite.
+constexpr double SOBOL_PHASE_LIMIT = 3.37e9;
+inline int sobol_first_out_of_domain(const double* meas, const double* omax, int D) {
+    for (int d = 0; d < D; ++d) {
+        const double r = 2.0 * (omax[d] * std::fabs(meas[D + d]) + (meas[d] == 0.0 ? omax[d] * meas[2 * D + d] : 0.0));
+        if (!(r < SOBOL_PHASE_LIMIT)) return d;
+    }
+    return -1;
 }
 // The work units of the pair kernel: the blocks (jb, kb), jb <= kb < nb, of the upper triangle in row-major order, a row cut into runs
 // of at most kseg blocks; a unit is (jb, kb0, kb1).  A column's sum visits the units in this order, so the schedule may depend on the

@@ -616,12 +616,12 @@ extern "C" int scfgp_sobol(scfgp_ctx* c, const int32_t* kind, const double* p0, 
     const int64_t nunits = (int64_t)units.size() / 3;
     int G = std::min(D, SOBOL_GROUP);
     if (c->test_sobol_group > 0) G = std::min(G, c->test_sobol_group);
-    // one allocation: meas | psi1 | Ed | E | Eb | phibar | W | A | f0 | sums | units | rec
+    // one allocation: meas | omax | psi1 | Ed | E | Eb | phibar | W | A | f0 | sums | units | rec
     const int64_t n_meas = 3 * D, n_tab = 2 * (int64_t)D * Jt, n_e = 2 * Jt, n_w = (int64_t)K * nw, n_a = 2 * (int64_t)Jt * nw,
                   n_sums = (int64_t)nsets * nw, n_units = (3 * nunits + 1) / 2, n_rec = nunits * nsets * pass;
     DevTmp buf;
-    if (int rc = dmalloc(c, &buf.p, sizeof(double) * (n_meas + 2 * n_tab + 2 * n_e + K + n_w + n_a + nw + n_sums + n_units + n_rec))) return rc;
-    double* d_meas = buf.p; double* d_psi1 = d_meas + n_meas; double* d_Ed = d_psi1 + n_tab; double* d_E = d_Ed + n_tab;
+    if (int rc = dmalloc(c, &buf.p, sizeof(double) * (n_meas + D + 2 * n_tab + 2 * n_e + K + n_w + n_a + nw + n_sums + n_units + n_rec))) return rc;
+    double* d_meas = buf.p; double* d_omax = d_meas + n_meas; double* d_psi1 = d_omax + D; double* d_Ed = d_psi1 + n_tab; double* d_E = d_Ed + n_tab;
     double* d_Eb = d_E + n_e; double* d_phibar = d_Eb + n_e; double* d_W = d_phibar + K; double* d_A = d_W + n_w; double* d_f0 = d_A + n_a;
     double* d_sums = d_f0 + nw; int* d_units = (int*)(d_sums + n_sums); double* d_rec = d_sums + n_sums + n_units;
 
@@ -630,7 +630,14 @@ extern "C" int scfgp_sobol(scfgp_ctx* c, const int32_t* kind, const double* p0, 
     HIPCHK(c, hipMemcpyAsync(d_meas, h.data(), sizeof(double) * n_meas, hipMemcpyHostToDevice, c->st));
     if (cols) HIPCHK(c, hipMemcpyAsync(d_W, W, sizeof(double) * n_w, hipMemcpyHostToDevice, c->st));
     if (nunits) HIPCHK(c, hipMemcpyAsync(d_units, units.data(), sizeof(int) * 3 * nunits, hipMemcpyHostToDevice, c->st));
+    // the largest frequency of every input, read back with the same wait: the measure is held against the domain of sin / cos before
+    // any table or pair is formed
+    std::vector<double> h_omax(D);
+    sobol_omax(g, c->d_Fall, d_omax, c->st);
+    HIPCHK(c, hipMemcpyAsync(h_omax.data(), d_omax, sizeof(double) * D, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));                      // h is reused for the results
+    if (int d = sobol_first_out_of_domain(h.data(), h_omax.data(), D); d >= 0)
+        return f.arg("input " + std::to_string(d) + ": the measure's phases leave the sin/cos domain (2 max|Om| |x| < 3.37e9)");
     { ProfScope ps(c, "sobol_tables"); sobol_tables(g, c->d_Fall, c->d_sc, d_meas, Jt, d_psi1, d_Ed, d_E, d_Eb, d_phibar, c->st); }
     if (cols) { ProfScope ps(c, "sobol_weights"); sobol_weights(g, d_W, c->d_sc, d_E, Jt, nw, d_A, d_f0, c->st); }
     for (int w0 = 0; flags && w0 < nw; w0 += pass) {

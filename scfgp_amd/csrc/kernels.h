@@ -424,6 +424,8 @@ constexpr int SOBOL_GROUP = 16;                 // inputs per workgroup of the p
 // each; entries j >= J are not written), phibar (K, or NULL) = s (Re E | Im E)
 void sobol_tables(const Geom& g, const double* Fall, const Scal* sc, const double* meas, int Jt, double* psi1, double* Ed, double* E,
                   double* Eb, double* phibar, hipStream_t st);
+// omax (D) = max_j |Fall[d][j]|: with the measure it bounds every phase the tables and the pair kernel hand to fast_sincos
+void sobol_omax(const Geom& g, const double* Fall, double* omax, hipStream_t st);
 // W (K x nw, row-major) -> A (Jt x nw complex) = s (W[j] - i W[J + j]), zero rows from J on; f0 (nw, or NULL) = Re sum_j A_j E_j
 void sobol_weights(const Geom& g, const double* W, const Scal* sc, const double* E, int Jt, int nw, double* A, double* f0, hipStream_t st);
 // The centred quadratic forms of columns w0 .. w0 + ncols of A.  units (3 ints each: block of j, first and one-past-last block of k, blocks

@@ -11,6 +11,11 @@
 // (tests/test_sincos_ref.py, tests/test_gpu_phase_range.py): <= 0.77 * 2^-53 over the hard cases up to |fn| = 2^20 (multiples of
 // pi/2, quadrant flips, ties of rint) and no larger out to |z| = 1e9.  Branch-free; the library sincos carries a Payne-Hanek
 // path the phases of this model never need (|FF| is tens to hundreds of radians).
+// Call sites and the tests that drive each with chosen phases: the feature-map kernels of fmap.hip at every dispatch
+// (tests/test_gpu_phase_range.py); psi and sinc of sobol.hip in the tables and in the three product chains of the pair kernel
+// (tests/test_gpu_sobol_range.py; scfgp_sobol refuses a measure whose pair phases 2 max|Om| |x| would leave the domain); the
+// zeroed-column phases of pd_sums_kernel in the context's type and the grid rotations of pd_mean_rows_kernel and
+// pd_ice_weights_kernel of pd.hip (tests/test_gpu_pd_range.py; a grid value is not refused, the limit is |g F_all[d][j]| < 3.37e9).
 // --------------------------------------------------------------------------
 __device__ __forceinline__ void fast_sincos(double z, double& sn, double& cs) {
     const double fn = rint(z * 6.36619772367581382433e-01);              // 2/pi

@@ -83,6 +83,16 @@ __global__ __launch_bounds__(64) void sobol_tables_kernel(const double* __restri
     if (phibar) { phibar[j] = sc->s * e.re; phibar[J + j] = sc->s * e.im; }
 }
 
+// omax[d] = max_j |Fall[d][j]| over j < J, one wave per input: what scfgp_sobol holds the measure against before any psi is evaluated
+// (api_host.h: sobol_first_out_of_domain).  A maximum has no order, so the shuffle tree is no part of any summation.
+__global__ __launch_bounds__(64) void sobol_omax_kernel(const double* __restrict__ Fall, int J, int Jp, double* __restrict__ omax) {
+    const int d = blockIdx.x;
+    double m = 0.0;
+    for (int j = threadIdx.x; j < J; j += 64) m = fmax(m, fabs(Fall[(int64_t)d * Jp + j]));
+    for (int o = 32; o; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    if (threadIdx.x == 0) omax[d] = m;
+}
+
 // A (Jt x nw complex): a_j of every column, zero for j >= J; f0 (nw, or NULL) = Re sum_j a_j E_j in index order
 __global__ __launch_bounds__(256) void sobol_weights_kernel(const double* __restrict__ W, const Scal* __restrict__ sc,
                                                             const double* __restrict__ E, int J, int Jt, int nw, double* __restrict__ A,
@@ -264,6 +274,10 @@ void sobol_tables(const Geom& g, const double* Fall, const Scal* sc, const doubl
                   double* Eb, double* phibar, hipStream_t st) {
     hipLaunchKernelGGL(sobol_tables_kernel, dim3((unsigned)((g.J + 63) / 64)), dim3(64), 0, st, Fall, sc, meas, g.D, g.J, g.Jp, Jt, psi1, Ed,
                        E, Eb, phibar);
+}
+
+void sobol_omax(const Geom& g, const double* Fall, double* omax, hipStream_t st) {
+    hipLaunchKernelGGL(sobol_omax_kernel, dim3((unsigned)g.D), dim3(64), 0, st, Fall, g.J, g.Jp, omax);
 }
 
 void sobol_weights(const Geom& g, const double* W, const Scal* sc, const double* E, int Jt, int nw, double* A, double* f0, hipStream_t st) {

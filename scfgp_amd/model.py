@@ -317,7 +317,9 @@ class SCFGP(object):
         the range of the scaled training inputs, which any scaler allows.  Columns the scaler dropped get S = T = 0.  nsamples > 0 adds
         the posterior distribution of every index over that many exact draws of the weights (sample_weights with `seed`): 'S_samples',
         'T_samples' (nsamples, D_raw), 'V_samples', and 'S_mean', 'S_q05', 'S_q95', 'T_mean', 'T_q05', 'T_q95' (NaN-aware).  A function
-        whose variance is not above rounding level (1e-12 of its mean square) has no indices: NaN, not a division by zero."""
+        whose variance is not above rounding level (1e-12 of its mean square) has no indices: NaN, not a division by zero.
+        A measure so far out that its phases leave the domain of the feature map's sin / cos (2 max|Om| |x| >= 3.37e9 in SCALED units)
+        raises ValueError; the input that the text names is counted over the SCALED columns, those the X scaler kept, not the raw ones."""
         owner = self._owner('sobol')
         kind, p0, p1, scaled = self._measure('sobol', bounds, measure)
 

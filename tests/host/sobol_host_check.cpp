@@ -1,5 +1,5 @@
 // Stand-alone check of the host arithmetic that scfgp_sobol adds to scfgp_amd/csrc/api_host.h (plain C++17, no HIP): the scans of the
-// measure, its device form, and the schedule of the pair kernel -- every block (jb, kb) of the upper triangle in exactly one unit, in
+// measure, its device form, the test of its phases against the domain of sin / cos, and the schedule of the pair kernel -- every block (jb, kb) of the upper triangle in exactly one unit, in
 // row-major order, the run length and the columns per pass against the record budget.  Built and run by tests/test_sobol_host.py, plain
 // and under -fsanitize=address,undefined.
 #include "../../scfgp_amd/csrc/api_host.h"
@@ -44,6 +44,46 @@ static void check_measure() {
     CHECK(meas[0] == 0.0 && meas[1] == 1.0 && meas[2] == 2.0);
 }
 
+// the domain of sin / cos: R_d = 2 omax (|centre| + half width) or 2 omax |mean| against 3.37e9, the first input at or beyond it
+static void check_domain() {
+    const double two30 = 1073741824.0;
+    {   // the case that was found: centre 2.5 * 2^30, half width 1/8, max |Om| = 1 -> R = 5.4e9; 1.5 * 2^30 -> 3.2e9 passes
+        const double om[1] = {1.0};
+        double meas[3] = {0.0, 2.5 * two30, 0.125};
+        CHECK(sobol_first_out_of_domain(meas, om, 1) == 0);
+        meas[1] = 1.5 * two30; CHECK(sobol_first_out_of_domain(meas, om, 1) == -1);
+        meas[1] = -2.5 * two30; CHECK(sobol_first_out_of_domain(meas, om, 1) == 0);       // |centre|
+        meas[1] = two30; meas[2] = 0.0; CHECK(sobol_first_out_of_domain(meas, om, 1) == -1);     // R = 2^31 = 2.1e9
+        meas[2] = two30; CHECK(sobol_first_out_of_domain(meas, om, 1) == 0);               // R = 2^32: the half width counts
+    }
+    {   // either side of the limit, R formed exactly: omax = 1/2, so R = |centre| + half width
+        const double om[1] = {0.5};
+        double meas[3] = {0.0, 3.37e9, 0.0};
+        CHECK(sobol_first_out_of_domain(meas, om, 1) == 0);                                // R == limit is outside
+        meas[1] = std::nextafter(3.37e9, 0.0); CHECK(sobol_first_out_of_domain(meas, om, 1) == -1);
+        meas[1] = 3.37e9 - 1.0; meas[2] = 1.0; CHECK(sobol_first_out_of_domain(meas, om, 1) == 0);      // the half width counts ...
+        meas[0] = 1.0; CHECK(sobol_first_out_of_domain(meas, om, 1) == -1);                // ... on a uniform input only
+        meas[2] = 1e300; CHECK(sobol_first_out_of_domain(meas, om, 1) == -1);              // a normal's sd takes no sin / cos
+    }
+    {   // the first of several; an input without frequencies passes whatever its measure; the ends of the range refuse, never NaN
+        const double om[4] = {1.0, 0.0, 3.0, 1e-290};
+        const int32_t k[4] = {0, 0, 1, 0};
+        const double p0[4] = {0.0, -DBL_MAX / 2, 2e9, -DBL_MAX / 2}, p1[4] = {1.0, DBL_MAX / 2, 1.0, DBL_MAX / 2};
+        double meas[12];
+        sobol_measure(k, p0, p1, 4, meas);
+        CHECK(sobol_first_out_of_domain(meas, om, 4) == 2);                                // 2 * 3 * 2e9
+        const double p0b[4] = {0.0, 0.9 * DBL_MAX, 1e8, -DBL_MAX / 2};
+        const double p1b[4] = {1.0, DBL_MAX, 1.0, DBL_MAX / 2};
+        sobol_measure(k, p0b, p1b, 4, meas);
+        CHECK(std::isfinite(meas[5]) && std::isfinite(meas[9]));
+        CHECK(sobol_first_out_of_domain(meas, om, 4) == 3);                                // input 1: omax 0; input 3: 2e-290 * 9e307
+        const double big[4] = {1.0, 2.0, 3.0, 2.0};
+        CHECK(sobol_first_out_of_domain(meas, big, 4) == 1);                               // 2 * 2 * 0.95 DBL_MAX = +inf: refused
+        const double none[4] = {0.0, 0.0, 0.0, 0.0};
+        CHECK(sobol_first_out_of_domain(meas, none, 4) == -1);
+    }
+}
+
 // every block of the triangle once, in row-major order; no run longer than kseg; the count agrees
 static void check_units(int nb, int kseg) {
     std::vector<int> u;
@@ -86,6 +126,7 @@ static void check_schedule() {
 
 int main() {
     check_measure();
+    check_domain();
     check_schedule();
     if (failures) std::printf("%d checks failed\n", failures);
     else std::printf("ok\n");
