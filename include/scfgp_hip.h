@@ -375,7 +375,9 @@ int scfgp_predict_cov(scfgp_ctx* ctx, const double* Xa, int64_t Ta, const double
  * state of the context survives (resident rows, exchange buffers, Li / B of the last evaluation, optimiser state, precision level).
  * SCFGP_EARG (with a scfgp_last_error text, before any device work) for NULL pointers, n < 1, a bad mode, a missing X scaler in mode 1 or
  * parameters not set; SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if the Cholesky of S fails: the outputs are
- * untouched in all three cases.  Out of scope: a communicator / row-sharded form (the update is replicated work on n rows: every rank
+ * untouched in all three cases.  S has eigenvalues >= 1 in exact arithmetic; in SCFGP_F32 / SCFGP_F16X3 contexts C^T C carries an error of
+ * eps32 |S|, so the Cholesky can fail once |S| nears 1 / eps32 (seen at lam_max(S) = 9e8: 46 rows joining a fit of 16 at a = -7, b = 3).
+ * Out of scope: a communicator / row-sharded form (the update is replicated work on n rows: every rank
  * calls it with the same rows) and keeping the factors resident on the device between calls.  Removing observations: scfgp_forget. */
 int scfgp_condition(scfgp_ctx* ctx, const double* Xn, const double* yn, int64_t n, const double* alpha, const double* Li, int mode,
                     double* alpha_out, double* Li_out);
@@ -472,7 +474,12 @@ int scfgp_forget(scfgp_ctx* ctx, const double* Xo, const double* yo, int64_t n, 
  * n >= 1 without limit: the rows go through in chunks of floor(32768 / block) whole blocks, so device memory does not grow with n.  A
  * row's outputs depend on the rows of its own block only, bit for bit (not on n, the chunk or the block's position).  C runs in the
  * context's precision (SCFGP_F16X3 contexts run fp32 mode's kernels and agree with it bit for bit); H = C C^T is formed by fp64 MFMA and
- * everything after it is fp64.  The training state of the context survives (resident rows, exchange buffers, optimiser state, precision
+ * everything after it is fp64.  Accuracy goes with 1 / (1 - lam_max(H_I)): |D mu|, |D sigma| stay within a modest multiple of
+ * u sigma / (1 - lam_max) with u = 2^-53 in SCFGP_F64 contexts and eps32 = 2^-24 in SCFGP_F32 / SCFGP_F16X3 ones (measured down to
+ * 1 - lam_max = 6e-9 in fp64).  In SCFGP_F32 / SCFGP_F16X3 contexts rows that ARE in the fit can draw SCFGP_ENOTPD once 1 - lam_max
+ * approaches eps32 || |C||C|^T ||: seen at 1 - lam_max = 2e-8 with 62 rows of a K = 64 fit in one block and, where C has large cancelling
+ * entries (a = -7, b = 3), already at 4e-7 for single rows, while 4e-6 still went through; stats[5] near 1 is the warning.  The training
+ * state of the context survives (resident rows, exchange buffers, optimiser state, precision
  * level).  SCFGP_EARG (with a scfgp_last_error text, before any device work) for bad pointers, mode or block, a missing X scaler in mode
  * 1, no resident rows, or parameters not set; SCFGP_ENONFINITE for non-finite rows, targets or factors; SCFGP_ENOTPD if some I - H has no
  * Cholesky factor (the rows were not in the fit): the message names the first such block.  On these two stats is untouched and mu, std,

@@ -157,7 +157,7 @@ struct scfgp_ctx {
     // ... and those of scfgp_condition, allocated by its first call (ensure_update): the update stage's own K x K matrices (fp64: the old
     // factor, S / Li', M, M^-1, S^-1; typed: Li^T), its vectors [alpha | gamma | alpha' | 32 partial sums] (Kp each), the summed and the
     // per-chunk [packed C^T C | C^T r], targets and residuals of a chunk, the Gram launch's slabs, row weights and queue heads
-    // (u_flag: [0] Cholesky flag, [1] non-finite flag, [8..15] queue heads)
+    // (u_flag: [0] Cholesky flag, [1] non-finite input, [2] non-finite output of the K x K stage, [8..15] queue heads)
     double *u_Li = nullptr, *u_S = nullptr, *u_Lm = nullptr, *u_Mi = nullptr, *u_Si = nullptr, *u_vec = nullptr, *u_acc = nullptr, *u_part = nullptr;
     double *u_y = nullptr, *u_r = nullptr, *u_slabs = nullptr; size_t u_slabs_bytes = 0;
     void* u_LiT = nullptr; float* u_ws2 = nullptr; int* u_flag = nullptr;

@@ -135,15 +135,18 @@ static int update_finish(scfgp_ctx* c, RowFeed& feed, const char* who, const cha
     const Fail fail = {c, who};
     const KUpdate k = update_buffers(c);
     kstage_update(k, c->st);
-    update_check_finite(c->u_S, K2, c->u_flag, c->st);
-    update_check_finite(k.alpha_out, Kp, c->u_flag, c->st);
+    // u_flag[1]: what went in; u_flag[2]: what came out, as in scfgp_forget: a factorisation that failed leaves NaN behind, which is
+    // u_flag[0]'s to tell (an fp32 context's C^T C is off by eps32 |S|, which reaches the unit eigenvalues of S once |S| nears 1 / eps32)
+    update_check_finite(c->u_S, K2, c->u_flag + 1, c->st);
+    update_check_finite(k.alpha_out, Kp, c->u_flag + 1, c->st);
     update_store_factor(c->u_S, g0.K, g0.Kp, feed.raw, c->st);
     HIPCHK(c, hipGetLastError());
-    int flags[2] = {0, 0};
+    int flags[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(flags, c->u_flag, sizeof(flags), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
     if (flags[1]) return fail.nonfinite(std::string("non-finite rows, ") + what + " or factors");
     if (flags[0]) return fail.set("I + C^T C is not positive definite", SCFGP_ENOTPD);
+    if (flags[2]) return fail.nonfinite("the updated factors are not finite");
     HIPCHK(c, hipMemcpyAsync(Li_out, feed.raw, sizeof(double) * g0.K * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(alpha_out, k.alpha_out, sizeof(double) * g0.K, hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipStreamSynchronize(c->st));
